@@ -187,21 +187,46 @@ pregather_backward_kernel(int c, int n, int m, int ns, OperandB op,
   float v[CHUNK];
 #pragma clang loop unroll(full)
   for (int j = 0; j < CHUNK; ++j) v[j] = row[e[j] & (CHUNK * 1024 - 1)];
-  unsigned cur = e[0] >> 16;
-  float sum = v[0];
-  bool shared_run = true;  // the lane's first run may have begun in the lane before
+  // A lane's runs: the first (which may have begun in the lanes before), the inner ones (its own:
+  // stored), the last (which may go on in the lanes after).  The runs that cross lanes are summed
+  // by the lane they begin in, adding the partial sums of the following lanes in lane order -- the
+  // same order in every run (LDS atomics from several waves added them in scheduling order).
+  constexpr unsigned kPad = 0xFFFFFFFFu >> 16;
+  unsigned cur = e[0] >> 16, head_key = cur;
+  float sum = v[0], head_sum = 0.f;
+  bool single = true;  // one run over the whole lane: head == tail
 #pragma clang loop unroll(full)
   for (int j = 1; j < CHUNK; ++j) {
     const unsigned key = e[j] >> 16;
     if (key != cur) {
-      if (shared_run) atomicAdd(&acc[cur], sum); else acc[cur] = sum;
-      shared_run = false;
+      if (single) head_sum = sum; else acc[cur] = sum;
+      single = false;
       sum = 0.f;
       cur = key;
     }
     sum = __fadd_rn(sum, v[j]);
   }
-  if (cur != (0xFFFFFFFFu >> 16)) atomicAdd(&acc[cur], sum);  // may continue in the next lane
+  if (single) head_sum = sum;
+  __syncthreads();  // every lane has read its values: the staged row becomes the lanes' table
+  unsigned *t_head_key = reinterpret_cast<unsigned *>(row);
+  unsigned *t_tail_key = t_head_key + kPgThreads;
+  float *t_head_sum = row + 2 * kPgThreads;
+  unsigned *t_single = t_head_key + 3 * kPgThreads;
+  t_head_key[tid] = head_key;
+  t_tail_key[tid] = cur;
+  t_head_sum[tid] = head_sum;
+  t_single[tid] = single;
+  __syncthreads();
+  const bool continued = tid > 0 && t_tail_key[tid - 1] == head_key;
+  if (!single && !continued && head_key != kPad) acc[head_key] = head_sum;
+  if (!(single && continued) && cur != kPad) {  // the last run begins in this lane
+    float total = sum;
+    for (int l = tid + 1; l < kPgThreads && t_head_key[l] == cur; ++l) {
+      total = __fadd_rn(total, t_head_sum[l]);
+      if (!t_single[l]) break;
+    }
+    acc[cur] = total;
+  }
   __syncthreads();
   for (int t = tid; t < n; t += kPgThreads) dst[t] = acc[t];
 }

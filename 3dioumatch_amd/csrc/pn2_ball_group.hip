@@ -339,8 +339,8 @@ int inverse_chunk(int mns) {
 // its quads are loaded before the first LDS atomic (one trip to the L2 instead of one per pass
 // and element) and equal neighbours inside a quad are counted and ranked as ONE run: first-hit
 // padding repeats an index up to nsample times in a row, and every repeat was a same-address LDS
-// atomic (32 us at SA2's 8 x 1024 x 32; the order of a point's entries is free -- the sorted
-// backward adds them up whatever it is).
+// atomic (32 us at SA2's 8 x 1024 x 32).  The order of a point's entries is the order its sums
+// are formed in, so it must not depend on the scheduling of the waves (below).
 template <bool VEC>
 __global__ void __launch_bounds__(1024)
 group_inverse_kernel(int n, int mns, int chunk_log2, const int *__restrict__ idx,
@@ -410,27 +410,35 @@ group_inverse_kernel(int n, int mns, int chunk_log2, const int *__restrict__ idx
   auto put = [&](int s, int k, int e) {
     (VEC ? stage : out)[((s & chunk_mask) << 10) + (s >> chunk_log2)] = ((unsigned)k << 16) | (unsigned)e;
   };
-  if (VEC) {
+  // The slots are drawn one wave at a time: within a wave the order of the returning atomics is
+  // fixed, so a point's entries take the same order in every run and the sorted backward adds them
+  // up in the same order (with the waves racing, a point's sum changed at round-off from run to run).
+  for (int phase = 0; phase < 16; ++phase) {
+    if (w == phase) {
+      if (VEC) {
 #pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      if (v[q].x < 0) continue;
-      int len[4];
-      runs(v[q], len);
-      const int k[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
-      const int e = (q * 1024 + tid) * 4;
-      int s = 0;
+        for (int q = 0; q < Q; ++q) {
+          if (v[q].x < 0) continue;
+          int len[4];
+          runs(v[q], len);
+          const int k[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+          const int e = (q * 1024 + tid) * 4;
+          int s = 0;
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (len[u] > 0) s = atomicAdd(&cnt[k[u]], len[u]);  // a run's first element draws its slots
-        put(s, k[u], e + u);
-        ++s;
+          for (int u = 0; u < 4; ++u) {
+            if (len[u] > 0) s = atomicAdd(&cnt[k[u]], len[u]);  // a run's first element draws its slots
+            put(s, k[u], e + u);
+            ++s;
+          }
+        }
+      } else {
+        for (int e = tid; e < mns; e += 1024) {
+          const int k = ib[e];
+          put(atomicAdd(&cnt[k], 1), k, e);
+        }
       }
     }
-  } else {
-    for (int e = tid; e < mns; e += 1024) {
-      const int k = ib[e];
-      put(atomicAdd(&cnt[k], 1), k, e);
-    }
+    __syncthreads();
   }
   for (int s = mns + tid; s < (1024 << chunk_log2); s += 1024)
     (VEC ? stage : out)[((s & chunk_mask) << 10) + (s >> chunk_log2)] = kInvPad;

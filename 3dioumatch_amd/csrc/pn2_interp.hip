@@ -281,18 +281,22 @@ three_interpolate_affine_lds_kernel(int c, int m, int n, const float *__restrict
 
 // Scatter-add with the CPW destination rows privatised in LDS (ds_add_f32), written back once:
 // no global atomics and no pre-zeroing (the global-atomic kernel below remains for large m).
+// Every wave adds into its own copy of the rows and the four copies are summed in wave order, so
+// the result does not depend on how the waves are scheduled (with one shared copy the order of
+// the waves' atomics -- and so the round-off of the sums -- changed from run to run).
 template <int CPW>
 __global__ void __launch_bounds__(256)
 three_interpolate_grad_lds_kernel(int c, int n, int m, const float *__restrict__ grad_out,
                                   size_t g_bstride, const int *__restrict__ idx,
                                   const float *__restrict__ weight,
                                   float *__restrict__ grad_points) {
-  extern __shared__ __attribute__((aligned(16))) float rows[];
+  extern __shared__ __attribute__((aligned(16))) float lds[];
   const BlockId blk = xcd_block_id();
   const int b = blk.y, l0 = blk.x * CPW;
   const int nc = c - l0 < CPW ? c - l0 : CPW;
-  for (int t = threadIdx.x; t < nc * m; t += 256) rows[t] = 0.f;
+  for (int t = threadIdx.x; t < 4 * CPW * m; t += 256) lds[t] = 0.f;
   __syncthreads();
+  float *rows = lds + (threadIdx.x >> 6) * CPW * m;  // this wave's copy
   for (int j = threadIdx.x; j < n; j += 256) {
     const int *ib = idx + ((size_t)b * n + j) * 3;
     const float *wb = weight + ((size_t)b * n + j) * 3;
@@ -311,7 +315,9 @@ three_interpolate_grad_lds_kernel(int c, int n, int m, const float *__restrict__
   }
   __syncthreads();
   float *dst = grad_points + ((size_t)b * c + l0) * m;
-  for (int t = threadIdx.x; t < nc * m; t += 256) dst[t] = rows[t];
+  const int span = CPW * m;
+  for (int t = threadIdx.x; t < nc * m; t += 256)
+    dst[t] = __fadd_rn(__fadd_rn(__fadd_rn(lds[t], lds[span + t]), lds[2 * span + t]), lds[3 * span + t]);
 }
 
 // grad_points[b,l,i_t] += grad_out[b,l,j] * w_t   (interpolate_gpu.cu:121-148)
@@ -396,12 +402,12 @@ static int interpolate_grad_run(int b, int c, int n, int m, const float *grad_ou
                                 const int *idx, const float *weight, float *grad_points,
                                 hipStream_t stream) {
   if (b <= 0 || c <= 0 || m <= 0) return 0;
-  if (n > 0 && m <= 1024) {  // the destination rows of a workgroup fit its LDS
+  if (n > 0 && m <= 1024) {  // the destination rows of a workgroup, one copy per wave, fit 64 KB
     // 4 channels per workgroup: the FP layers' 256 channels x 8 clouds are 512 workgroups (16
     // channels each left half the CUs idle with one 4-wave workgroup on the others: 50 us)
     constexpr int CPW = 4;
     hipLaunchKernelGGL(three_interpolate_grad_lds_kernel<CPW>, dim3(pn2_ceil_div(c, CPW), b),
-                       dim3(256), sizeof(float) * (size_t)CPW * m, stream, c, n, m, grad_out,
+                       dim3(256), sizeof(float) * 4 * (size_t)CPW * m, stream, c, n, m, grad_out,
                        g_bstride, idx, weight, grad_points);
     return pn2_launch_status();
   }

@@ -1,8 +1,22 @@
 #!/usr/bin/env python
 """bench.py -- scenes/sec of the VoteNet-IoU supervised train step (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run only measures the headline: it sets up, warms up, times K steps of the loop that feeds
+data (`value`, `ms_per_step`), writes the outputs of the last timed step when --dump-outputs DIR is
+given, and prints the result line.  --full adds everything else the line can carry (below): the
+resident-batch loop, the host time per step, the step without the prefetched index chain, the
+per-operator table and roofline, the two other workloads and the CPU baseline.
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller -- the loss,
+every tensor of its end_points, the parameters after its update (and the EMA teacher's, semi) --
+as DIR/<name>.npy in float32 (float64 for float64 and integer tensors), at most 64 MB in all:
+where the whole set is larger, the biggest arrays are cut to one byte budget each by a fixed
+seeded sample of their flattened elements (1-D in the file).  The inputs are seeded, so two runs
+with the same arguments compute on identical data, and the step is deterministic: they write the
+same outputs.
 
 One STEP = one pass of the hot path over one synthetic batch, i.e. the reference's
 pretrain.py:train_one_epoch body (pretrain.py:310-347) at BASELINE config 2:
@@ -14,7 +28,7 @@ region.  N > 1: one process per GPU, same per-GPU batch (weak scaling); the data
 exchange is ONE all_reduce of the flat 4.26 MB gradient buffer per step (RCCL by default,
 --backend gloo for a CPU-mediated run), between the backward graph and the Adam graph.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     -- the north-star pair ball_query + group_points(xyz) + group_points(feat) at B=8,
                   N=40000, m=2048, nsample=64: algorithmic bytes (38 516 736 B)
                   / measured duration (events on the launch stream around HIP-graph replays) vs
@@ -25,6 +39,9 @@ The JSON line also carries
   kernels      -- every hot-path kernel at the config-2 shapes: us, algorithmic bytes or flops,
                   the bound, the fraction of that roofline;
   ms_per_step_no_prefetch -- the same step with the coordinate-only index chain run inline;
+  value_resident, ms_per_step_resident, host_ms_per_step -- the resident-batch loop, and the
+                  host time per iteration with the device drained between iterations;
+  workloads    -- short passes of the two other BASELINE workloads (N=1, pretrain only);
   cpu_baseline -- the same train step on the host cores with the oracle (OpenMP build) behind
                   the same Python modules, on a bounded sample (B=1), rank 0 / N=1 only.
 """
@@ -65,10 +82,16 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: resident loop, host time per step, "
+                         "step without prefetch, per-operator table + roofline, the two other workloads, "
+                         "CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline")
+    ap.add_argument("--no-kernels", action="store_true", help="(--full) no per-operator table / roofline")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="skip the short passes of the two other BASELINE workloads (N = 1 default run)")
+                    help="(--full) skip the short passes of the two other BASELINE workloads (N = 1 run)")
     ap.add_argument("--workload", choices=("pretrain", "semi", "sunrgbd"), default="pretrain",
                     help="pretrain = BASELINE configs[1] (the headline metric); semi = configs[3]: "
                          "stage-2 step, 4 labeled + 8 unlabeled scenes per GPU, EMA teacher; "
@@ -104,11 +127,61 @@ def build_step(V, cfg, device, world, local_rank, workload="pretrain"):
                                   graphs_fallback=True)  # reported as config.hip_graphs
 
     def step(batch):
-        return runner(batch)[0]
+        step.last = runner(batch)  # (loss, end_points) of the latest step, for --dump-outputs
+        return step.last[0]
 
     step.prefetch = runner.prefetch_geometry
     step.runner = runner
+    step.last = None
     return step
+
+
+DUMP_LIMIT = 64 * 2 ** 20  # bytes of .npy files in all
+NPY_HEADER = 256  # an upper bound of the header of one .npy file
+
+
+def dump_outputs(dirname, step):
+    """What the latest step handed its caller, as dirname/<name>.npy: `loss`, `end_points.<key>`
+    for every tensor of its end_points, `parameters` after its update (and `teacher_parameters`,
+    the EMA teacher of the semi-supervised step).  float32, or float64 for float64 and integer
+    tensors.  Above DUMP_LIMIT in all, the biggest arrays are cut to one common byte budget each by
+    a fixed seeded sample of their flattened elements (sorted indices, saved 1-D)."""
+    loss, end_points = step.last
+    tensors = {"loss": loss}
+    tensors.update(("end_points." + k, v) for k, v in end_points.items() if torch.is_tensor(v))
+    tensors["parameters"] = step.runner.flat_params
+    if getattr(step.runner, "flat_teacher", None) is not None:
+        tensors["teacher_parameters"] = step.runner.flat_teacher
+    arrays = {}
+    for name, t in sorted(tensors.items()):
+        t = t.detach()
+        dtype = torch.float32 if t.is_floating_point() and t.element_size() <= 4 else torch.float64
+        arrays[name] = t.to(device="cpu", dtype=dtype).numpy()
+    # the largest per-array budget that keeps the whole set under the limit (water-filling over
+    # the sizes in ascending order)
+    room = DUMP_LIMIT - NPY_HEADER * len(arrays)
+    sizes = sorted(a.nbytes for a in arrays.values())
+    cap = sizes[-1]
+    for i, s in enumerate(sizes):
+        share = room // (len(sizes) - i)
+        if s > share:
+            cap = share
+            break
+        room -= s
+    os.makedirs(dirname, exist_ok=True)
+    sampled, total = [], 0
+    for name, a in arrays.items():
+        if a.nbytes > cap:
+            keep = cap // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+            sampled.append(name)
+        path = os.path.join(dirname, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    assert total <= DUMP_LIMIT, total
+    print("bench.py: %d arrays of the last timed step in %s (%.1f MB; sampled: %s)"
+          % (len(arrays), dirname, total / 2 ** 20, ", ".join(sampled) or "none"), file=sys.stderr)
 
 
 TIME_OP_EAGER = []  # names of operators whose graph capture failed (timed as an eager loop)
@@ -468,16 +541,16 @@ def main():
 
     step = build_step(V, cfg, device, world, local_rank, args.workload)
     step.runner.time_exchange = world > 1  # events around every eager gradient all-reduce
-    if args.workload == "semi":
-        scenes = SEMI_LABELED + SEMI_UNLABELED
+    rotate = max(0, args.rotate)
+    # the resident-batch loop runs with --full, or as the headline loop when --rotate 0
+    resident = args.full or rotate == 0
+    scenes = SEMI_LABELED + SEMI_UNLABELED if args.workload == "semi" else 16 if args.workload == "sunrgbd" else B
+    batch = None
+    if resident and args.workload == "semi":
         batch = data.make_semi_batch(SEMI_LABELED, SEMI_UNLABELED, NPTS, cfg, seed=100 + rank,
                                      device=device)
-    elif args.workload == "sunrgbd":
-        scenes = 16
-        batch = data.make_batch(scenes, npts, cfg, seed=100 + rank, device=device)
-    else:
-        scenes = B
-        batch = data.make_batch(B, NPTS, cfg, seed=100 + rank, device=device)  # resident in HBM
+    elif resident:
+        batch = data.make_batch(scenes, npts, cfg, seed=100 + rank, device=device)  # resident in HBM
 
     def fence():
         if world > 1:
@@ -491,7 +564,7 @@ def main():
     # one prefetched during the last timed step is consumed after it).
     pipelined = not args.no_prefetch
 
-    def timed_loop(step, batch, steps, warmup):
+    def timed_loop(step, batch, steps, warmup, after_timed=None):
         views = [dict(batch), dict(batch)]  # two views of the resident batch: current / next
         if pipelined:
             step.prefetch(views[0])
@@ -511,14 +584,17 @@ def main():
         elapsed = time.perf_counter() - t0
         if not bool(torch.isfinite(history).all()):
             raise RuntimeError("non-finite loss during the timed steps")
+        if after_timed is not None:
+            after_timed()
         return elapsed, views
 
-    def rotating_loop(step, host_batches, steps, warmup):
+    def rotating_loop(step, host_batches, steps, warmup, after_timed=None, host_pass=True):
         """The timed loop of a training run that FEEDS data: K distinct batches in pinned host
         memory, three device-side input sets; iteration i copies batch i+2 host -> device on a
         copy stream (its set was last read by step i-1), prefetches the index chain of batch i+1
-        and runs step i.  Also returns the host time per iteration measured in a second pass with
-        the device idle-waited between iterations (Python + launch time only)."""
+        and runs step i.  after_timed() runs right after the timed steps.  host_pass: also returns
+        the host time per iteration measured in a second pass with the device idle-waited between
+        iterations (Python + launch time only), and leaves no prefetched slot pending."""
         k = len(host_batches)
         # ONE copy stream per process: HIP maps streams onto a few hardware queues, and a later workload's
         # fresh stream was seen to share a queue with the step's own streams (the semi-supervised
@@ -589,6 +665,12 @@ def main():
             one(i, history)
         fence()
         elapsed = time.perf_counter() - t0
+        if not bool(torch.isfinite(history[:warmup + steps]).all()):
+            raise RuntimeError("non-finite loss during the timed steps")
+        if after_timed is not None:
+            after_timed()
+        if not host_pass:
+            return elapsed, None, h2d_bytes
         # host time per iteration: the same calls with the device drained between iterations, so the
         # host never waits on a full queue -- what one rank's Python + launches cost per step
         host = 0.0
@@ -606,8 +688,11 @@ def main():
             fence()
         return elapsed, host / steps, h2d_bytes
 
-    rotate = max(0, args.rotate)
-    elapsed_rot = host_ms = h2d_bytes = None
+    def dump():  # the outputs of the headline loop's last timed step, before anything else runs
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, step)
+
+    elapsed = elapsed_rot = host_ms = h2d_bytes = None
     if rotate > 0:
         def make(seed):
             if args.workload == "semi":
@@ -615,18 +700,24 @@ def main():
             return data.make_batch(scenes, npts, cfg, seed=seed)
         host_batches = [{key: v.pin_memory() for key, v in make(100 + rank * rotate + j).items()
                          if torch.is_tensor(v)} for j in range(rotate)]
-        elapsed_rot, host_s, h2d_bytes = rotating_loop(step, host_batches, args.steps, args.warmup)
-        host_ms = host_s * 1e3
-    elapsed, views = timed_loop(step, batch, args.steps, args.warmup)
+        elapsed_rot, host_s, h2d_bytes = rotating_loop(step, host_batches, args.steps, args.warmup,
+                                                       after_timed=dump, host_pass=resident)
+        host_ms = None if host_s is None else host_s * 1e3
+    if resident:
+        elapsed, views = timed_loop(step, batch, args.steps, args.warmup,
+                                    after_timed=dump if rotate == 0 else None)
     rccl = None
     if world > 1:
         # MAX over ranks of both timed loops (and of the host time per step)
-        t = torch.tensor([elapsed, elapsed_rot if elapsed_rot is not None else 0.0, host_ms or 0.0],
+        t = torch.tensor([elapsed or 0.0, elapsed_rot or 0.0, host_ms or 0.0],
                          device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        elapsed = float(t[0].item())
+        if elapsed is not None:
+            elapsed = float(t[0].item())
         if elapsed_rot is not None:
-            elapsed_rot, host_ms = float(t[1].item()), float(t[2].item())
+            elapsed_rot = float(t[1].item())
+        if host_ms is not None:
+            host_ms = float(t[2].item())
         # what the N > 1 line needs to be checked from outside: the collective's backend, the
         # width of the process group, which device every rank drove, the gradient all-reduce's
         # device time (median over the warm-up + timed steps of rank 0)
@@ -641,7 +732,7 @@ def main():
     # the same step with the index chain inline (not part of `value`): what the one-step-ahead
     # prefetch of the coordinate-only chain hides
     ms_inline = None
-    if pipelined and world == 1:
+    if args.full and pipelined and world == 1:
         extra = max(2, args.steps // 2)
         step(views[(args.warmup + args.steps) % 2])  # consumes the last prefetched slot
         fence()
@@ -652,7 +743,6 @@ def main():
         ms_inline = (time.perf_counter() - t1) * 1e3 / extra
 
     if rank == 0:
-        ms_res = elapsed * 1e3 / args.steps
         timed = elapsed_rot if elapsed_rot is not None else elapsed  # the loop `value` is quoted on
         ms = timed * 1e3 / args.steps
         out = {
@@ -661,18 +751,14 @@ def main():
             "value": round(scenes * world * args.steps / timed, 3), "unit": "scenes/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms, 3),
-            # the loop of rounds 1-4: ONE batch resident in HBM, replayed (no host -> device copy)
-            "value_resident": round(scenes * world * args.steps / elapsed, 3),
-            "ms_per_step_resident": round(ms_res, 3),
+            "full": args.full,
             "rotate": rotate,
-            "host_ms_per_step": None if host_ms is None else round(host_ms, 3),
             "h2d_bytes_per_step": h2d_bytes,
             "timed_loop": ("%d distinct batches (seeds %d..%d) in pinned host memory, batch i+2 copied "
                            "host -> device on a copy stream inside the timed region, index chain of "
                            "batch i+1 prefetched, step i" % (rotate, 100 + rank * rotate,
                                                              100 + rank * rotate + rotate - 1))
             if rotate > 0 else "one batch resident in HBM, replayed",
-            "ms_per_step_no_prefetch": None if ms_inline is None else round(ms_inline, 3),
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32",
             "products": "3xbf16 split: every fp32 product of the shared-MLP GEMMs = 6 x "
@@ -684,9 +770,15 @@ def main():
                        "fps_prefetch_one_step_ahead": pipelined,
                        "hip_graphs": bool(step.runner.graphs)},
         }
+        if args.full:
+            # the loop of rounds 1-4: ONE batch resident in HBM, replayed (no host -> device copy)
+            out["value_resident"] = round(scenes * world * args.steps / elapsed, 3)
+            out["ms_per_step_resident"] = round(elapsed * 1e3 / args.steps, 3)
+            out["host_ms_per_step"] = None if host_ms is None else round(host_ms, 3)
+            out["ms_per_step_no_prefetch"] = None if ms_inline is None else round(ms_inline, 3)
         if rccl is not None:
             out["rccl"] = rccl
-        if not args.no_kernels:
+        if args.full and not args.no_kernels:
             table, forms = kernel_table(device)
             # headline = the SLOWEST of the three clouds the kernel is quoted on (cloud U(L), cloud R,
             # the timed step's own batch); the per-cloud durations are all in `forms`
@@ -778,7 +870,7 @@ def main():
                                    "PAIR_BYTES always counts the unfused 38.5 MB"}
             out["kernels"] = table
             out["time_op_eager_fallbacks"] = TIME_OP_EAGER
-        if world == 1 and args.workload == "pretrain" and not args.no_workloads:
+        if args.full and world == 1 and args.workload == "pretrain" and not args.no_workloads:
             # the two other single-GPU workloads of BASELINE.json, short passes OUTSIDE the headline
             # timed region (configs[2]: SUN RGB-D pretrain; configs[3]: the semi-supervised step)
             del step
@@ -824,7 +916,7 @@ def main():
                         "picked": wstep.runner._teacher_probe_pick}
                 del wstep, wbatch
                 torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline and args.workload == "pretrain":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "pretrain":
             out["cpu_baseline"] = cpu_baseline(V, cfg)
         if "workloads" in out:  # (kept behind the contract's keys in the printed line)
             out["workloads"] = out.pop("workloads")

@@ -9,7 +9,7 @@ Part 2 (iou_bev_cpu_ref.npz): outputs of the REFERENCE's own compiled CPU code
    (oracle/_ref/libiou3d_ref.so, built from OpenPCDet/pcdet/ops/iou3d_nms/src/iou3d_cpu.cpp
    by `make -C oracle ref`): BEV overlap (box_overlap) and BEV IoU (boxes_iou_bev_cpu) for
    oriented, axis-aligned and known-answer boxes.  These pin oracle/iou3d_oracle.c to the
-   reference bit-for-bit.
+   reference bit-for-bit.  iou_bev_cpu_ref_seeds.npz: the same on six more box pairs.
 Part 3 (iou3d_nms_oracle.npz): 3-D IoU matrix and NMS results of the oracle (no reference CPU
    form exists for the wrapper epilogue / NMS kernels).
 Only DATA is stored (inputs and expected outputs).
@@ -120,6 +120,25 @@ def part2():
     save("iou_bev_cpu_ref.npz", **out)
 
 
+def part2_seeds():
+    """iou_bev_cpu_ref_seeds.npz: the same two reference functions on boxes_pair(80) of seeds
+    11-13, oriented and axis-aligned (the cases of test_iou_oracle_bitexact_vs_live_reference)."""
+    if not have_reference():
+        print("oracle/_ref not built (no reference sources?) -- skipping part 2 (seeds)")
+        return
+    ref = Reference()
+    out = {}
+    for seed in (11, 12, 13):
+        for aligned in (False, True):
+            tag = "%d_%s" % (seed, "aligned" if aligned else "oriented")
+            a, b = synth.boxes_pair(80, seed=seed, axis_aligned=aligned)
+            out["a_" + tag] = a
+            out["b_" + tag] = b
+            out["overlap_" + tag] = ref.box_overlap(a, b)
+            out["iou_bev_" + tag] = ref.boxes_iou_bev_cpu(a, b)
+    save("iou_bev_cpu_ref_seeds.npz", **out)
+
+
 def part3():
     a, b = synth.boxes_pair(96, seed=5)
     ka, kb = synth.box_kats()
@@ -138,4 +157,5 @@ def part3():
 if __name__ == "__main__":
     part1()
     part2()
+    part2_seeds()
     part3()

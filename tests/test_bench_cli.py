@@ -1,11 +1,14 @@
 """bench.py end to end on the GPU: the JSON contract of the default workload and the two other
-BASELINE workloads (short runs)."""
+BASELINE workloads (short runs, --full), the lean plain run and its --dump-outputs; on the CPU,
+the output dump's size limit."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 from conftest import ROOT
 
@@ -22,7 +25,7 @@ def _run(*flags):
 
 @pytest.mark.gpu
 def test_bench_default_line_has_roofline_and_cpu_baseline():
-    d = _run()
+    d = _run("--full")
     assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
     assert d["unit"] == "scenes/s" and d["value"] > 0 and d["higher_is_better"] is True
     assert d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "f32"
@@ -86,7 +89,7 @@ def test_bench_default_line_has_roofline_and_cpu_baseline():
 @pytest.mark.gpu
 @pytest.mark.parametrize("workload,scenes", [("semi", 12), ("sunrgbd", 16)])
 def test_bench_other_workloads(workload, scenes):
-    d = _run("--workload", workload, "--no-kernels", "--no-cpu-baseline")
+    d = _run("--full", "--workload", workload, "--no-kernels", "--no-cpu-baseline")
     assert "workloads" not in d and d["rotate"] == 4 and d["host_ms_per_step"] > 0
     assert REQUIRED <= set(d) and d["config"]["per_gpu_batch"] == scenes
     assert d["config"]["hip_graphs"] is True and d["value"] > 0
@@ -102,7 +105,7 @@ def test_bench_two_ranks_line_is_self_verifying():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port),
                         os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--backend", "gloo", "--no-kernels", "--no-cpu-baseline"],
+                        "--backend", "gloo", "--full", "--no-kernels", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -124,6 +127,68 @@ def test_bench_two_ranks_line_is_self_verifying():
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert bad.returncode != 0 and "process group of 2 ranks" in bad.stderr
 
+
+FULL_ONLY = {"value_resident", "ms_per_step_resident", "host_ms_per_step", "ms_per_step_no_prefetch",
+             "roofline", "kernels", "time_op_eager_fallbacks", "workloads", "cpu_baseline"}
+
+
+def _dumped(path):
+    return {f[:-4]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path)) if f.endswith(".npy")}
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """A plain run measures the headline only and writes what its last timed step computed; the
+    same arguments with --full time the same steps on the same inputs before anything else."""
+    plain, full = str(tmp_path / "plain"), str(tmp_path / "full")
+    d = _run("--dump-outputs", plain)
+    assert REQUIRED <= set(d) and d["steps"] == 2 and d["warmup"] == 1 and d["full"] is False
+    assert not FULL_ONLY & set(d), FULL_ONLY & set(d)
+    assert d["rotate"] == 4 and abs(d["value"] - 8 * 1000.0 / d["ms_per_step"]) <= 0.02 * d["value"]
+    a = _dumped(plain)
+    assert sum(os.path.getsize(os.path.join(plain, f)) for f in os.listdir(plain)) <= 64 * 2 ** 20
+    assert {"loss", "parameters", "end_points.point_clouds", "end_points.center"} <= set(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert np.isfinite(a["loss"]) and a["parameters"].size == 1063985
+    d = _run("--full", "--no-kernels", "--no-workloads", "--no-cpu-baseline", "--dump-outputs", full)
+    assert d["full"] is True and d["value_resident"] > 0
+    b = _dumped(full)
+    assert set(a) == set(b) and all(a[k].shape == b[k].shape for k in a)
+    # the same inputs (batch 2 of the rotation, seed 102) and the same outputs, array for array: the
+    # step is deterministic, so a run computes what any other run with these arguments computes
+    differ = [k for k in a if not np.array_equal(a[k], b[k])]
+    assert not differ, differ
+
+
+def test_dump_outputs_stays_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: dtypes, names, and the byte limit kept by a fixed sample of the biggest arrays."""
+    import bench
+
+    class Runner(object):
+        flat_params = torch.nn.Parameter(torch.arange(5000, dtype=torch.float32))
+
+    def step():
+        pass
+    step.runner = Runner()
+    g = torch.Generator().manual_seed(0)
+    step.last = (torch.tensor(1.5), {"big": torch.rand(3, 20000, generator=g), "small": torch.rand(7, generator=g),
+                                     "inds": torch.arange(40000, dtype=torch.int32), "labeled_num": 4,
+                                     "half": torch.ones(10, dtype=torch.float16)})
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 200000)
+    for out in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / out), step)
+    a, b = _dumped(str(tmp_path / "a")), _dumped(str(tmp_path / "b"))
+    assert set(a) == {"loss", "parameters", "end_points.big", "end_points.small", "end_points.inds",
+                      "end_points.half"}
+    assert sum(os.path.getsize(os.path.join(tmp_path, "a", f)) for f in os.listdir(tmp_path / "a")) <= 200000
+    assert a["end_points.inds"].dtype == np.float64 and a["end_points.half"].dtype == np.float32
+    assert a["end_points.big"].dtype == np.float32 and a["end_points.big"].ndim == 1
+    assert a["end_points.small"].shape == (7,) and np.array_equal(a["parameters"], np.arange(5000))
+    assert float(a["loss"]) == 1.5
+    # a sample is a subset of the array, the same one on every call
+    assert np.array_equal(a["end_points.big"], b["end_points.big"])
+    assert np.isin(a["end_points.big"], step.last[1]["big"].numpy()).all()
+    assert np.all(np.diff(a["end_points.inds"]) > 0)
 
 def test_bench_fails_loudly_without_a_gpu():
     """No CPU fallback in the measured path: on a machine without a GPU bench.py stops with a

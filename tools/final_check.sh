@@ -1,9 +1,11 @@
 #!/bin/bash
 # End-of-round check on the GPU box: full bench line, stress configuration, the GPU test suite, smoke.
+#     bash tools/final_check.sh OUTDIR
 export TMPDIR=/tmp
-mkdir -p gpurun_out/r6f
-timeout 900 python bench.py > gpurun_out/r6f/bench_line.json 2> gpurun_out/r6f/bench.err; echo "bench rc=$?"
-timeout 600 python tools/stress_bench.py gpurun_out/r6f/r6_stress_config5.json > gpurun_out/r6f/stress.log 2>&1; echo "stress rc=$?"
+O=${1:?usage: bash tools/final_check.sh OUTDIR}
+mkdir -p "$O"
+timeout 900 python bench.py --full > "$O"/bench_line.json 2> "$O"/bench.err; echo "bench rc=$?"
+timeout 600 python tools/stress_bench.py "$O"/stress_config5.json > "$O"/stress.log 2>&1; echo "stress rc=$?"
 timeout 2400 python -m pytest tests -q -m gpu -x 2>&1 | tail -3
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
 timeout 600 python tools/gram256_soak.py 100 2>&1 | tail -1

@@ -10,9 +10,9 @@ O=$ROOT/gpurun_out/${TAG}_profiles; mkdir -p $O
 P=/tmp/prof_$TAG; rm -rf $P; mkdir -p $P
 run() { name=$1; shift; timeout 240 "$@" > $O/$name.log 2>&1; echo "$name rc=$?"; }
 # -- the step, timed steps only
-run step rocprofv3 --kernel-trace --stats --output-format csv -d $P/step -o step -- python bench.py --steps 20 --warmup 5 --no-kernels --no-cpu-baseline --no-workloads
+run step rocprofv3 --kernel-trace --stats --output-format csv -d $P/step -o step -- python bench.py --full --steps 20 --warmup 5 --no-kernels --no-cpu-baseline --no-workloads
 python tools/step_breakdown.py $P/step/step_kernel_trace.csv 20 400 $O/${TAG}_train_step_timed_summary.csv > $O/step_breakdown.txt 2>&1
-run semi rocprofv3 --kernel-trace --stats --output-format csv -d $P/semi -o step -- python bench.py --workload semi --steps 20 --warmup 5 --no-kernels --no-cpu-baseline
+run semi rocprofv3 --kernel-trace --stats --output-format csv -d $P/semi -o step -- python bench.py --full --workload semi --steps 20 --warmup 5 --no-kernels --no-cpu-baseline
 python tools/step_breakdown.py $P/semi/step_kernel_trace.csv 20 400 $O/${TAG}_semi_step_timed_summary.csv > $O/semi_breakdown.txt 2>&1
 # -- the north-star pair: the `layer` form ALONE (one form per kernel name in every stats / counter file)
 run pair_stats rocprofv3 --kernel-trace --stats --output-format csv -d $P/pair -o pair -- python tools/pair_bench.py 10 --plain --only layer

@@ -3,7 +3,7 @@
 # streams, profiler-serialised): start offset, duration, kernel -> gpurun_out/step_trace_one.txt
 export TMPDIR=/tmp
 P=/tmp/sp; rm -rf $P; mkdir -p $P
-rocprofv3 --kernel-trace --output-format csv -d $P/step -o step -- python bench.py --steps 6 --warmup 3 --no-kernels --no-cpu-baseline --no-workloads > $P/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $P/step -o step -- python bench.py --full --steps 6 --warmup 3 --no-kernels --no-cpu-baseline --no-workloads > $P/log 2>&1
 python - <<'PY'
 import csv
 rows=list(csv.DictReader(open('/tmp/sp/step/step_kernel_trace.csv')))
