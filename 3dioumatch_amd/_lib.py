@@ -156,6 +156,8 @@ _SIGNATURES = {
     "votenet_loss_scratch_floats": [_vp],
     "votenet_bbox_jitter": [_c_int, _c_int, _c_int, _c_int] + [_vp] * 15,
     "votenet_gridconv_points": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "votenet_iou_opt_box_step": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _vp,
+                                 _vp, _vp, _vp, _vp, _vp, _c_float, _vp, _vp, _vp, _vp],
     "votenet_channel_normalize": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp],
     "votenet_channel_normalize_grad": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "votenet_adam_step": [ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,

@@ -154,6 +154,23 @@ int votenet_gridconv_points(int b, int k, int ctot, const float *unit, const flo
                             const float *size, const float *heading, float *whole, float *feats,
                             void *stream);
 
+/* test-time IoU optimisation (evaluate_with_opt, train.py:444-491): one ascent step of every box
+ * up the gradient of its own IoU logit, through the grid points, the three nearest seeds and their
+ * inverse-distance weights of models/grid_conv_module.py:64-105.  unit (64,3) the unit grid;
+ * seed_xyz (b,nseed,3); idx (b,k*64,3) int32 the three nearest seeds of every grid point;
+ * proj (b,ch,nseed) = W0[:, 3:] . seed features; w0 the first layer's weight, ldw0 its row stride
+ * (columns 0..2 = the relative-coordinate rows); dz (b,ch,k*64) the gradient at the first layer's
+ * output -- its raw GEMM output when y0 is NULL, else the gradient after BatchNorm + ReLU, with
+ * y0 (b,ch,k*64) that raw output and scale / shift / gain (ch) the eval-mode BatchNorm forward
+ * coefficients and gamma * invstd; heading (b,k).  center, size (b,k,3) are updated in place:
+ * += rate * dL/d(center, half size); grad (b,k,6) = (dL/dcenter, dL/dsize) unless NULL */
+int votenet_iou_opt_box_step(int b, int k, int nseed, int ch, const float *unit,
+                             const float *seed_xyz, const int *idx, const float *proj,
+                             const float *w0, int ldw0, const float *dz, const float *y0,
+                             const float *scale, const float *shift, const float *gain,
+                             const float *heading, float rate, float *center, float *size,
+                             float *grad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
