@@ -933,3 +933,76 @@ def pregather_backward(fly, inverse, n):
                                              invstd.data_ptr(), coef.data_ptr(), inverse.data_ptr(),
                                              out.data_ptr(), _stream(y)), "mlp_pregather_backward")
     return out
+
+
+# ---- eval-mode pooled shared MLP in one pass (csrc/mlp_eval_pool.hip) ----
+def eval_lin4_supported(b, c_in, c_mid, c_out, m, ns):
+    """Does eval_lin4_pool cover a c_in -> c_mid -> c_out module on a (b, c_in, m, ns) grouped input?"""
+    return bool(_lib.mlp_eval_lin4_supported(int(b), int(c_in), int(c_mid), int(c_out), int(m), int(ns)))
+
+
+def eval_stored_supported(b, c_in, c_mid, c_out, m, ns):
+    """Does eval_stored_pool cover the c_in -> c_mid -> c_out tail on a (b, c_in, m, ns) layer-0 output?"""
+    return bool(_lib.mlp_eval_stored_supported(int(b), int(c_in), int(c_mid), int(c_out), int(m), int(ns)))
+
+
+def fold_bn(bn):
+    """(scale, shift) of an eval-mode nn.BatchNorm: bn_coefficients(..., training=False), the same bits
+    the plain eval path uses.  Reads the parameters and running buffers, writes none of them."""
+    c = bn.num_features
+    placeholder = bn.weight.detach().view(1, c)  # (only its shape and device are read)
+    _, _, scale, shift = bn_coefficients(placeholder, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                         bn.momentum, bn.eps, False)
+    return scale, shift
+
+
+def eval_lin4_prepare(w0, coeff0, w1, w2, img=None):
+    """The weight image of eval_lin4_pool: w0 (64,4) with its folded BatchNorm coeff0 = (scale, shift),
+    w1 (64,64), w2 (128,64) (mlp_chain_lin4_prepare).  img: a previous image to fill in place."""
+    for t, name in ((w0, "w0"), (w1, "w1"), (w2, "w2")):
+        _f32c(t, name)
+    if img is None:
+        img = torch.empty(int(_lib.mlp_chain_lin4_image_bytes()), dtype=torch.uint8, device=w0.device)
+    with torch.cuda.device(w0.device):
+        _L.check(_lib.mlp_chain_lin4_prepare(w0.data_ptr(), coeff0[0].data_ptr(), coeff0[1].data_ptr(),
+                                             w1.data_ptr(), w2.data_ptr(), img.data_ptr(), _stream(w0)),
+                 "mlp_chain_lin4_prepare")
+    return img
+
+
+def eval_lin4_pool(x4, img, coeff1, coeff2):
+    """x4 (B,4,m,ns) -> pooled (B,128,m) of the eval-mode 4 -> 64 -> 64 -> 128 module whose image is img."""
+    _f32c(x4, "x4")
+    b, _, m, ns = x4.shape
+    out = torch.empty((b, 128, m), dtype=torch.float32, device=x4.device)
+    with torch.cuda.device(x4.device):
+        _L.check(_lib.mlp_eval_lin4_pool(b, m, ns, x4.data_ptr(), img.data_ptr(), coeff1[0].data_ptr(),
+                                         coeff1[1].data_ptr(), coeff2[0].data_ptr(), coeff2[1].data_ptr(),
+                                         out.data_ptr(), _stream(x4)), "mlp_eval_lin4_pool")
+    return out
+
+
+def eval_stored_prepare(w1, w2, img=None):
+    """The weight image of eval_stored_pool: w1 (128,128), w2 (C_out,128)."""
+    _f32c(w1, "w1"); _f32c(w2, "w2")
+    c_out = w2.shape[0]
+    if img is None:
+        img = torch.empty(int(_lib.mlp_eval_stored_image_bytes(c_out)), dtype=torch.uint8, device=w1.device)
+    with torch.cuda.device(w1.device):
+        _L.check(_lib.mlp_eval_stored_prepare(c_out, w1.data_ptr(), w2.data_ptr(), img.data_ptr(), _stream(w1)),
+                 "mlp_eval_stored_prepare")
+    return img
+
+
+def eval_stored_pool(y0, coeff0, img, coeff1, coeff2):
+    """y0 (B,128,m,ns) raw layer-0 output -> pooled (B,C_out,m), C_out = len(coeff2[0])."""
+    _f32c(y0, "y0")
+    b, _, m, ns = y0.shape
+    c_out = coeff2[0].numel()
+    out = torch.empty((b, c_out, m), dtype=torch.float32, device=y0.device)
+    with torch.cuda.device(y0.device):
+        _L.check(_lib.mlp_eval_stored_pool(b, c_out, m, ns, y0.data_ptr(), coeff0[0].data_ptr(),
+                                           coeff0[1].data_ptr(), img.data_ptr(), coeff1[0].data_ptr(),
+                                           coeff1[1].data_ptr(), coeff2[0].data_ptr(), coeff2[1].data_ptr(),
+                                           out.data_ptr(), _stream(y0)), "mlp_eval_stored_pool")
+    return out

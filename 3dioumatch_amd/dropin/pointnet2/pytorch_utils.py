@@ -534,6 +534,12 @@ class SharedMLP(nn.Sequential):
 
     def _run(self, x, pool, pre=None):
         from pointnet2 import _mlp_ext as K
+        if _eval_plans is not None and pool:  # only inside fused_eval(): the inference engine
+            plan = _eval_plans.get(id(self))
+            if plan is not None and plan.mlp is self:
+                out = plan.run(x, pre)
+                if out is not None:
+                    return out
         layers = list(self)
         # the module's own counters for the one-launch reductions of its layers (include/mlp_hip.h
         # `tickets`): nothing in the library is keyed by stream
@@ -620,6 +626,121 @@ class SharedMLP(nn.Sequential):
         if self._use_fused(x):
             return self._run(x, pool=True)
         return torch.max(super().forward(x), dim=3)[0]
+
+
+# ---- eval mode: the pooled MLP of a set-abstraction level in one pass (csrc/mlp_eval_pool.hip) ----
+_eval_plans = None  # {id(SharedMLP): EvalPlan} while fused_eval() is in force
+
+
+@contextlib.contextmanager
+def fused_eval(plans):
+    """Inside this context the pooled forwards of the SharedMLPs that `plans` ({id(module): EvalPlan})
+    names run through their plan's one-pass kernels where its shape gate allows.  Only the inference
+    engine (votenet/inference.py) enters it; outside it nothing changes."""
+    global _eval_plans
+    prev = _eval_plans
+    _eval_plans = plans
+    try:
+        yield
+    finally:
+        _eval_plans = prev
+
+
+def fold_bn_affine(gamma, beta, running_mean, running_var, eps):
+    """The eval-mode BatchNorm y -> gamma (y - mean) / sqrt(var + eps) + beta as y * scale + shift, in
+    the dtype of its arguments (the definition mlp_bn_eval_coeff computes on the device in fp32)."""
+    scale = gamma / torch.sqrt(running_var + eps)
+    return scale, beta - running_mean * scale
+
+
+class EvalPlan(object):
+    """Eval-mode BatchNorm of a three-layer pooled SharedMLP folded into per-channel (scale, shift)
+    ONCE, plus the weight images of its one-pass kernel.  Two forms: LIN4 (4 -> 64 -> 64 -> 128, the
+    grouped input of SA1) and STORED (c -> 128 -> 128 -> 128 / 256: layer 0 as the plain path runs it,
+    the rest in one pass).  refresh() re-folds in place (captured graphs keep their addresses); the
+    module's parameters and buffers are only read.  `hits` counts the forwards it served."""
+
+    def __init__(self, mlp):
+        layers = list(mlp)
+        if len(layers) != 3 or not all(SharedMLP._fusable(layer) for layer in layers):
+            raise ValueError("EvalPlan: a SharedMLP of three conv(1x1) -> BatchNorm2d -> ReLU layers")
+        self.mlp = mlp
+        self.shapes = [tuple(layer.conv.weight.shape[:2]) for layer in layers]  # (out, in)
+        (c1, c0), (c2, _), (c3, _) = self.shapes
+        if c0 == 4 and c1 == 64 and c2 == 64 and c3 == 128:
+            self.form = "lin4"
+        elif c1 == 128 and c2 == 128 and c3 in (128, 256):
+            self.form = "stored"
+        else:
+            raise ValueError("EvalPlan: no one-pass kernel for layers %s" % (self.shapes,))
+        self.coeffs, self.img, self.hits = None, None, 0
+        self.refresh()
+
+    def _weights(self):
+        return [layer.conv.weight.detach().reshape(layer.conv.weight.shape[0], -1) for layer in self.mlp]
+
+    def refresh(self):
+        from pointnet2 import _mlp_ext as K
+        bns = [next(layer.bn.children()) for layer in self.mlp]
+        with torch.no_grad():
+            coeffs = [K.fold_bn(bn) for bn in bns]
+            w = [t.contiguous() for t in self._weights()]
+            if self.coeffs is None:
+                self.coeffs = coeffs
+            else:
+                for old, new in zip(self.coeffs, coeffs):
+                    old[0].copy_(new[0])
+                    old[1].copy_(new[1])
+            if self.form == "lin4":
+                self.img = K.eval_lin4_prepare(w[0], self.coeffs[0], w[1], w[2], self.img)
+            else:
+                self.img = K.eval_stored_prepare(w[1], w[2], self.img)
+
+    def _layer0(self, x, pre):
+        """Layer 0's raw output (B, 128, m, ns) exactly as _FusedMLPChain.forward forms it in eval mode."""
+        from pointnet2 import _mlp_ext as K
+        w0 = self._weights()[0]
+        if pre is not None and isinstance(pre[0], str):
+            from pointnet2 import _ext
+            _, q_idx, q_weight, rel, shape = pre
+            z = K.gemm_forward(w0[:, 3:].contiguous(), x)
+            return _ext.three_interpolate_affine(z, q_idx, q_weight, w0[:, :3].contiguous(), rel).view(shape)
+        if pre is not None:
+            idx, _, npts = pre
+            return K.pregather_forward(K.gemm_forward(w0, x), idx, npts)
+        return K.gemm_forward(w0, x) if x.dim() == 4 else None
+
+    def run(self, x, pre):
+        """The pooled output, or None where the one-pass kernel does not apply (the caller then runs
+        the plain path)."""
+        from pointnet2 import _mlp_ext as K
+        if torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32:
+            return None
+        if any(next(layer.bn.children()).training for layer in self.mlp):
+            return None
+        x = x.contiguous()
+        (c1, c0), (c2, _), (c3, _) = self.shapes
+        if self.form == "lin4":
+            if pre is not None or x.dim() != 4 or x.shape[1] != 4 or \
+                    not K.eval_lin4_supported(x.shape[0], c0, c1, c3, x.shape[2], x.shape[3]):
+                return None
+            self.hits += 1
+            return K.eval_lin4_pool(x, self.img, self.coeffs[1], self.coeffs[2])
+        if pre is not None and isinstance(pre[0], str):
+            b, _, m, ns = pre[4]
+        elif pre is not None:
+            b, m, ns = pre[0].shape
+        elif x.dim() == 4:
+            b, _, m, ns = x.shape
+        else:
+            return None
+        if not K.eval_stored_supported(b, c1, c2, c3, m, ns):
+            return None
+        y0 = self._layer0(x, pre)
+        if y0 is None:
+            return None
+        self.hits += 1
+        return K.eval_stored_pool(y0.contiguous(), self.coeffs[0], self.img, self.coeffs[1], self.coeffs[2])
 
 
 class _PackPoints(Function):

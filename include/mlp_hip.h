@@ -436,6 +436,31 @@ int mlp_wgrad_first4_from_gated(int parts, const float *gpart, const float *w, c
  * workspace of conv2d backward-weight, pytorch_utils.py:70-124) */
 size_t mlp_gemm_wgrad_workspace_floats(int b, int m, int k, int r);
 
+/* ---- eval-mode pooled shared MLP in one pass (csrc/mlp_eval_pool.hip) ------------------------
+ * conv(1x1) -> BN -> ReLU x 3 -> max over nsample with every BatchNorm folded into a per-channel
+ * (scale, shift) (mlp_bn_eval_coeff); only the pooled (b, c_out, m) is written.
+ * LIN4 form, the SA1 module 4 -> 64 -> 64 -> 128 on the grouped input (b, 4, m, ns):
+ * 1 when covered (ns 16 / 32 / 64, m * ns % 256 == 0), else 0 (pytorch_utils.py:14-39) */
+int mlp_eval_lin4_supported(int b, int c_in, int c_mid, int c_out, int m, int ns);
+/* x4 (b,4,m*ns), img = mlp_chain_lin4_prepare(w0, sc0, sh0, w1, w2), folded (sc1, sh1) (64) and
+ * (sc2, sh2) (128) -> out (b,128,m) (pytorch_utils.py:14-39 + pointnet2_modules.py:256-262) */
+int mlp_eval_lin4_pool(int b, int m, int ns, const float *x4, const void *img, const float *sc1,
+                       const float *sh1, const float *sc2, const float *sh2, float *out, void *stream);
+/* STORED form, the tail 128 -> 128 -> c_out (128 / 256) of a module whose first layer's raw output
+ * y0 (b,128,m,ns) is given: 1 when covered (ns 16 / 32 / 64, m * ns % 32 == 0), else 0
+ * (pytorch_utils.py:14-39) */
+int mlp_eval_stored_supported(int b, int c_in, int c_mid, int c_out, int m, int ns);
+/* bytes of the weight image of mlp_eval_stored_prepare (nn.Conv2d weights, pytorch_utils.py:70-124) */
+size_t mlp_eval_stored_image_bytes(int c_out);
+/* w1 (128,128), w2 (c_out,128) -> img (16-byte aligned): fragment-ordered bf16 images, exact
+ * three-term split (the conv weights of pytorch_utils.py:14-39) */
+int mlp_eval_stored_prepare(int c_out, const float *w1, const float *w2, void *img, void *stream);
+/* y0 (b,128,m*ns) + folded (sc0, sh0), img, (sc1, sh1), (sc2, sh2) -> out (b,c_out,m)
+ * (pytorch_utils.py:14-39 + pointnet2_modules.py:256-262) */
+int mlp_eval_stored_pool(int b, int c_out, int m, int ns, const float *y0, const float *sc0,
+                         const float *sh0, const void *img, const float *sc1, const float *sh1,
+                         const float *sc2, const float *sh2, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
