@@ -805,9 +805,7 @@ MLP_API int mlp_bn_finalize_pairs(int c, int parts, int n_part, const float *pai
   hipStream_t stream = (hipStream_t)stream_;
   double *sums = reinterpret_cast<double *>(scratch);
   const FwdFinalize fin = {nullptr, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift};
-  // (MLP_BN_PAIRS_ONE_LAUNCH = the largest number of parts finished in one launch; 0: always two)
-  static const int one_limit = getenv("MLP_BN_PAIRS_ONE_LAUNCH") ? atoi(getenv("MLP_BN_PAIRS_ONE_LAUNCH")) : kPairsOneLaunch;
-  if (parts <= one_limit) {
+  if (parts <= kPairsOneLaunch) {
     hipLaunchKernelGGL(bn_pairs_one_kernel, dim3(pn2_ceil_div(c, kWave)), dim3(1024), 0, stream, c, parts, n_part,
                        pairs, fin);
     return pn2_launch_status();

@@ -32,7 +32,6 @@
 #include "common.h"
 #include "mlp_operand.h"
 #include "mlp_bwd_x6.h"
-#include <stdlib.h>
 
 #ifndef MLP_LIN4_OCC
 #define MLP_LIN4_OCC 1  // workgroups per CU of the gated (64,64) form: at 2 (256 registers) it spills inside the chunk loop and
@@ -46,7 +45,7 @@ namespace {
 // indices -- eight 4-byte LDS reads from the same conflict-free tiles -- and an MFMA step covers
 // 16 of them, so a chunk is M/16 dgrad steps and TN/16 wgrad steps.
 template <int MB, int KB, int KBD, int NB, int PMODE, int QMODE, int OCC, bool STATS, bool DGRAD = true,
-          bool X6 = false, bool GATED = true>
+          bool X6 = false>
 __global__ void __launch_bounds__(256, OCC)
 gemm_bwd_fused_kernel(int k_total, int r, int total_chunks, int chunks_per_cloud, int xyz,
                       OperandB opp, OperandB opq, const float *__restrict__ w,
@@ -89,8 +88,8 @@ gemm_bwd_fused_kernel(int k_total, int r, int total_chunks, int chunks_per_cloud
   // ONE row k of the block and 16 of its columns: the sums and the four G entries of the row are
   // in-lane accumulations (2 + 4 registers instead of 32), the column's x4 a broadcast LDS read.
   // `dq` then receives the G partials: (2 gridDim.x, 64, 4) floats.
-  // (GATED = false: the round-5 form -- dQ written, the sums only -- kept for A/B, MLP_LIN4_GATED=0)
-  constexpr bool TF = QLIN && GATED;
+  constexpr bool TF = QLIN;
+  static_assert(!TF || X6, "the T form is instantiated in the bf16 form only");
   constexpr bool RAWQ = STATS;  // the Q tile then holds raw rows, rectified as fragments are read
   constexpr int SROWS = STATS ? 32 * KBD : 1;
   __shared__ float4 Rc[SROWS];       // per Q row: sc, sh, mu, is
@@ -385,10 +384,8 @@ gemm_bwd_fused_kernel(int k_total, int r, int total_chunks, int chunks_per_cloud
           for (int e = 0; e < DK; ++e)
 #pragma unroll
             for (int n = 0; n < DN; ++n)
-              accD[e][n] = TF ? __builtin_amdgcn_mfma_f32_32x32x2f32(bp[g & 1][u][n], wreg[e][g * DU + u],
-                                                                     accD[e][n], 0, 0, 0)
-                              : __builtin_amdgcn_mfma_f32_32x32x2f32(wreg[e][g * DU + u], bp[g & 1][u][n],
-                                                                     accD[e][n], 0, 0, 0);
+              accD[e][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(wreg[e][g * DU + u], bp[g & 1][u][n],
+                                                                accD[e][n], 0, 0, 0);
         between(g);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -647,8 +644,7 @@ int fused_cus() {
 // workgroups of the persistent launch: one resident round, at least 8 chunks each (the partial
 // dW every workgroup writes must stay small next to the activations it read)
 int fused_workgroups(const FusedShape &s, long long total_chunks) {
-  static const long long forced = getenv("MLP_FUSED_BWD_WGS") ? atoll(getenv("MLP_FUSED_BWD_WGS")) : 0;
-  long long g = forced > 0 ? forced : (long long)fused_cus() * s.occ;
+  long long g = (long long)fused_cus() * s.occ;
   if (g > total_chunks / 8) g = total_chunks / 8;
   return (int)(g < 1 ? 1 : g);
 }
@@ -661,9 +657,8 @@ int fused_workgroups(const FusedShape &s, long long total_chunks) {
 // network, whole chunks per cloud, the pooled form with nsample a multiple of 16
 MLP_API int mlp_gemm_backward_fused_supported(int b, int m, int k, int r, int pmode, int qmode,
                                               int ns) {
-  static const bool off = getenv("MLP_FUSED_BACKWARD") && atoi(getenv("MLP_FUSED_BACKWARD")) == 0;
   FusedShape s;
-  if (off || b <= 0 || r <= 0 || !fused_shape(m, k, &s)) return 0;
+  if (b <= 0 || r <= 0 || !fused_shape(m, k, &s)) return 0;
   if (r % s.tn != 0 || (long long)b * (r / s.tn) < 64) return 0;
   if (pmode != OP_DY && pmode != OP_POOLDY) return 0;
   if (pmode == OP_POOLDY && (ns <= 0 || ns % 16 != 0 || r % ns != 0 || (ns % s.tn != 0 && s.tn % ns != 0)))
@@ -679,13 +674,6 @@ MLP_API int mlp_gemm_backward_fused_supported(int b, int m, int k, int r, int pm
   const bool either = m == 128 && k == 128;
   if (!either && pooled_only != (pmode == OP_POOLDY)) return 0;
   return 1;
-}
-
-// 1 when mlp_gemm_backward_fused with qmode 4 leaves the gated sums of the virtual layer below in dq
-// (parts x 64 x 4 floats) instead of the data gradient (b, 64, r); 0 with MLP_LIN4_GATED=0 (A/B)
-MLP_API int mlp_gemm_backward_fused_lin4_gated(void) {
-  static const bool off = getenv("MLP_LIN4_GATED") && atoi(getenv("MLP_LIN4_GATED")) == 0;
-  return off ? 0 : 1;
 }
 
 // number of (s1, s2) partials per channel that mlp_gemm_backward_fused leaves in stats_part
@@ -741,37 +729,23 @@ MLP_API int mlp_gemm_backward_fused(int b, int m, int k, int r, const float *w, 
     if (rcx == 0) return mlp_reduce_weight_partials(m * k, gx, workspace, dw, stream);
   }
   if (k != 64) stats_part = nullptr;
-  static const bool x6 = !(getenv("MLP_GEMM_SPLIT_BF16") && atoi(getenv("MLP_GEMM_SPLIT_BF16")) == 0) &&
-                         !(getenv("MLP_BWD_SPLIT_BF16") && atoi(getenv("MLP_BWD_SPLIT_BF16")) == 0);
 #define FUSED_X(MB, KB, KBD, NB, PM, QM, OCC, ST, X6)                                           \
   hipLaunchKernelGGL((gemm_bwd_fused_kernel<MB, KB, KBD, NB, PM, QM, OCC, ST, true, X6>), dim3(g), \
                      dim3(256), 0, stream, k, r, total, cpc, s.xyz, P, Q, w, dq, workspace,     \
                      stats_part)
-#define FUSED(MB, KB, KBD, NB, PM, QM, OCC, ST)                                                 \
-  do { if (x6) FUSED_X(MB, KB, KBD, NB, PM, QM, OCC, ST, true);                                 \
-       else FUSED_X(MB, KB, KBD, NB, PM, QM, OCC, ST, false); } while (0)
   // (the bf16 form wins where the registers hold it; measured per shape, profiles/r4_split_bf16.json)
+#define FUSED(MB, KB, KBD, NB, PM, QM, OCC, ST) FUSED_X(MB, KB, KBD, NB, PM, QM, OCC, ST, true)
 #define FUSED_F32(MB, KB, KBD, NB, PM, QM, OCC, ST) FUSED_X(MB, KB, KBD, NB, PM, QM, OCC, ST, false)
-  if (m == 64 && k == 64 && qmode == OP_LIN4 && !mlp_gemm_backward_fused_lin4_gated()) {
-    if (x6) hipLaunchKernelGGL((gemm_bwd_fused_kernel<2, 2, 2, 2, OP_DY, OP_LIN4, 2, true, true, true, false>), dim3(g),
-                               dim3(256), 0, stream, k, r, total, cpc, s.xyz, P, Q, w, dq, workspace, stats_part);
-    else hipLaunchKernelGGL((gemm_bwd_fused_kernel<2, 2, 2, 2, OP_DY, OP_LIN4, 2, true, true, false, false>), dim3(g),
-                            dim3(256), 0, stream, k, r, total, cpc, s.xyz, P, Q, w, dq, workspace, stats_part);
-  } else if (m == 64 && k == 64 && qmode == OP_LIN4) FUSED(2, 2, 2, 2, OP_DY, OP_LIN4, MLP_LIN4_OCC, true);
+  if (m == 64 && k == 64 && qmode == OP_LIN4) FUSED(2, 2, 2, 2, OP_DY, OP_LIN4, MLP_LIN4_OCC, true);
   else if (m == 64 && k == 64) FUSED(2, 2, 2, 2, OP_DY, OP_BNRELU, 2, true);
   else if (m == 128 && k == 64) FUSED(4, 2, 2, 2, OP_POOLDY, OP_BNRELU, 1, true);
-  else if (m == 128 && k == 128 && pmode == OP_DY) FUSED_F32(4, 4, 4, 1, OP_DY, OP_BNRELU, 2, false);
-  else if (m == 128 && k == 128) FUSED_F32(4, 4, 4, 1, OP_POOLDY, OP_BNRELU, 2, false);
   else if (m == 256 && k == 128) FUSED(8, 4, 4, 1, OP_POOLDY, OP_BNRELU, 1, false);
   else if (m == 128 && k == 131) FUSED(4, 5, 4, 1, OP_DY, OP_DIRECT, 1, false);
   else if (dq != nullptr) FUSED_F32(4, 9, 8, 1, OP_DY, OP_DIRECT, 1, false);
-  else if (x6 && !(getenv("MLP_WGRAD_ONLY_SPLIT") && atoi(getenv("MLP_WGRAD_ONLY_SPLIT")) == 0))
+  else
     // the layer's input needs no gradient: the persistent weight-gradient half alone (its bf16 form
     // fits the registers: no W^T fragments, no dQ blocks)
     hipLaunchKernelGGL((gemm_bwd_fused_kernel<4, 9, 8, 1, OP_DY, OP_DIRECT, 1, false, false, true>), dim3(g),
-                       dim3(256), 0, stream, k, r, total, cpc, s.xyz, P, Q, w, dq, workspace, stats_part);
-  else
-    hipLaunchKernelGGL((gemm_bwd_fused_kernel<4, 9, 8, 1, OP_DY, OP_DIRECT, 1, false, false>), dim3(g),
                        dim3(256), 0, stream, k, r, total, cpc, s.xyz, P, Q, w, dq, workspace, stats_part);
 #undef FUSED_F32
 #undef FUSED

@@ -25,7 +25,6 @@
 #pragma once
 #include "common.h"
 #include "mlp_operand.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -435,11 +434,9 @@ gemm_bwd_x6_kernel(int k_total, int r, int total_chunks, int chunks_per_cloud, i
 }  // namespace
 
 // workgroups of the bf16-split backward for a (128,128) layer of b clouds x r columns (one per CU,
-// at least 8 chunks each), or 0 when that kernel does not run (switched off / not this shape)
+// at least 8 chunks each), or 0 when that kernel does not run (not this shape)
 static int mlp_bwd_x6_workgroups(int b, int m, int k, int r, int cus) {
-  static const bool off = (getenv("MLP_GEMM_SPLIT_BF16") && atoi(getenv("MLP_GEMM_SPLIT_BF16")) == 0) ||
-                          (getenv("MLP_BWD_SPLIT_BF16") && atoi(getenv("MLP_BWD_SPLIT_BF16")) == 0);
-  if (off || !(m == 128 && k == 128) || r % 32 != 0 || b <= 0) return 0;
+  if (!(m == 128 && k == 128) || r % 32 != 0 || b <= 0) return 0;
   const long long total = (long long)b * (r / 32);
   long long g = cus;
   if (g > total / 8) g = total / 8;

@@ -30,7 +30,6 @@
 //         every other kernel that recomputes it (lin4).
 #include "common.h"
 #include "mlp_operand.h"
-#include <stdlib.h>
 #include <mutex>
 #include <set>
 #include <type_traits>
@@ -50,7 +49,6 @@ struct ChainArgs {
                          // columns, C = 64 (stats pass) / M3
   float *ext;            // 2 planes of (b, M3, r / NS): winning raw value, first index
   size_t ext_plane;
-  int store_mode;        // bit 0: y2 with streaming stores, bit 1: y3 with streaming stores
 };
 
 constexpr int kChainK = 64;  // channels entering layer 2 / layer 3 (SA1: 64 -> 64 -> 128)
@@ -282,16 +280,14 @@ __global__ void __launch_bounds__(256, FULL ? 2 : 4) chain_lin4_kernel(const Cha
       accumulate(acc2, 2);
     } else {
       // y2 (N form): register q of block i = channel 32 i + (q & 3) + 8 (q >> 2) + 4 h, this
-      // lane's column -- 128-byte row segments per half-wave
+      // lane's column -- 128-byte row segments per half-wave, streaming stores (y3: plain stores)
       if (a.y2 != nullptr) {
         float *dst = a.y2 + ((size_t)b * M2 + 4 * h) * a.r + col0 + l31;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            float *d1 = &dst[(size_t)(32 * i + (q & 3) + 8 * (q >> 2)) * a.r];
-            if (a.store_mode & 1) __builtin_nontemporal_store(acc2[i][q], d1);
-            else *d1 = acc2[i][q];
+            __builtin_nontemporal_store(acc2[i][q], &dst[(size_t)(32 * i + (q & 3) + 8 * (q >> 2)) * a.r]);
           }
       }
       // ---- layer 3 (T form) on relu(bn(y2)) taken straight from layer 2's accumulators; the four
@@ -357,8 +353,7 @@ __global__ void __launch_bounds__(256, FULL ? 2 : 4) chain_lin4_kernel(const Cha
           for (int g = 0; g < 4; ++g) {
             typedef float f32x4 __attribute__((ext_vector_type(4)));
             const f32x4 o = {acc3[j][4 * g], acc3[j][4 * g + 1], acc3[j][4 * g + 2], acc3[j][4 * g + 3]};
-            if (a.store_mode & 2) __builtin_nontemporal_store(o, reinterpret_cast<f32x4 *>(dst + 8 * g));
-            else *reinterpret_cast<f32x4 *>(dst + 8 * g) = o;
+            *reinterpret_cast<f32x4 *>(dst + 8 * g) = o;
           }
         }
       }
@@ -458,11 +453,6 @@ bool chain_shape_ok(int b, int r, int ns) {
 // workgroups of a pass: 4 waves x kTilesPerWave tiles each
 int chain_workgroups(int b, int r) { return (int)((long long)b * (r / 32) / (4 * kTilesPerWave)); }
 
-bool chain_enabled() {
-  static const bool off = getenv("MLP_CHAIN_FWD") && atoi(getenv("MLP_CHAIN_FWD")) == 0;
-  return !off;
-}
-
 template <typename Kern>
 void chain_launch(Kern kern, int wgs, size_t lds_bytes, hipStream_t stream, const ChainArgs &args) {
   // (every instantiation has the same pointer TYPE: remember the kernels by address)
@@ -552,7 +542,7 @@ chain_finalize_kernel(int c, int parts, int n_part, const float *__restrict__ pa
 // module leaves (one per workgroup) and the columns each covers; 0 when the shape is outside the
 // kernel (m3 = 128, nsample 16 / 32 / 64, r a multiple of 256).
 MLP_API int mlp_chain_lin4_parts(int b, int r, int m3, int ns, int *cols_per_part) {
-  if (!chain_enabled() || m3 != 128 || !chain_shape_ok(b, r, ns)) return 0;
+  if (m3 != 128 || !chain_shape_ok(b, r, ns)) return 0;
   if (cols_per_part) *cols_per_part = 32 * 4 * kTilesPerWave;
   return chain_workgroups(b, r);
 }
@@ -602,7 +592,6 @@ MLP_API int mlp_chain_lin4_forward(int b, int r, int ns, const float *x4, const 
   a.x4 = x4; a.wimg = (const char *)img; a.sc2 = sc2; a.sh2 = sh2;
   a.gamma3 = gamma3; a.y2 = y2; a.y3 = y3; a.pairs = pairs3; a.ext = ext;
   a.ext_plane = (size_t)b * 128 * (r / ns);
-  a.store_mode = getenv("MLP_CHAIN_STORE") ? atoi(getenv("MLP_CHAIN_STORE")) : 1;
   const size_t lds_bytes = kImgBytes + 512;
   hipStream_t stream = (hipStream_t)stream_;
   const int wgs = chain_workgroups(b, r);

@@ -199,14 +199,14 @@ __device__ __forceinline__ float half_wave_extreme(float v) {
 //        pass no longer re-reads y either.  ext: 2 planes (value, first index) of
 //        (b, m_total, r / POOL).
 template <int TM, int TN, int WM, int WN, int MODE, bool A_TRANS, bool A_VEC, bool STATS = false,
-          int POOL = 0, bool X6 = false>
+          int POOL = 0>
 #ifndef MLP_X6_OCC
 #define MLP_X6_OCC 3
 #endif
 #ifndef MLP_X6_OCC_256
 #define MLP_X6_OCC_256 3
 #endif
-__global__ void __launch_bounds__(256, X6 ? (((MODE <= OP_BNRELU || MODE == OP_LIN4) && !A_TRANS) ? (TM <= 128 ? MLP_X6_OCC : MLP_X6_OCC_256) : 2) : (((MODE <= OP_BNRELU || MODE == OP_LIN4) && TM <= 128) ? 4 : 2))
+__global__ void __launch_bounds__(256, ((MODE <= OP_BNRELU || MODE == OP_LIN4) && !A_TRANS) ? (TM <= 128 ? MLP_X6_OCC : MLP_X6_OCC_256) : 2)
 gemm_nn2_kernel(int m_total, int k_total, int r, const float *__restrict__ a, int lda,
                 unsigned a_bytes, OperandB opb, float *__restrict__ c, size_t b_stride_in,
                 size_t b_stride_out, float *__restrict__ stats = nullptr, int stat_channels = 0,
@@ -373,18 +373,6 @@ gemm_nn2_kernel(int m_total, int k_total, int r, const float *__restrict__ a, in
     for (int j = 0; j < NB; ++j)
       bf[j] = *reinterpret_cast<const float4 *>(&Bs[buf][b_frag + hh * PLB + j * (128 + 16)]);
   };
-  auto multiply = [&](const float4 (&af)[MB], const float4 (&bf)[NB]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          const float av = e == 0 ? af[i].x : e == 1 ? af[i].y : e == 2 ? af[i].z : af[i].w;
-          const float bv = e == 0 ? bf[j].x : e == 1 ? bf[j].y : e == 2 ? bf[j].z : bf[j].w;
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-        }
-  };
 
   const int chunks = (k_total + KC - 1) / KC;
   fetch(0);
@@ -396,29 +384,22 @@ gemm_nn2_kernel(int m_total, int k_total, int r, const float *__restrict__ a, in
     float4 af0[MB], bf0[NB], af1[MB], bf1[NB];
     fragments(cur, 0, af0, bf0);
     fragments(cur, 1, af1, bf1);                   // in flight during the first 4 * MB * NB MFMAs
-    if constexpr (X6) {
-      // the lane's eight k of the chunk (af0 | af1), as three bf16 terms each; six products per
-      // block, the small ones first
-      Split3 sa[MB];
+    // the lane's eight k of the chunk (af0 | af1), as three bf16 terms each; six products per
+    // block, the small ones first
+    Split3 sa[MB];
 #pragma unroll
-      for (int ii = 0; ii < MB; ++ii) sa[ii] = split3(af0[ii], af1[ii]);
-      // one column block at a time (its split lives for MB x 6 MFMAs); the next chunk is staged and
-      // the one after it requested after the first block's MFMAs are issued
+    for (int ii = 0; ii < MB; ++ii) sa[ii] = split3(af0[ii], af1[ii]);
+    // one column block at a time (its split lives for MB x 6 MFMAs); the next chunk is staged and
+    // the one after it requested after the first block's MFMAs are issued
 #pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        const Split3 sb = split3(bf0[j], bf1[j]);
+    for (int j = 0; j < NB; ++j) {
+      const Split3 sb = split3(bf0[j], bf1[j]);
 #pragma unroll
-        for (int ii = 0; ii < MB; ++ii) mfma_x6(acc[ii][j], sa[ii], sb);
-        if (j == 0) {
-          if (i + 1 < chunks) stash(cur ^ 1);
-          if (i + 2 < chunks) fetch((i + 2) * KC);
-        }
+      for (int ii = 0; ii < MB; ++ii) mfma_x6(acc[ii][j], sa[ii], sb);
+      if (j == 0) {
+        if (i + 1 < chunks) stash(cur ^ 1);
+        if (i + 2 < chunks) fetch((i + 2) * KC);
       }
-    } else {
-      multiply(af0, bf0);
-      if (i + 1 < chunks) stash(cur ^ 1);            // chunk i+1: registers -> the other buffer
-      if (i + 2 < chunks) fetch((i + 2) * KC);       // chunk i+2: in flight during the MFMAs
-      multiply(af1, bf1);
     }
     __syncthreads();  // buffer cur is free again, buffer cur^1 is complete
   }
@@ -789,7 +770,7 @@ gemm_nn_small_kernel(int m_total, int k_total, int r, const float *__restrict__ 
 // r-steps; shares are summed through LDS at the end.  The R axis is staged [r][m] / [r][k].
 constexpr int RC = 32;  // r chunk (128-byte row segments per load)
 
-template <int PMODE, int QMODE, int KBW, int WK, int RS, bool X6 = false>
+template <int PMODE, int QMODE, int KBW, int WK, int RS>
 __global__ void __launch_bounds__(256)
 gemm_wgrad_kernel(int m_total, int k_begin, int k_end, int k_total, int r, int r_per_slice,
                   OperandB opp, OperandB opq, float *__restrict__ part, size_t p_stride,
@@ -864,30 +845,6 @@ gemm_wgrad_kernel(int m_total, int k_begin, int k_end, int k_total, int r, int r
             (q_ok[s] && rr + seg_r + i < r_hi) ? transform<QMODE>(qx[s][i], qdz[s][i], qc[s]) : 0.f;
     __syncthreads();
     if (rr + RC < r_hi) fetch(rr + RC);
-    if constexpr (X6 && (RC / RS) % 16 == 0) {
-      // a wave's share of the r-chunk in 16-deep bf16 MFMA steps (mlp_operand.h split3 / mfma_x6)
-#pragma unroll
-      for (int st = 0; st < RC / RS / 16; ++st) {
-        const int row0 = wr * (RC / RS) + 16 * st + 8 * (lane >> 5);
-        Split3 sp[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          float v[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = Ps[(row0 + e) * LDP + i * 32 + (lane & 31)];
-          sp[i] = split3(v);
-        }
-#pragma unroll
-        for (int j = 0; j < KBW; ++j) {
-          float v[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = Qs[(row0 + e) * LDQ + (wk * KBW + j) * 32 + (lane & 31)];
-          const Split3 sq = split3(v);
-#pragma unroll
-          for (int i = 0; i < 2; ++i) mfma_x6(acc[i][j], sp[i], sq);
-        }
-      }
-    } else {
 #pragma unroll
     for (int st = 0; st < RC / 2 / RS; ++st) {
       const int row = wr * (RC / RS) + 2 * st + (lane >> 5);
@@ -901,7 +858,6 @@ gemm_wgrad_kernel(int m_total, int k_begin, int k_end, int k_total, int r, int r
 #pragma unroll
         for (int j = 0; j < KBW; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[i], bq[j], acc[i][j], 0, 0, 0);
-    }
     }
   }
   if (RS > 1) {  // sum the r-shares of each column group: share s -> LDS -> share 0
@@ -1195,20 +1151,6 @@ __global__ void __launch_bounds__(256) reduce_partials_batch_kernel(const Reduce
   else reduce_partials_block<false>(blk - t.first_block[e], t.count[e], t.parts[e], t.part[e], t.out[e]);
 }
 
-// fp32 products as six bf16 MFMAs (see split3): on unless MLP_GEMM_SPLIT_BF16=0 (read once)
-bool gemm_x6() {
-  static const bool on = !(getenv("MLP_GEMM_SPLIT_BF16") && atoi(getenv("MLP_GEMM_SPLIT_BF16")) == 0);
-  return on;
-}
-
-// the stand-alone weight-gradient kernel split the same way: slower over the layer shapes (2436
-// against 2346 us, profiles/r4_split_bf16.json) -- its fragments are split by every wave again;
-// kept behind MLP_WGRAD_SPLIT_BF16=1
-bool wgrad_x6() {
-  static const bool on = gemm_x6() && getenv("MLP_WGRAD_SPLIT_BF16") && atoi(getenv("MLP_WGRAD_SPLIT_BF16")) == 1;
-  return on;
-}
-
 // forward GEMM whose epilogue also leaves BatchNorm partials (see gemm_nn2_kernel STATS); only
 // instantiated for the operand modes of the forward pass
 template <int TM, int TN, int WM, int WN, int MODE, bool A_TRANS>
@@ -1218,12 +1160,11 @@ void launch_stats(bool a_vec, int r, int b, hipStream_t stream, int rows, int k,
   if constexpr (!A_TRANS && MODE <= OP_BNRELU) {
     // partial (part, channel) pairs: part = cloud * tiles + tile, channel = done + row
     float *st = stats + (size_t)done * 2;
-#define ST_LAUNCH(AV, X6)                                                                         \
-  hipLaunchKernelGGL((gemm_nn2_kernel<TM, TN, WM, WN, MODE, false, AV, true, 0, X6>),               \
+#define ST_LAUNCH(AV)                                                                             \
+  hipLaunchKernelGGL((gemm_nn2_kernel<TM, TN, WM, WN, MODE, false, AV, true>),                      \
                      dim3(pn2_ceil_div(r, TN), 1, b), dim3(256), 0, stream, rows, k, r, a_t, lda,   \
                      a_bytes, op, c_t, in_stride, out_stride, st, channels)
-    if (gemm_x6()) { if (a_vec) ST_LAUNCH(true, true); else ST_LAUNCH(false, true); }
-    else { if (a_vec) ST_LAUNCH(true, false); else ST_LAUNCH(false, false); }
+    if (a_vec) ST_LAUNCH(true); else ST_LAUNCH(false);
 #undef ST_LAUNCH
   }
 }
@@ -1238,11 +1179,11 @@ int launch_nn(int b, int m, int k, int r, const float *a, int lda, const Operand
   if ((long long)b * r <= small_cols) {  // a few hundred columns per cloud: latency-bound regime
     // (measured, tools/small_gemm_bench.py: the transposed form with a plain operand gains from the
     //  split at two workgroups per CU, 20 -> 15.6 us; with the on-the-fly dY operand it spills and does not)
-    if (gemm_x6() && (!A_TRANS || MODE == OP_DIRECT) && img.p != nullptr)
+    if ((!A_TRANS || MODE == OP_DIRECT) && img.p != nullptr)
       hipLaunchKernelGGL((gemm_nn_small_kernel<MODE, A_TRANS, true, true>),
                          dim3(pn2_ceil_div(r, 64), pn2_ceil_div(m, 64), b), dim3(256), 0, stream, m,
                          k, r, a, lda, op, c, in_stride, out_stride, img);
-    else if (gemm_x6() && (!A_TRANS || MODE == OP_DIRECT))
+    else if (!A_TRANS || MODE == OP_DIRECT)
       hipLaunchKernelGGL((gemm_nn_small_kernel<MODE, A_TRANS, true>),
                          dim3(pn2_ceil_div(r, 64), pn2_ceil_div(m, 64), b), dim3(256), 0, stream, m,
                          k, r, a, lda, op, c, in_stride, out_stride, AImage{nullptr, 0, 0});
@@ -1253,8 +1194,7 @@ int launch_nn(int b, int m, int k, int r, const float *a, int lda, const Operand
     return pn2_launch_status();
   }
   // rows are covered by 256-row tiles, then one smaller tile for the remainder
-  const char *v2env = getenv("MLP_GEMM_PIPELINED");
-  const bool pipelined = !(v2env && atoi(v2env) == 0) && (r % 256 == 0);
+  const bool pipelined = r % 256 == 0;
   const size_t a_total = A_TRANS ? (size_t)k * lda : (size_t)m * lda;  // floats from `a` on
   int done = 0;
   while (done < m) {
@@ -1268,14 +1208,6 @@ int launch_nn(int b, int m, int k, int r, const float *a, int lda, const Operand
     if (stats)                                                                                  \
       launch_stats<TM, TN, WM, WN, MODE, A_TRANS>(a_vec, r, b, stream, rows, k, a_t, lda, a_bytes, \
                                                   op, c_t, in_stride, out_stride, stats, m, done); \
-    else if (pipelined && a_vec && gemm_x6())                                                   \
-      hipLaunchKernelGGL((gemm_nn2_kernel<TM, TN, WM, WN, MODE, A_TRANS, true, false, 0, true>), \
-                         dim3(pn2_ceil_div(r, TN), 1, b), dim3(256), 0, stream, rows, k, r, a_t,  \
-                         lda, a_bytes, op, c_t, in_stride, out_stride);                         \
-    else if (pipelined && gemm_x6())                                                            \
-      hipLaunchKernelGGL((gemm_nn2_kernel<TM, TN, WM, WN, MODE, A_TRANS, false, false, 0, true>), \
-                         dim3(pn2_ceil_div(r, TN), 1, b), dim3(256), 0, stream, rows, k, r, a_t,  \
-                         lda, a_bytes, op, c_t, in_stride, out_stride);                         \
     else if (pipelined && a_vec)                                                                \
       hipLaunchKernelGGL((gemm_nn2_kernel<TM, TN, WM, WN, MODE, A_TRANS, true>),                \
                          dim3(pn2_ceil_div(r, TN), 1, b), dim3(256), 0, stream, rows, k, r, a_t,  \
@@ -1466,10 +1398,9 @@ MLP_API int mlp_gemm_forward(int b, int m, int k, int r, const float *w, const f
 // 1 when the layer runs on the small 64 x 64 kernel in its bf16 form, i.e. when
 // mlp_gemm_forward_img / mlp_gemm_backward_small_img can take their weight from an image
 MLP_API int mlp_gemm_image_supported(int b, int r) {
-  static const bool off = getenv("MLP_WEIGHT_IMAGES") && atoi(getenv("MLP_WEIGHT_IMAGES")) == 0;
   const char *env = getenv("MLP_SMALL_GEMM_COLS");
   const long long small_cols = env ? atoll(env) : 16384;
-  return !off && b > 0 && r > 0 && (long long)b * r <= small_cols && gemm_x6();
+  return b > 0 && r > 0 && (long long)b * r <= small_cols;
 }
 
 // mlp_gemm_forward with the weight ALSO given as the bf16 image mlp_weight_images_build made of it
@@ -1492,15 +1423,11 @@ MLP_API int mlp_gemm_forward_img(int b, int m, int k, int r, const float *w, con
 // Can the forward GEMM of this shape leave BatchNorm partials behind?  Returns the number of
 // (mean, M2) pairs per channel (0: no -- use mlp_bn_train_stats on y) and the columns each covers.
 MLP_API int mlp_gemm_forward_stats_parts(int b, int m, int k, int r, int *cols_per_part) {
-  const char *v2env = getenv("MLP_GEMM_PIPELINED");
-  const char *stenv = getenv("MLP_GEMM_EPILOGUE_STATS");
-  if ((v2env && atoi(v2env) == 0) || (stenv && atoi(stenv) == 0)) return 0;
   const char *env = getenv("MLP_SMALL_GEMM_COLS");
   const long long small_cols = env ? atoll(env) : 16384;
   if (b <= 0 || r % 256 != 0 || (long long)b * r <= small_cols) return 0;
   int tn;
-  if (gemm_x6() && mlp_fwd128_enabled_for(b, m, k, r)) tn = 64;  // (128, 128): the persistent T-form kernel
-  else if (m == 256) tn = 64;            // one 256 x 64 tile per column block
+  if (m == 256) tn = 64;            // one 256 x 64 tile per column block
   else if (m > 32 && m <= 128) tn = 128; // one 128 x 128 / 64 x 128 tile
   else return 0;                         // several row tiles of different widths: not covered
   if (cols_per_part) *cols_per_part = tn;
@@ -1514,9 +1441,6 @@ MLP_API int mlp_gemm_forward_stats(int b, int m, int k, int r, const float *w, c
                                    float *pairs, void *stream_) {
   if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
   if (!pairs || mlp_gemm_forward_stats_parts(b, m, k, r, nullptr) == 0) return (int)hipErrorInvalidValue;
-  if (gemm_x6() && mlp_fwd128_enabled_for(b, m, k, r))  // (its pairs cover 64 columns: no other kernel may run)
-    return mlp_fwd128_launch(b, r, 0, mode == OP_DIRECT ? 1 : 0, w, x, scale, shift, nullptr, y, pairs, nullptr,
-                             (hipStream_t)stream_);
   OperandB op = {x, nullptr, scale, shift, nullptr, nullptr, nullptr};
   const size_t in_stride = (size_t)k * r, out_stride = (size_t)m * r;
   if (mode == OP_DIRECT)
@@ -1529,8 +1453,6 @@ MLP_API int mlp_gemm_forward_stats(int b, int m, int k, int r, const float *w, c
 // 1 when mlp_gemm_forward_stats_pool covers the pooled last layer: statistics from the epilogue
 // available, one row tile (m = 128 or 256), nsample 32 or 64, 16-byte aligned weight rows
 MLP_API int mlp_gemm_forward_stats_pool_supported(int b, int m, int k, int r, int ns) {
-  const char *env = getenv("MLP_GEMM_EPILOGUE_POOL");
-  if (env && atoi(env) == 0) return 0;
   if (mlp_gemm_forward_stats_parts(b, m, k, r, nullptr) == 0) return 0;
   return (m == 128 || m == 256) && (ns == 16 || ns == 32 || ns == 64) && r % ns == 0 && k % 4 == 0;
 }
@@ -1548,21 +1470,17 @@ MLP_API int mlp_gemm_forward_stats_pool(int b, int m, int k, int r, const float 
       (reinterpret_cast<size_t>(w) & 15) != 0)
     return (int)hipErrorInvalidValue;
   hipStream_t stream = (hipStream_t)stream_;
-  if (gemm_x6() && mlp_fwd128_enabled_for(b, m, k, r))  // (128, 128): 64-column pairs, no other kernel may run
-    return mlp_fwd128_launch(b, r, ns, 0, w, x, scale, shift, gamma, y, pairs, ext, stream);
   // (256, 128), nsample 16 / 32: the persistent T-form kernel (same pairs, same ext; y may be NULL)
-  if (gemm_x6() && mlp_pool_fwd256_supported(b, m, k, r, ns, w, x) && (reinterpret_cast<size_t>(y) & 15) == 0)
+  if (mlp_pool_fwd256_supported(b, m, k, r, ns, w, x) && (reinterpret_cast<size_t>(y) & 15) == 0)
     return mlp_pool_fwd256_launch(b, r, ns, w, x, scale, shift, gamma, y, pairs, ext, stream);
   OperandB op = {x, nullptr, scale, shift, nullptr, nullptr, nullptr};
   const size_t in_stride = (size_t)k * r, out_stride = (size_t)m * r;
   const size_t plane = (size_t)b * m * (r / ns);
   const unsigned a_bytes = (unsigned)(4 * (size_t)m * k);
-#define POOLED_X(TM, TN, WM, WN, NS, X6)                                                           \
-  hipLaunchKernelGGL((gemm_nn2_kernel<TM, TN, WM, WN, OP_BNRELU, false, true, true, NS, X6>),      \
+#define POOLED(TM, TN, WM, WN, NS)                                                                 \
+  hipLaunchKernelGGL((gemm_nn2_kernel<TM, TN, WM, WN, OP_BNRELU, false, true, true, NS>),          \
                      dim3(r / TN, 1, b), dim3(256), 0, stream, m, k, r, w, k, a_bytes, op, y,     \
                      in_stride, out_stride, pairs, m, ext, plane, gamma)
-#define POOLED(TM, TN, WM, WN, NS)                                                                 \
-  do { if (gemm_x6()) POOLED_X(TM, TN, WM, WN, NS, true); else POOLED_X(TM, TN, WM, WN, NS, false); } while (0)
   if (m == 256 && ns == 16) POOLED(256, 64, 4, 1, 16);
   else if (m == 256 && ns == 32) POOLED(256, 64, 4, 1, 32);
   else if (m == 256) POOLED(256, 64, 4, 1, 64);
@@ -1570,7 +1488,6 @@ MLP_API int mlp_gemm_forward_stats_pool(int b, int m, int k, int r, const float 
   else if (ns == 32) POOLED(128, 128, 2, 2, 32);
   else POOLED(128, 128, 2, 2, 64);
 #undef POOLED
-#undef POOLED_X
   return pn2_launch_status();
 }
 
@@ -1586,14 +1503,9 @@ MLP_API int mlp_gemm_forward_stats_lin4(int b, int r, const float *w, const floa
       (reinterpret_cast<size_t>(w) & 15) != 0 || (reinterpret_cast<size_t>(w1) & 15) != 0)
     return (int)hipErrorInvalidValue;
   OperandB op = {x4, nullptr, scale, shift, nullptr, nullptr, nullptr, nullptr, 0, 0, w1};
-  if (gemm_x6())
-    hipLaunchKernelGGL((gemm_nn2_kernel<64, 128, 2, 2, OP_LIN4, false, true, true, 0, true>),
-                       dim3(r / 128, 1, b), dim3(256), 0, (hipStream_t)stream_, m, k, r, w, k,
-                       (unsigned)(4 * (size_t)m * k), op, y, (size_t)4 * r, (size_t)m * r, pairs, m);
-  else
-    hipLaunchKernelGGL((gemm_nn2_kernel<64, 128, 2, 2, OP_LIN4, false, true, true>),
-                       dim3(r / 128, 1, b), dim3(256), 0, (hipStream_t)stream_, m, k, r, w, k,
-                       (unsigned)(4 * (size_t)m * k), op, y, (size_t)4 * r, (size_t)m * r, pairs, m);
+  hipLaunchKernelGGL((gemm_nn2_kernel<64, 128, 2, 2, OP_LIN4, false, true, true>),
+                     dim3(r / 128, 1, b), dim3(256), 0, (hipStream_t)stream_, m, k, r, w, k,
+                     (unsigned)(4 * (size_t)m * k), op, y, (size_t)4 * r, (size_t)m * r, pairs, m);
   return pn2_launch_status();
 }
 
@@ -1636,10 +1548,9 @@ static int wgrad_direct_r_per_slice(int b, int m, int k, int r);
 // Both backward GEMMs of a small layer in ONE launch (gemm_small_backward_pair_kernel): 1 when
 // the layer is in the small regime of both kernels.
 MLP_API int mlp_gemm_backward_small_supported(int b, int m, int k, int r, int pmode, int qmode) {
-  static const bool off = getenv("MLP_SMALL_BWD_PAIR") && atoi(getenv("MLP_SMALL_BWD_PAIR")) == 0;
   const char *env = getenv("MLP_SMALL_GEMM_COLS");
   const long long small_cols = env ? atoll(env) : 16384;
-  return !off && b > 0 && m > 0 && k > 0 && (long long)b * r <= small_cols &&
+  return b > 0 && m > 0 && k > 0 && (long long)b * r <= small_cols &&
          wgrad_direct_ok(b, m, k, r, pmode, qmode);
 }
 
@@ -1754,8 +1665,7 @@ static int wgrad_r_per_slice(int b, int m, int k, int r) {
   // is exactly one resident round of workgroups (3 per CU, 2 for the 192-wide tile whose
   // six accumulators cost a wave of occupancy), minus 16 CUs of slack for the index-chain
   // kernels of the next batch that run beside it -- a partial second round is pure tail
-  static const long long forced = getenv("MLP_WGRAD_WGS") ? atoll(getenv("MLP_WGRAD_WGS")) : 0;
-  const long long target = forced > 0 ? forced : (wgrad_next_tile(k) == 192 ? 480 : 720);
+  const long long target = wgrad_next_tile(k) == 192 ? 480 : 720;
   const long long tiles = (long long)pn2_ceil_div(m, 64) * b;
   long long slices = (target + tiles / 2) / tiles;
   if (slices < 1) slices = 1;
@@ -1774,12 +1684,12 @@ MLP_API size_t mlp_gemm_wgrad_workspace_floats(int b, int m, int k, int r) {
 }
 
 // the direct-fragment kernel: small layers only (its operands must stay in L2: every 64 x 64 block
-// of dW re-reads its rows), operand modes without the pooled gradient; MLP_WGRAD_DIRECT=0 disables
+// of dW re-reads its rows: at most kWgradDirectCols columns over the batch), operand modes
+// without the pooled gradient
+constexpr long long kWgradDirectCols = 32768;
 static bool wgrad_direct_ok(int b, int m, int k, int r, int pmode, int qmode) {
-  static const bool off = getenv("MLP_WGRAD_DIRECT") && atoi(getenv("MLP_WGRAD_DIRECT")) == 0;
-  static const long long cols = getenv("MLP_WGRAD_DIRECT_COLS") ? atoll(getenv("MLP_WGRAD_DIRECT_COLS")) : 32768;
-  return !off && gemm_x6() && (pmode == OP_DIRECT || pmode == OP_DY) &&
-         (qmode == OP_DIRECT || qmode == OP_BNRELU) && (long long)b * r <= cols && r >= 32;
+  return (pmode == OP_DIRECT || pmode == OP_DY) && (qmode == OP_DIRECT || qmode == OP_BNRELU) &&
+         (long long)b * r <= kWgradDirectCols && r >= 32;
 }
 
 static int wgrad_direct_r_per_slice(int b, int m, int k, int r) {
@@ -1822,20 +1732,11 @@ static int wgrad_run(int b, int m, int k, int r, int pmode, const OperandB &P, i
       const int tk = wgrad_next_tile(k - kb);                                                   \
       const int ke = kb + tk < k ? kb + tk : k;                                                 \
       dim3 grid(1, pn2_ceil_div(m, 64), b * slices);                                            \
-      if (tk == 256 && wgrad_x6())                                                              \
-        hipLaunchKernelGGL((gemm_wgrad_kernel<PM, QM, 2, 4, 1, true>), grid, dim3(256), 0, stream, m, \
-                           kb, ke, k, r, per, P, Q, workspace, ps, qs);                         \
-      else if (tk == 256)                                                                       \
+      if (tk == 256)                                                                            \
         hipLaunchKernelGGL((gemm_wgrad_kernel<PM, QM, 2, 4, 1>), grid, dim3(256), 0, stream, m, \
-                           kb, ke, k, r, per, P, Q, workspace, ps, qs);                         \
-      else if (tk == 192 && wgrad_x6())                                                          \
-        hipLaunchKernelGGL((gemm_wgrad_kernel<PM, QM, 3, 2, 2, true>), grid, dim3(256), 0, stream, m, \
                            kb, ke, k, r, per, P, Q, workspace, ps, qs);                         \
       else if (tk == 192)                                                                       \
         hipLaunchKernelGGL((gemm_wgrad_kernel<PM, QM, 3, 2, 2>), grid, dim3(256), 0, stream, m, \
-                           kb, ke, k, r, per, P, Q, workspace, ps, qs);                         \
-      else if (tk == 128 && wgrad_x6())                                                          \
-        hipLaunchKernelGGL((gemm_wgrad_kernel<PM, QM, 2, 2, 2, true>), grid, dim3(256), 0, stream, m, \
                            kb, ke, k, r, per, P, Q, workspace, ps, qs);                         \
       else if (tk == 128)                                                                       \
         hipLaunchKernelGGL((gemm_wgrad_kernel<PM, QM, 2, 2, 2>), grid, dim3(256), 0, stream, m, \

@@ -25,7 +25,6 @@
 // chunk); 32-column chunks; roles of equal matrix time, see the kernel.
 #include "common.h"
 #include "mlp_operand.h"
-#include <stdlib.h>
 #include <mutex>
 #include <type_traits>
 
@@ -553,8 +552,7 @@ constexpr size_t kGramLds = 2 * (3 * (128 + 64) * 80 + 64 * 144) + 64 * 16 + 64 
 // 1 when mlp_pool_gram_backward covers the layer: (m, k) = (128, 64), nsample 16 / 32 / 64, whole
 // 32-column chunks per cloud
 MLP_API int mlp_pool_gram_supported(int b, int m, int k, int r, int ns) {
-  static const bool off = getenv("MLP_POOL_GRAM") && atoi(getenv("MLP_POOL_GRAM")) == 0;
-  if (off || b <= 0 || m != kGM || k != kGK || r <= 0 || r % 32 != 0) return 0;
+  if (b <= 0 || m != kGM || k != kGK || r <= 0 || r % 32 != 0) return 0;
   if ((ns != 16 && ns != 32 && ns != 64) || r % ns != 0) return 0;
   return (long long)b * (r / 32) >= 64 ? 1 : 0;
 }

@@ -780,14 +780,7 @@ int gram256_workgroups(int b, int r, int least) {
   if (g > total / least) g = total / least;
   return (int)(g < 1 ? 1 : g);
 }
-int gram256_dgrad_least() {
-  static const int v = getenv("MLP_GRAM256_DGRAD_CHUNKS") ? atoi(getenv("MLP_GRAM256_DGRAD_CHUNKS")) : 8;
-  return v > 0 ? v : 8;
-}
-int gram256_wgrad_least() {
-  static const int v = getenv("MLP_GRAM256_WGRAD_CHUNKS") ? atoi(getenv("MLP_GRAM256_WGRAD_CHUNKS")) : 16;
-  return v > 0 ? v : 16;
-}
+constexpr int kDgradLeast = 8, kWgradLeast = 16;
 
 constexpr size_t kDgradLds = 2 * (3 * (size_t)kHQIMG + kHRAW) + 3 * (size_t)(kHSIMG + kHSP) + kHK * 16 + kHK * 4;
 constexpr size_t kWgradLds = 2 * 3 * (size_t)kHQIMG;
@@ -800,20 +793,18 @@ static_assert(kDgradLds <= 160 * 1024, "LDS of the data-gradient pass");
 // 1 when mlp_pool_gram256_backward covers the layer: (m, k) = (256, 128), nsample 16 / 32, whole
 // 32-column chunks per cloud
 MLP_API int mlp_pool_gram256_supported(int b, int m, int k, int r, int ns) {
-  static const bool off = (getenv("MLP_POOL_GRAM") && atoi(getenv("MLP_POOL_GRAM")) == 0) ||
-                          (getenv("MLP_POOL_GRAM256") && atoi(getenv("MLP_POOL_GRAM256")) == 0);
   // worth it from SA2's size on (B = 8: 8192 chunks; measured: 308 us against 355 there, 154 against
   // 105 at SA3's 2048 chunks -- the two passes' fixed costs); read on every call: tests lower it
   const long long least = getenv("MLP_POOL_GRAM256_MIN_CHUNKS") ? atoll(getenv("MLP_POOL_GRAM256_MIN_CHUNKS")) : 4096;
-  if (off || b <= 0 || m != kHM || k != kHK || r <= 0 || r % 32 != 0) return 0;
+  if (b <= 0 || m != kHM || k != kHK || r <= 0 || r % 32 != 0) return 0;
   if ((ns != 16 && ns != 32) || r % ns != 0) return 0;
   return (long long)b * (r / 32) >= least ? 1 : 0;
 }
 
 // number of per-workgroup partials of stats_part (128, parts, 2) and floats of workspace
-MLP_API int mlp_pool_gram256_parts(int b, int r) { return gram256_workgroups(b, r, gram256_dgrad_least()); }
+MLP_API int mlp_pool_gram256_parts(int b, int r) { return gram256_workgroups(b, r, kDgradLeast); }
 MLP_API size_t mlp_pool_gram256_workspace_floats(int b, int r, int ns) {
-  const size_t g = (size_t)gram256_workgroups(b, r, gram256_wgrad_least());
+  const size_t g = (size_t)gram256_workgroups(b, r, kWgradLeast);
   const size_t groups = ns > 0 ? (size_t)(r / ns) : 0;
   // qp (512) + M3 (16384) + v (128) + the records (2 words per group and channel) + partials per
   // workgroup + the sums as doubles
@@ -836,8 +827,8 @@ MLP_API int mlp_pool_gram256_backward(int b, int r, int ns, const float *w3, con
       (reinterpret_cast<size_t>(y2) & 15))
     return (int)hipErrorInvalidValue;
   hipStream_t stream = (hipStream_t)stream_;
-  const int g1 = gram256_workgroups(b, r, gram256_dgrad_least());
-  const int g2 = gram256_workgroups(b, r, gram256_wgrad_least());
+  const int g1 = gram256_workgroups(b, r, kDgradLeast);
+  const int g2 = gram256_workgroups(b, r, kWgradLeast);
   float *qp = workspace, *m3 = qp + 512, *v = m3 + 16384;
   const int groups = r / ns;
   uint2 *recs = reinterpret_cast<uint2 *>(v + 128);  // (16-byte aligned: 17 024 floats in)

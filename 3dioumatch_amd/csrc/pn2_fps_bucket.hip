@@ -61,7 +61,7 @@ typedef int fps_i32x4 __attribute__((ext_vector_type(4)));
 typedef float fps_f32x4 __attribute__((ext_vector_type(4)));
 __device__ fps_f32x4 fps_buffer_load_x4(fps_i32x4 rsrc, int voffset, int soffset, int aux)
     __asm("llvm.amdgcn.raw.buffer.load.v4f32");
-__device__ void fps_buffer_store_f32(float data, fps_i32x4 rsrc, int voffset, int soffset, int aux)
+__device__ void fps_raw_store_f32(float data, fps_i32x4 rsrc, int voffset, int soffset, int aux)
     __asm("llvm.amdgcn.raw.buffer.store.f32");
 
 namespace {
@@ -428,7 +428,7 @@ fps_bucket_rounds_kernel(int n, int m, int log2bs, size_t cloud_stride,
               const float d = sqdist3(q[k0 + k].x, q[k0 + k].y, q[k0 + k].z, x1, y1, z1);
               const float told = q[k0 + k].w;
               asm("v_min_f32 %0, %1, %2" : "=v"(d2[k]) : "v"(d), "v"(told));
-              fps_buffer_store_f32(d2[k], rec_rs, rec_off + 12, (s * kWave + bk[k0 + k]) * kBucketStep, 0);
+              fps_raw_store_f32(d2[k], rec_rs, rec_off + 12, (s * kWave + bk[k0 + k]) * kBucketStep, 0);
             }
 #ifdef FPS_PROBE
             if (probe_first) { FPS_STAMP(4) }

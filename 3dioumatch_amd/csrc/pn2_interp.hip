@@ -9,7 +9,6 @@
 //  * three_interpolate: lanes own consecutive query points j (coalesced idx/weight/out
 //    traffic), and walk a group of channels so idx/weight are fetched once.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -356,11 +355,10 @@ PN2_API int pn2_three_nn(int b, int n, int m, const float *unknown, const float 
   if (b <= 0 || n <= 0) return 0;
   // a launch of the plain kernel that leaves most SIMDs with one wave or none: the split form
   // (one tile of candidates only: its fold assumes the quarters are in index order)
-  static const bool split_off = getenv("PN2_THREE_NN_SPLIT") && atoi(getenv("PN2_THREE_NN_SPLIT")) == 0;
   // (measured: 8 x 9216 queries x 1024 candidates 107 -> 51 us, 8 x 2048 x 1024 104 -> 18; at
   // 8 x 32768 -- 1024 workgroups of the plain kernel, four per CU -- the branchy plain scan wins, 125
   // against 133 us: the threshold is two workgroups per CU)
-  if (!split_off && m > 0 && m <= kNNTile && (long long)b * pn2_ceil_div(n, 256) <= 512) {
+  if (m > 0 && m <= kNNTile && (long long)b * pn2_ceil_div(n, 256) <= 512) {
     dim3 grid(pn2_ceil_div(n, kWave), b);
     hipLaunchKernelGGL(three_nn_split_kernel, grid, dim3(256), 0, (hipStream_t)stream_, n, m, unknown,
                        known, dist2, idx);

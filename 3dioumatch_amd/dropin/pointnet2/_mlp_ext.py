@@ -11,6 +11,9 @@ import torch
 
 from pointnet2._ext import _L, _lib, _stream
 
+# least number of columns (batch x points) from which small_backward_prefers_dy writes dy once
+SMALL_BWD_DY_COLS = 4096
+
 
 def _f32c(t, name):
     if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
@@ -511,15 +514,11 @@ def gemm_backward_fused(w, x, xcoeff=None, fly=None, pooled=None, xstats=None, n
     xs, xh = xcoeff if xcoeff is not None else (None, None)
     xmean, xinv, xgamma, xtraining = xstats if qmode != 0 else (None, None, None, False)
     parts = int(_lib.mlp_gemm_backward_fused_stats_parts(b, m, k, r)) if qmode != 0 else 0
-    gated = lin_w is not None and bool(_lib.mlp_gemm_backward_fused_lin4_gated())
-    if gated:
+    if lin_w is not None:
         _f32c(lin_w, "lin_w")
         if parts <= 0:
             raise RuntimeError("gemm_backward_fused(lin_w): no partials for this shape")
         dx = torch.empty((parts, k, 4), dtype=torch.float32, device=x.device)  # the gated sums' partials
-    elif lin_w is not None:
-        _f32c(lin_w, "lin_w")
-        dx = torch.empty((b, k) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
     else:
         dx = torch.empty_like(x) if need_dx else None
     dw = torch.empty((m, k), dtype=torch.float32, device=x.device)
@@ -545,7 +544,7 @@ def gemm_backward_fused(w, x, xcoeff=None, fly=None, pooled=None, xstats=None, n
                                                    small[2:].data_ptr(), _stream(x)),
                      "mlp_bn_backward_finalize")
             below = (small[0], small[1], small[2:])
-    if gated:
+    if lin_w is not None:
         dx = GatedSums(dx)
     return dx, dw, below
 
@@ -581,13 +580,12 @@ def small_backward_prefers_dy(w, y):
     of the K/64 row tiles of the data gradient and every tile of the weight gradient re-forms the
     same dy tile (6 instructions + the bf16 split per element, up to 8 times over).  Measured
     (tools/small_bwd_form_bench.py): 256 x 512 at 8 x 1024 columns 105 -> 83 us, 256 x 256 60 -> 48,
-    at 8 x 512 columns 39 -> 37, 128 x 128 at 8 x 256 columns 19.5 = 19.4.  MLP_SMALL_BWD_DY_COLS:
-    least number of columns (default 4096, 0 = never)."""
+    at 8 x 512 columns 39 -> 37, 128 x 128 at 8 x 256 columns 19.5 = 19.4: from SMALL_BWD_DY_COLS
+    columns on."""
     m, k = w.shape
     b = y.shape[0]
     r = y.numel() // (b * m)
-    least = int(os.environ.get("MLP_SMALL_BWD_DY_COLS", "4096"))
-    return least > 0 and b * r >= least and bool(_lib.mlp_gemm_backward_small_supported(b, m, k, r, 0, 0))
+    return b * r >= SMALL_BWD_DY_COLS and bool(_lib.mlp_gemm_backward_small_supported(b, m, k, r, 0, 0))
 
 
 def gemm_backward_small(w, x, xcoeff=None, dy=None, fly=None, need_dx=True):
@@ -641,7 +639,7 @@ def wgrad_first4(w, x, fly, moments=None):
     m, k = w.shape
     b = x.shape[0]
     r = x.numel() // (b * x.shape[1])
-    if (m, k) != (64, 4) or x.shape[1] != 4 or r % 4 != 0 or os.environ.get("MLP_WGRAD_FIRST4", "1") == "0":
+    if (m, k) != (64, 4) or x.shape[1] != 4 or r % 4 != 0:
         return None
     _f32c(w, "w"); _f32c(x, "x")
     _, dz, scale, shift, mean, invstd, coef = fly
@@ -687,8 +685,6 @@ def lin4_supported(w0, w1, x):
     kernels of the second layer (w1 (64,64))?"""
     if os.environ.get("MLP_FIRST4_VIRTUAL", "1") == "0":
         return False
-    if os.environ.get("MLP_WGRAD_FIRST4", "1") == "0":
-        return False  # the virtual layer's weight gradient only exists as mlp_wgrad_first4
     if tuple(w0.shape) != (64, 4) or tuple(w1.shape) != (64, 64) or x.shape[1] != 4:
         return False
     b = x.shape[0]
@@ -729,8 +725,6 @@ def gemm_forward_bn_lin4(w, x4, w1, coeff1, gamma, beta, running_mean, running_v
 def chain_lin4_supported(w0, w1, w2, x4, ns):
     """Can layers 2 and 3 of a 4 -> 64 -> 64 -> 128 module run as ONE register-chained kernel
     (csrc/mlp_chain.hip) on x4 (B,4,m,ns)?"""
-    if os.environ.get("MLP_CHAIN_FWD", "1") == "0":
-        return False
     if tuple(w0.shape) != (64, 4) or tuple(w1.shape) != (64, 64) or tuple(w2.shape) != (128, 64):
         return False
     if x4.dim() != 4 or x4.shape[1] != 4 or x4.shape[3] != ns:
@@ -811,7 +805,7 @@ def pool_gram_supported(w, y_in, ns):
     csrc/mlp_pool_gram256.hip)?  Only the (B, *, m, ns) extent of y_in is looked at (the chained SA1
     form asks with its 4-channel input: the layer's own input never exists there)."""
     entry = _gram_entry(w)
-    if os.environ.get("MLP_POOL_GRAM", "1") == "0" or entry is None or y_in.dim() != 4:
+    if entry is None or y_in.dim() != 4:
         return False
     b, r = y_in.shape[0], y_in.shape[2] * y_in.shape[3]
     return bool(entry[0](b, w.shape[0], w.shape[1], r, int(ns)))

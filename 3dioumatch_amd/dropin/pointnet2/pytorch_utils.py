@@ -487,14 +487,6 @@ def bump_batches_tracked(counter):
         counter.add_(1)
 
 
-def _fused_enabled():
-    return os.environ.get("PN2_FUSED_MLP", "1") != "0"
-
-
-def _mfma_enabled():
-    return os.environ.get("PN2_MFMA_MLP", "1") != "0"
-
-
 class SharedMLP(nn.Sequential):
     """Stack of 1x1 Conv2d (+BN+ReLU) layers `layer0..layerK` applied to a (B, C, npoint,
     nsample) tensor: the grouped shared MLP of a set-abstraction layer.
@@ -530,7 +522,7 @@ class SharedMLP(nn.Sequential):
 
     def _use_fused(self, x):
         return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and len(self) > 0
-                and _fused_enabled() and all(self._fusable(layer) for layer in self))
+                and all(self._fusable(layer) for layer in self))
 
     def _run(self, x, pool, pre=None):
         from pointnet2 import _mlp_ext as K
@@ -544,18 +536,18 @@ class SharedMLP(nn.Sequential):
         # the module's own counters for the one-launch reductions of its layers (include/mlp_hip.h
         # `tickets`): nothing in the library is keyed by stream
         tickets = K.tickets_of(self, max(layer.conv.out_channels for layer in layers), x.device)
-        if _mfma_enabled():
-            bns = [next(layer.bn.children()) for layer in layers]
-            training = bns[0].training
-            if all(bn.training == training for bn in bns):
-                params = []
-                for layer, bn in zip(layers, bns):
-                    if training:
-                        bump_batches_tracked(bn.num_batches_tracked)
-                    params += [layer.conv.weight, bn.weight, bn.bias, bn.running_mean,
-                               bn.running_var]
-                return _FusedMLPChain.apply(x, pool, training, [bn.momentum for bn in bns],
-                                            [bn.eps for bn in bns], pre, tickets, *params)
+        bns = [next(layer.bn.children()) for layer in layers]
+        training = bns[0].training
+        if all(bn.training == training for bn in bns):
+            params = []
+            for layer, bn in zip(layers, bns):
+                if training:
+                    bump_batches_tracked(bn.num_batches_tracked)
+                params += [layer.conv.weight, bn.weight, bn.bias, bn.running_mean,
+                           bn.running_var]
+            return _FusedMLPChain.apply(x, pool, training, [bn.momentum for bn in bns],
+                                        [bn.eps for bn in bns], pre, tickets, *params)
+        # (mixed train / eval BatchNorm: layer by layer)
         for i, layer in enumerate(layers):
             bn = next(layer.bn.children())
             y = layer.conv(x)
@@ -575,10 +567,10 @@ class SharedMLP(nn.Sequential):
     def pregather_ok(self, xyz, new_xyz, features, m, ns):
         """Can forward_pregathered replace forward_pooled(grouped) for these inputs (m groups of
         ns members)?"""
-        if features is None or len(self) < 2 or not _pregather_enabled():
+        if features is None or len(self) < 2:
             return False
-        if not (features.is_cuda and features.dtype == torch.float32 and _fused_enabled()
-                and _mfma_enabled() and all(self._fusable(layer) for layer in self)):
+        if not (features.is_cuda and features.dtype == torch.float32
+                and all(self._fusable(layer) for layer in self)):
             return False
         bns = [next(layer.bn.children()) for layer in self]
         if any(bn.training != bns[0].training for bn in bns):
@@ -602,10 +594,10 @@ class SharedMLP(nn.Sequential):
         from pointnet2 import _ext
         layers = list(self)
         recording = torch.is_grad_enabled()
-        if recording and (features.requires_grad or os.environ.get("PN2_INTERP_FIRST_TRAIN", "1") == "0"):
+        if recording and features.requires_grad:
             return False  # (a gradient w.r.t. the features would need the scatter form)
         return (os.environ.get("PN2_INTERP_FIRST", "1") != "0"
-                and _mfma_enabled() and len(layers) >= 2 and features.is_cuda and features.dim() == 3
+                and len(layers) >= 2 and features.is_cuda and features.dim() == 3
                 and features.dtype == torch.float32 and hasattr(_ext, "three_interpolate_affine")
                 and layers[0].conv.weight.shape[1] == features.shape[1] + 3
                 and _ext.three_interpolate_affine_supported(layers[0].conv.weight.shape[0],
@@ -770,10 +762,6 @@ class _PackPoints(Function):
             dxyz = dc[:, :n].contiguous() if ctx.needs_input_grad[0] else None
             dnew = dc[:, n:].contiguous() if ctx.needs_input_grad[1] else None
         return dxyz, dnew, dfeat, None
-
-
-def _pregather_enabled():
-    return os.environ.get("PN2_PREGATHER", "1") != "0"
 
 
 class FC(nn.Sequential):

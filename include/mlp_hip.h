@@ -293,9 +293,6 @@ size_t mlp_gemm_backward_fused_workspace_floats(int b, int m, int k, int r);
  * (sum g, sum g*xhat) with g = dq * [x*xscale + xshift > 0], parts =
  * mlp_gemm_backward_fused_stats_parts() -- the input of mlp_bn_backward_finalize, in place of
  * that layer's mlp_bn_relu_backward_stats pass over (x, dq). */
-/* 1: qmode 4 leaves the gated sums in dq (above); 0 (MLP_LIN4_GATED=0): dq (b,64,r) is written as for
- * the other modes and mlp_wgrad_first4 reads it (the round-5 form, pytorch_utils.py:70-124 unchanged) */
-int mlp_gemm_backward_fused_lin4_gated(void);
 int mlp_gemm_backward_fused(int b, int m, int k, int r, const float *w, int pmode, const float *y,
                             const float *dz, const int *argmax, int ns, const float *scale,
                             const float *shift, const float *mean, const float *invstd,
