@@ -790,15 +790,20 @@ static_assert(kDgradLds <= 160 * 1024, "LDS of the data-gradient pass");
 
 #define MLP_API extern "C" __attribute__((visibility("default")))
 
-// 1 when mlp_pool_gram256_backward covers the layer: (m, k) = (256, 128), nsample 16 / 32, whole
-// 32-column chunks per cloud
+// what mlp_pool_gram256_backward covers: (m, k) = (256, 128), nsample 16 / 32, whole 32-column
+// chunks per cloud
+static bool gram256_covers(int b, int m, int k, int r, int ns) {
+  return b > 0 && m == kHM && k == kHK && r > 0 && r % 32 == 0 && (ns == 16 || ns == 32) && r % ns == 0;
+}
+
+// 1 when the forward should leave the layer's backward to mlp_pool_gram256_backward: covered, and
+// worth it from SA2's size on (B = 8: 8192 chunks; measured: 308 us against 355 there, 154 against
+// 105 at SA3's 2048 chunks -- the two passes' fixed costs).  The threshold is read on every call
+// (tests lower it); the backward does not re-check it, so a forward decision made under one value
+// holds for its backward
 MLP_API int mlp_pool_gram256_supported(int b, int m, int k, int r, int ns) {
-  // worth it from SA2's size on (B = 8: 8192 chunks; measured: 308 us against 355 there, 154 against
-  // 105 at SA3's 2048 chunks -- the two passes' fixed costs); read on every call: tests lower it
   const long long least = getenv("MLP_POOL_GRAM256_MIN_CHUNKS") ? atoll(getenv("MLP_POOL_GRAM256_MIN_CHUNKS")) : 4096;
-  if (b <= 0 || m != kHM || k != kHK || r <= 0 || r % 32 != 0) return 0;
-  if ((ns != 16 && ns != 32) || r % ns != 0) return 0;
-  return (long long)b * (r / 32) >= least ? 1 : 0;
+  return gram256_covers(b, m, k, r, ns) && (long long)b * (r / 32) >= least ? 1 : 0;
 }
 
 // number of per-workgroup partials of stats_part (128, parts, 2) and floats of workspace
@@ -821,7 +826,7 @@ MLP_API int mlp_pool_gram256_backward(int b, int r, int ns, const float *w3, con
                                       const float *mean3, const float *invstd3, const int *argmax,
                                       const float *dpooled, const float *ymax, float *dq, float *dw3,
                                       float *stats_part, float *workspace, void *stream_) {
-  if (!mlp_pool_gram256_supported(b, kHM, kHK, r, ns) || !w3 || !y2 || !sc2 || !sh2 || !mean2 || !invstd2 ||
+  if (!gram256_covers(b, kHM, kHK, r, ns) || !w3 || !y2 || !sc2 || !sh2 || !mean2 || !invstd2 ||
       !coef3 || !sc3 || !sh3 || !mean3 || !invstd3 || !argmax || !dpooled || !ymax || !dq || !dw3 ||
       !stats_part || !workspace || (reinterpret_cast<size_t>(workspace) & 15) ||
       (reinterpret_cast<size_t>(y2) & 15))

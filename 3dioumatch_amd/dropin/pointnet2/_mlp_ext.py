@@ -328,12 +328,13 @@ def gemm_forward_bn(w, x, coeff, gamma, beta, running_mean, running_var, momentu
 
 
 def forward_pool_supported(w, x, coeff):
-    """Does gemm_forward_bn(w, x, coeff, ..., pool=True) leave the pooled extrema behind (x (B,K,m,ns))?"""
-    if x.dim() != 4 or coeff is None or w.data_ptr() % 16 != 0:
+    """Does gemm_forward_bn(w, x, coeff, ..., pool=True) leave the pooled extrema behind (x (B,K,m,ns),
+    or that shape as a tuple; coeff: any value but None where the forward decides before it exists)?"""
+    shape = x if isinstance(x, tuple) else tuple(x.shape)
+    if len(shape) != 4 or coeff is None or w.data_ptr() % 16 != 0:
         return False
-    b, k, _, ns = x.shape
-    r = x.numel() // (b * k)
-    return bool(_lib.mlp_gemm_forward_stats_pool_supported(b, w.shape[0], k, r, ns))
+    b, k, m, ns = shape
+    return bool(_lib.mlp_gemm_forward_stats_pool_supported(b, w.shape[0], k, m * ns, ns))
 
 
 def pool_from_extrema(ext, scale, shift):
@@ -588,6 +589,27 @@ def small_backward_prefers_dy(w, y):
     return b * r >= SMALL_BWD_DY_COLS and bool(_lib.mlp_gemm_backward_small_supported(b, m, k, r, 0, 0))
 
 
+def through_bn(w, y, dz, gamma, scale, shift, mean, invstd, training, tickets=None):
+    """BatchNorm + ReLU backward of (y, dz) as the gradient operand of the layer's GEMMs:
+    (dgamma, dbeta, coef, operand keywords) -- dy written once where the pair launch would
+    otherwise re-form it in every tile (small_backward_prefers_dy), else on the fly"""
+    if small_backward_prefers_dy(w, y):
+        dy, dg, dbe = bn_relu_backward(y, dz, gamma, scale, shift, mean, invstd, training, tickets)
+        return dg, dbe, None, dict(dy=dy)
+    dg, dbe, coef = bn_relu_backward_stats(y, dz, gamma, scale, shift, mean, invstd, training, tickets)
+    return dg, dbe, coef, dict(fly=(y, dz, scale, shift, mean, invstd, coef))
+
+
+def both(w, x, xcoeff=None, need_dx=True, **grad):
+    """(dw, dx) of one layer from its gradient operand (dy= / fly= / pooled= as gemm_wgrad takes it):
+    one launch for the two GEMMs where the layer is small, else gemm_wgrad + gemm_dgrad"""
+    pair = None if "pooled" in grad else gemm_backward_small(w, x, xcoeff, need_dx=need_dx, **grad)
+    if pair is not None:
+        return pair[1], pair[0]
+    dw = gemm_wgrad(w.shape[0], w.shape[1], x, xcoeff, **grad)
+    return dw, (gemm_dgrad(w, **grad) if need_dx else None)
+
+
 def gemm_backward_small(w, x, xcoeff=None, dy=None, fly=None, need_dx=True):
     """Both backward GEMMs of a SMALL layer (FP modules, heads, pre-gather first layers) in one
     launch: -> (dx (B,K,...) or None, dw (M,K)), or None when the layer is outside the small
@@ -802,12 +824,13 @@ def _gram_entry(w):
 def pool_gram_supported(w, y_in, ns):
     """Can the backward of the pooled last layer (w (128,64) on y_in (B,64,m,ns), or w (256,128) on
     y_in (B,128,m,ns)) run without that layer's raw output (csrc/mlp_pool_gram.hip,
-    csrc/mlp_pool_gram256.hip)?  Only the (B, *, m, ns) extent of y_in is looked at (the chained SA1
-    form asks with its 4-channel input: the layer's own input never exists there)."""
+    csrc/mlp_pool_gram256.hip)?  Only the (B, *, m, ns) extent of y_in is looked at: y_in may be that
+    shape as a tuple (the forward decides before the layer's input exists)."""
     entry = _gram_entry(w)
-    if entry is None or y_in.dim() != 4:
+    shape = y_in if isinstance(y_in, tuple) else tuple(y_in.shape)
+    if entry is None or len(shape) != 4:
         return False
-    b, r = y_in.shape[0], y_in.shape[2] * y_in.shape[3]
+    b, r = shape[0], shape[2] * shape[3]
     return bool(entry[0](b, w.shape[0], w.shape[1], r, int(ns)))
 
 

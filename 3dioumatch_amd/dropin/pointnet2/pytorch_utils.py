@@ -135,6 +135,100 @@ class _BNReLUMaxPool(Function):
         return dy, dgamma, dbeta, None, None, None, None, None, None
 
 
+class Pregathered(object):
+    """Layer 0 applied BEFORE the gather (csrc/mlp_pregather.hip): the chain's input is then the packed
+    point-major operand src_ext (B, 3+C, n+m) of _mlp_ext.pregather_pack instead of the grouped tensor
+    (B, 3+C, m, ns), which is never formed: y_0 = (W_0 . src_ext)[.., idx] - (W_0 . src_ext)[.., n + j].
+    idx (B,m,ns) int32; inverse = its _ext.group_inverse, or None where no gradient is expected."""
+
+    def __init__(self, idx, inverse, n):
+        self.idx, self.inverse, self.n = idx, inverse, n
+        self.extent = tuple(idx.shape)  # (B, m, ns) of layer 0's output
+
+    def forward(self, w, x, bn=None):
+        """y_0; with bn = (gamma, beta, running_mean, running_var, momentum, eps) also its training-mode
+        (mean, invstd, scale, shift): the gather kernel leaves the rows' moments behind."""
+        from pointnet2 import _mlp_ext as K
+        z = K.gemm_forward(w, x)  # over the n + m points, not the m * ns gathered columns
+        return K.pregather_forward(z, self.idx, self.n, bn)
+
+    def backward(self, w, x, fly, need_dx):
+        """(dw, dx) of layer 0: the BatchNorm / ReLU backward of fly = (y_0, dz, ...) formed on the fly,
+        scatter-added over idx and summed per group; then two GEMMs over the n + m points."""
+        from pointnet2 import _ext
+        from pointnet2 import _mlp_ext as K
+        inverse = self.inverse
+        if inverse is None:  # forward ran without it (no gradient expected then): build it now
+            inverse = _ext.group_inverse(self.idx, self.n)
+        return K.both(w, x, need_dx=need_dx, dy=K.pregather_backward(fly, inverse, self.n))
+
+
+class Interpolated(object):
+    """Layer 0 commuted with a three-point interpolation: its input cat([rel (3 rows),
+    three_interpolate(x, idx, weight)]) over n >> m queries is not formed -- the GEMM runs over the m
+    source points x (B,C,m), then ONE kernel interpolates its output and adds the coordinate rows'
+    part.  idx / weight (B,n,3), rel (B,3,n); shape = (B, c, npoint, nsample) of layer 0's output,
+    n = npoint * nsample.  x carries no gradient (SharedMLP.interp_first_ok)."""
+
+    def __init__(self, idx, weight, rel, shape):
+        self.idx, self.weight, self.rel, self.shape = idx, weight, rel, shape
+        self.extent = (shape[0], shape[2], shape[3])
+
+    def forward(self, w, x):
+        from pointnet2 import _ext
+        from pointnet2 import _mlp_ext as K
+        z = K.gemm_forward(w[:, 3:].contiguous(), x)
+        y = _ext.three_interpolate_affine(z, self.idx, self.weight, w[:, :3].contiguous(), self.rel)
+        return y.view(self.shape)
+
+    def input(self, x):
+        """The layer's real input (B, 3+C, npoint, nsample), for its weight gradient: formed once, in
+        the backward pass."""
+        from pointnet2 import _ext
+        b, c = x.shape[0], 3 + x.shape[1]
+        feats = torch.empty((b, c, self.rel.shape[2]), dtype=torch.float32, device=x.device)
+        feats[:, :3].copy_(self.rel)
+        _ext.three_interpolate_into(x, self.idx, self.weight, feats, 3)
+        return feats.view(b, c, self.shape[2], self.shape[3])
+
+
+def chain_forms(ws, x, pre, pool, training, input_grad):
+    """(first, last): the forms _FusedMLPChain runs its first and last layers in, from host-side
+    shape gates only.  ws: the layers' weights as (out, in) matrices; x, pre as the chain takes them.
+    first: "plain"; "pregathered" / "interpolated" (pre); "virtual": a 4 -> 64 first layer followed
+    by 64 -> 64 (SA1) is never stored -- its output is a rank-4 function of x, so its BatchNorm
+    statistics follow from the second moments of x and every kernel that needs a row of it recomputes
+    that row (four FMAs per element) instead of a 268 MB tensor being written once and read three
+    times; "chained": virtual, and layers 1 + 2 (64 -> 64 -> 128, max-pooled) as ONE register-chained
+    kernel (csrc/mlp_chain.hip) -- layer 1's activation never leaves the registers, statistics and
+    pooled extrema are in-lane reductions of the second GEMM's accumulators.
+    last: "apply" (no pool); "bn_relu_pool" over the stored raw output; "extrema": the per-group
+    extrema the max over nsample needs come out of the GEMM epilogue; "gram": so do they, and the raw
+    output is not stored -- its backward runs from the Gram matrix of the layer's input
+    (csrc/mlp_pool_gram.hip, csrc/mlp_pool_gram256.hip: 537 MB at SA1, 268 MB at SA2)."""
+    from pointnet2 import _mlp_ext as K
+    n = len(ws)
+    if pre is not None and (n < 2 or x.dim() != 3):
+        raise RuntimeError("the pre-gather form needs src_ext (B, 3+C, n+m) and two layers or more")
+    first = "plain"
+    if isinstance(pre, Pregathered):
+        first = "pregathered"
+    elif isinstance(pre, Interpolated):
+        first = "interpolated"
+    elif training and n >= 3 and x.dim() == 4 and not input_grad and K.lin4_supported(ws[0], ws[1], x):
+        chained = pool and n == 3 and K.chain_lin4_supported(ws[0], ws[1], ws[2], x, x.shape[3])
+        first = "chained" if chained else "virtual"
+    if not pool:
+        return first, "apply"
+    b, m, ns = pre.extent if pre is not None else (x.shape[0], x.shape[2], x.shape[3])
+    y_in = (b, ws[-1].shape[1], m, ns)  # the last layer's input
+    if first == "chained":
+        return first, "gram" if K.pool_gram_supported(ws[2], y_in, ns) else "extrema"
+    if not (training and n >= 2 and K.forward_pool_supported(ws[-1], y_in, True)):
+        return first, "bn_relu_pool"
+    return first, "gram" if K.pool_gram_supported(ws[-1], y_in, ns) else "extrema"
+
+
 class _FusedMLPChain(Function):
     """The whole conv(1x1)+BN+ReLU stack (and optionally the final max over nsample) as ONE
     autograd node on the gfx950 kernels: MFMA GEMMs whose operand loads apply the previous
@@ -146,285 +240,145 @@ class _FusedMLPChain(Function):
 
     tickets = the module's counters for the one-launch reductions (_mlp_ext.tickets_of; None: a
     fresh zeroed array per reduction).
-
-    pre = None, or (idx (B,m,ns) int32, inverse (B,entries) int32, n): the first layer is applied
-    BEFORE the gather (csrc/mlp_pregather.hip) -- x is then the packed point-major operand
-    src_ext (B, 3+C, n+m) of _mlp_ext.pregather_pack instead of the grouped tensor (B, 3+C, m, ns),
-    which is never formed: y_0 = (W_0 . src_ext)[.., idx] - (W_0 . src_ext)[.., n + j]."""
+    pre = None, or the Pregathered / Interpolated form of layer 0's input (x is then that form's
+    operand).  chain_forms decides how the first and last layers run; the backward follows the
+    recorded decision."""
 
     @staticmethod
     def forward(ctx, x, pool, training, momenta, epss, pre, tickets, *params):
         from pointnet2 import _mlp_ext as K
-        n_layers = len(params) // 5
-        ctx.tickets = tickets
+        n = len(params) // 5
         x = x.contiguous()
-        ys, coefs = [], []
-        cur, cur_coeff = x, None
-        # A 4 -> 64 first layer followed by a 64 -> 64 layer (SA1) stays VIRTUAL: its output is a
-        # rank-4 function of x, so its BatchNorm statistics follow from the second moments of x
-        # and every kernel that needs a row of it recomputes that row (four FMAs per element)
-        # instead of a 268 MB tensor being written once and read three times.
-        moments = None
-        if pre is not None and (n_layers < 2 or x.dim() != 3):
-            raise RuntimeError("the pre-gather form needs src_ext (B, 3+C, n+m) and two layers or more")
-        virtual0 = (training and n_layers >= 3 and x.dim() == 4 and not ctx.needs_input_grad[0]
-                    and K.lin4_supported(params[0].reshape(params[0].shape[0], -1),
-                                         params[5].reshape(params[5].shape[0], -1), x))
-        # ... and layers 2 + 3 of that module (64 -> 64 -> 128, max-pooled) run as ONE register-chained
-        # kernel (csrc/mlp_chain.hip): layer 2's activation never leaves the registers, statistics
-        # and pooled extrema are in-lane reductions of the second GEMM's accumulators
-        chained = (virtual0 and pool and n_layers == 3 and
-                   K.chain_lin4_supported(params[0].reshape(params[0].shape[0], -1),
-                                          params[5].reshape(params[5].shape[0], -1),
-                                          params[10].reshape(params[10].shape[0], -1), x, x.shape[3]))
-        ext = None
-        gram_last, gram_ns = False, 0
-        for i in range(n_layers):
-            w, gamma, beta, rm, rv = params[5 * i:5 * i + 5]
-            w2 = w.reshape(w.shape[0], -1)
-            if chained and i >= 1:
-                if i == 2:
-                    continue
-                w0 = params[0].reshape(params[0].shape[0], -1)
-                lay = [(params[5 * q].reshape(params[5 * q].shape[0], -1),) + tuple(params[5 * q + 1:5 * q + 5])
-                       + (momenta[q], epss[q]) for q in (1, 2)]
-                # the LAST layer's raw output is not even stored when its backward can run from the
-                # Gram matrix of its input (csrc/mlp_pool_gram.hip): 537 MB at SA1
-                gram = K.pool_gram_supported(lay[1][0], x, x.shape[3])
-                # (a pass that no backward follows -- the EMA teacher -- stores neither raw output:
-                # layer 2's activation goes from one GEMM to the next in registers anyway)
-                y1, c1, y2, c2, ext = K.chain_lin4_forward(x, w0, cur_coeff, lay[0], lay[1],
-                                                           store=any(ctx.needs_input_grad), store_last=not gram)
-                if y1 is None:
-                    y1 = x.new_empty(0)  # never materialised
-                if y2 is None:
-                    y2 = x.new_empty(0)  # never materialised
-                ys += [y1, y2]
-                coefs += [c1, c2]
-                cur, cur_coeff = y2, (c2[2], c2[3])
-                gram_last = gram
-                continue
-            if pre is not None and isinstance(pre[0], str) and i == 0:
-                # ("interp", idx, weight, rel, shape): the layer's input is cat([rel (3 rows),
-                # three_interpolate(x)]) over n >> m queries and the convolution commutes with the
-                # interpolation: GEMM over the m source points, then ONE kernel interpolates its output
-                # and adds the coordinate rows' part (no-grad passes only: the weight gradient would
-                # need the interpolated input after all)
-                from pointnet2 import _ext
-                _, q_idx, q_weight, rel, shape = pre
-                z = K.gemm_forward(w2[:, 3:].contiguous(), x)
-                y = _ext.three_interpolate_affine(z, q_idx, q_weight, w2[:, :3].contiguous(), rel).view(shape)
-                mean, invstd, scale, shift = K.bn_coefficients(y, gamma, beta, rm, rv, momenta[0], epss[0],
-                                                               training, tickets)
-                ys.append(y)
-                coefs.append((mean, invstd, scale, shift))
-                cur, cur_coeff = y, (scale, shift)
-                continue
-            if pre is not None and i == 0:
-                idx, _, npts = pre
-                z = K.gemm_forward(w2, x)  # over the n + m points, not the m * ns gathered columns
-                if training:  # the gather kernel leaves the rows' moments behind
-                    y, mean, invstd, scale, shift = K.pregather_forward(
-                        z, idx, npts, (gamma, beta, rm, rv, momenta[0], epss[0]))
-                else:
-                    y = K.pregather_forward(z, idx, npts)
-                    mean, invstd, scale, shift = K.bn_coefficients(y, gamma, beta, rm, rv, momenta[0],
-                                                                   epss[0], False, tickets)
-                ys.append(y)
-                coefs.append((mean, invstd, scale, shift))
-                cur, cur_coeff = y, (scale, shift)
-                continue
-            if virtual0 and i == 0:
-                moments = K.first4_moments(x)
-                mean, invstd, scale, shift = K.first4_bn(moments, x.numel() // 4, w2, gamma, beta, rm, rv,
-                                                         momenta[0], epss[0])
-                ys.append(x.new_empty(0))  # never materialised
-                coefs.append((mean, invstd, scale, shift))
-                cur, cur_coeff = None, (scale, shift)
-                continue
-            if virtual0 and i == 1:
-                w0 = params[0].reshape(params[0].shape[0], -1)
-                y, mean, invstd, scale, shift = K.gemm_forward_bn_lin4(w2, x, w0, cur_coeff, gamma, beta,
-                                                                       rm, rv, momenta[1], epss[1])
-                ys.append(y)
-                coefs.append((mean, invstd, scale, shift))
-                cur, cur_coeff = y, (scale, shift)
-                continue
-            if training and pool and i == n_layers - 1:
-                # ... and so do the per-group extrema the max over nsample needs.  Where the layer's
-                # backward can run from the Gram matrix of its input (SA2 - SA4: 128 -> 256,
-                # csrc/mlp_pool_gram256.hip) the raw output is not stored at all: 268 MB at SA2
-                epilogue = (i >= 1 and cur is not None and cur.dim() == 4 and cur.numel() > 0
-                            and K.forward_pool_supported(w2, cur, cur_coeff))
-                gram = epilogue and K.pool_gram_supported(w2, cur, cur.shape[3])
-                # ... and in a pass that no backward follows (the EMA teacher, evaluation in training
-                # mode) nobody reads the raw output at all once the extrema are known
-                no_backward = not any(ctx.needs_input_grad)
-                y, mean, invstd, scale, shift, ext = K.gemm_forward_bn(
-                    w2, cur, cur_coeff, gamma, beta, rm, rv, momenta[i], epss[i], pool=True, tickets=tickets,
-                    store=not (gram or (epilogue and no_backward)))
-                if y is None:
-                    y = x.new_empty(0)  # never materialised
-                if gram:
-                    gram_last, gram_ns = True, cur.shape[3]
-            elif training:  # batch statistics come out of the GEMM epilogue where the shape allows
-                y, mean, invstd, scale, shift = K.gemm_forward_bn(w2, cur, cur_coeff, gamma, beta,
-                                                                  rm, rv, momenta[i], epss[i], tickets=tickets)
-            else:
-                y = K.gemm_forward(w2, cur, cur_coeff)
-                mean, invstd, scale, shift = K.bn_coefficients(y, gamma, beta, rm, rv, momenta[i],
-                                                               epss[i], training, tickets)
+        ws = [w.reshape(w.shape[0], -1) for w in params[0::5]]
+        bns = [tuple(params[5 * i + 1:5 * i + 5]) + (momenta[i], epss[i]) for i in range(n)]
+        first, last = chain_forms(ws, x, pre, pool, training, ctx.needs_input_grad[0])
+        # a pass that no backward follows (the EMA teacher, evaluation in training mode) stores no raw
+        # output it can do without
+        store = any(ctx.needs_input_grad)
+        ys, coefs = [], []  # raw output (None: not stored), (mean, invstd, scale, shift) per layer
+        moments, ext = None, None
+        if first in ("virtual", "chained"):
+            moments = K.first4_moments(x)
+            ys.append(None)
+            coefs.append(K.first4_bn(moments, x.numel() // 4, ws[0], *bns[0]))
+        if first == "chained":
+            y1, c1, y2, c2, ext = K.chain_lin4_forward(x, ws[0], coefs[0][2:], (ws[1],) + bns[1],
+                                                       (ws[2],) + bns[2], store=store, store_last=last != "gram")
+            ys += [y1, y2]
+            coefs += [c1, c2]
+        elif first == "virtual":
+            y, *c = K.gemm_forward_bn_lin4(ws[1], x, ws[0], coefs[0][2:], *bns[1])
             ys.append(y)
-            coefs.append((mean, invstd, scale, shift))
-            cur, cur_coeff = y, (scale, shift)
-        extra = []
-        if pool and ext is not None:
-            out, argmax, ymax = K.pool_from_extrema(ext, cur_coeff[0], cur_coeff[1])
-            extra = [argmax, ymax]
-        elif pool:
-            out, argmax, ymax = K.bn_relu_pool(cur, cur_coeff[0], cur_coeff[1])
-            extra = [argmax, ymax]
+            coefs.append(tuple(c))
+        elif first == "pregathered" and training:
+            y, *c = pre.forward(ws[0], x, bns[0])
+            ys.append(y)
+            coefs.append(tuple(c))
+        elif pre is not None:
+            ys.append(pre.forward(ws[0], x))
+            coefs.append(K.bn_coefficients(ys[0], *bns[0], training, tickets))
+        for i in range(len(ys), n):
+            cur, coeff = (x, None) if i == 0 else (ys[i - 1], coefs[i - 1][2:])
+            if i == n - 1 and last in ("extrema", "gram"):
+                y, *c, ext = K.gemm_forward_bn(ws[i], cur, coeff, *bns[i], pool=True, tickets=tickets,
+                                               store=store and last == "extrema")
+            elif training:  # batch statistics come out of the GEMM epilogue where the shape allows
+                y, *c = K.gemm_forward_bn(ws[i], cur, coeff, *bns[i], tickets=tickets)
+            else:
+                y = K.gemm_forward(ws[i], cur, coeff)
+                c = K.bn_coefficients(y, *bns[i], False, tickets)
+            ys.append(y)
+            coefs.append(tuple(c))
+        scale, shift = coefs[-1][2:]
+        argmax = ymax = None
+        if last == "apply":
+            out = K.bn_relu_apply(ys[-1], scale, shift)
+        elif last == "bn_relu_pool":
+            out, argmax, ymax = K.bn_relu_pool(ys[-1], scale, shift)
         else:
-            out = K.bn_relu_apply(cur, cur_coeff[0], cur_coeff[1])
-        flat = [t for c in coefs for t in c]
-        ctx.save_for_backward(x, *ys, *flat, *extra, *params)
-        ctx.n_layers, ctx.pool, ctx.training = n_layers, pool, training
-        ctx.moments = moments  # not None: the first layer is virtual (ys[0] is a placeholder)
-        ctx.gram_last = gram_last  # the last layer's raw output was not stored (ys[-1] is a placeholder)
-        ctx.ns = gram_ns if gram_ns else (x.shape[3] if x.dim() == 4 else 0)
-        ctx.pre = pre
+            out, argmax, ymax = K.pool_from_extrema(ext, scale, shift)
+        ctx.save_for_backward(x, moments, argmax, ymax, *ys, *[t for c in coefs for t in c], *params)
+        ctx.n_layers, ctx.training, ctx.tickets, ctx.pre = n, training, tickets, pre
+        ctx.first, ctx.last = first, last
         return out
 
     @staticmethod
     def backward(ctx, dout):
         from pointnet2 import _mlp_ext as K
-        n, pool, training = ctx.n_layers, ctx.pool, ctx.training
-        saved = ctx.saved_tensors
-        x, ys = saved[0], saved[1:1 + n]
-        pre_gather = ctx.pre
-        if ctx.pre is not None and isinstance(ctx.pre[0], str):
-            # the interpolation-commuted first layer: its weight gradient needs the layer's real
-            # input cat([rel, interpolate(x)]) -- formed here, once, instead of in the forward pass
-            # (the layer's input carries no gradient: asserted by interp_first_ok)
-            from pointnet2 import _ext
-            _, q_idx, q_weight, rel, shape = ctx.pre
-            feats = torch.empty((x.shape[0], 3 + x.shape[1], rel.shape[2]), dtype=torch.float32, device=x.device)
-            feats[:, :3].copy_(rel)
-            _ext.three_interpolate_into(x, q_idx, q_weight, feats, 3)
-            x = feats.view(x.shape[0], 3 + x.shape[1], shape[2], shape[3])
-            pre_gather = None
-        flat = saved[1 + n:1 + 5 * n]
-        coefs = [flat[4 * i:4 * i + 4] for i in range(n)]  # mean, invstd, scale, shift
-        pos = 1 + 5 * n
-        extra = saved[pos:pos + (2 if pool else 0)]
-        params = saved[pos + (2 if pool else 0):]
-        dout = dout.contiguous()
+        n, training, tickets, first, last = ctx.n_layers, ctx.training, ctx.tickets, ctx.first, ctx.last
+        x, moments, argmax, ymax, *rest = ctx.saved_tensors
+        ys, rest = rest[:n], rest[n:]
+        coefs, params = [tuple(rest[4 * i:4 * i + 4]) for i in range(n)], rest[4 * n:]
+        ws = [w.reshape(w.shape[0], -1) for w in params[0::5]]
+        if first == "interpolated":
+            # the layer's weight gradient needs its real input: formed here, once, instead of in the
+            # forward pass
+            x = ctx.pre.input(x)
+        need_dx, virtual = ctx.needs_input_grad[0], first in ("virtual", "chained")
         grads = [None] * (5 * n)
-        need_dx = ctx.needs_input_grad[0]
-        dy_tensor, fly, pooled, below = None, None, None, None
-        dz = dout
+        dz, below = dout.contiguous(), None
         for i in range(n - 1, -1, -1):
-            w, gamma = params[5 * i], params[5 * i + 1]
-            w2 = w.reshape(w.shape[0], -1)
+            gamma = params[5 * i + 1]
             mean, invstd, scale, shift = coefs[i]
-            if i == n - 1 and pool and ctx.gram_last:
+            if i == n - 1 and last == "gram":
                 # the layer's raw output does not exist: both products of its backward from the Gram
                 # matrix of its input and one sparse column per (channel, group)
-                dgamma, dbeta, coef = K.bn_relu_pool_backward_stats(
-                    None, dz, extra[0], extra[1], gamma, scale, shift, mean, invstd, training, ns=ctx.ns,
-                    tickets=ctx.tickets)
-                grads[5 * i + 1], grads[5 * i + 2] = dgamma, dbeta
-                dz, dw_last, below = K.pool_gram_backward(
-                    w2, ys[i - 1], coefs[i - 1], params[5 * (i - 1) + 1], coef, coefs[i], dz, extra[0],
-                    extra[1], ctx.ns, training)
-                grads[5 * i] = dw_last.view_as(w)
+                ns = ys[i - 1].shape[3]
+                dgamma, dbeta, coef = K.bn_relu_pool_backward_stats(None, dz, argmax, ymax, gamma, scale, shift,
+                                                                    mean, invstd, training, ns=ns,
+                                                                    tickets=tickets)
+                dz, dw, below = K.pool_gram_backward(ws[i], ys[i - 1], coefs[i - 1], params[5 * i - 4], coef,
+                                                     coefs[i], dz, argmax, ymax, ns, training)
+                grads[5 * i:5 * i + 3] = dw.view_as(params[5 * i]), dgamma, dbeta
                 continue
-            if i == n - 1 and pool:
+            if i == 0 and virtual:
+                # the layer above never wrote the gradient w.r.t. this layer's output: its one-pass
+                # backward left the gated sums (dz) the weight gradient needs, and the BatchNorm sums
+                dgamma, dbeta, coef = below
+                dw = K.wgrad_first4_from_gated(ws[0], dz, mean, invstd, coef, moments)
+                grads[0:3] = dw.view_as(params[0]), dgamma, dbeta
+                break
+            if i == n - 1 and last != "apply":
                 # dz of the pooled layer is one value per (channel, group): the GEMM operand
                 # loads rebuild dy from y, dpooled and the arg-max, nothing dense is written
-                dgamma, dbeta, coef = K.bn_relu_pool_backward_stats(
-                    ys[i], dz, extra[0], extra[1], gamma, scale, shift, mean, invstd, training,
-                    tickets=ctx.tickets)
-                dy_tensor, fly = None, None
-                pooled = (ys[i], dz, extra[0], scale, shift, mean, invstd, coef)
+                dgamma, dbeta, coef = K.bn_relu_pool_backward_stats(ys[i], dz, argmax, ymax, gamma, scale, shift,
+                                                                    mean, invstd, training, tickets=tickets)
+                grad = dict(pooled=(ys[i], dz, argmax, scale, shift, mean, invstd, coef))
+            elif below is not None or (i == 0 and first == "pregathered"):
+                # the sums left behind by the fused backward GEMM of layer i+1; or the pre-gather layer,
+                # whose dy is never written (pregather_backward forms it on the fly)
+                dgamma, dbeta, coef = below if below is not None else K.bn_relu_backward_stats(
+                    ys[i], dz, gamma, scale, shift, mean, invstd, training, tickets)
+                grad = dict(fly=(ys[i], dz, scale, shift, mean, invstd, coef))
             else:
-                pooled, dy_tensor = None, None
-                if below is not None:  # left behind by the fused backward GEMM of layer i+1
-                    dgamma, dbeta, coef = below
-                elif i == 0 and ctx.moments is not None:
-                    raise RuntimeError("the virtual first layer's BatchNorm sums must come from the "
-                                       "fused backward kernel of the second layer")
-                elif K.small_backward_prefers_dy(w2, ys[i]) and not (pre_gather is not None and i == 0):
-                    # a small layer: dy written once and read by the pair launch, instead of
-                    # re-formed by each of its tiles (_mlp_ext.small_backward_prefers_dy)
-                    dy_tensor, dgamma, dbeta = K.bn_relu_backward(ys[i], dz, gamma, scale, shift, mean,
-                                                                  invstd, training, ctx.tickets)
-                    coef = None
-                else:
-                    dgamma, dbeta, coef = K.bn_relu_backward_stats(ys[i], dz, gamma, scale, shift,
-                                                                   mean, invstd, training, ctx.tickets)
-                fly = None if dy_tensor is not None else (ys[i], dz, scale, shift, mean, invstd, coef)
-            grads[5 * i + 1], grads[5 * i + 2] = dgamma, dbeta
-            m, k = w2.shape
-            if pre_gather is not None and i == 0:
-                # gradient of z_ext = W_0 . src_ext: the BatchNorm / ReLU backward of (y_0, dz) formed
-                # on the fly, scatter-added over idx and summed per group; then two GEMMs over
-                # the n + m points
-                inverse = pre_gather[1]
-                if inverse is None:  # forward ran without it (no gradient expected then): build it now
-                    from pointnet2 import _ext
-                    inverse = _ext.group_inverse(pre_gather[0], pre_gather[2])
-                dzx = K.pregather_backward(fly, inverse, pre_gather[2])
-                pair = K.gemm_backward_small(w2, x, None, dy=dzx, need_dx=need_dx)
-                if pair is not None:
-                    dx, grads[0] = pair[0], pair[1].view_as(w)
-                    continue
-                grads[0] = K.gemm_wgrad(m, k, x, None, dy=dzx).view_as(w)
-                dx = K.gemm_dgrad(w2, dy=dzx).view_as(x) if need_dx else None
-                continue
-            virtual0 = ctx.moments is not None
-            src = x if (i == 0 or (i == 1 and virtual0)) else ys[i - 1]
-            src_coeff = None if i == 0 else (coefs[i - 1][2], coefs[i - 1][3])
-            lin_w = params[0].reshape(params[0].shape[0], -1) if (i == 1 and virtual0) else None
+                dgamma, dbeta, coef, grad = K.through_bn(ws[i], ys[i], dz, gamma, scale, shift, mean, invstd,
+                                                         training, tickets)
+            grads[5 * i + 1:5 * i + 3] = dgamma, dbeta
+            if i == 0 and first == "pregathered":
+                dw, dz = ctx.pre.backward(ws[0], x, grad["fly"], need_dx)
+                grads[0] = dw.view_as(params[0])
+                break
+            lin_w = ws[0] if (i == 1 and virtual) else None
+            src = x if (i == 0 or lin_w is not None) else ys[i - 1]
+            src_coeff = None if i == 0 else coefs[i - 1][2:]
+            src_stats = None if i == 0 else coefs[i - 1][:2] + (params[5 * i - 4], training)
             # both GEMMs from one pass over (y_i, dz) where the shape allows
-            src_stats = None if i == 0 else (coefs[i - 1][0], coefs[i - 1][1],
-                                             params[5 * (i - 1) + 1], training)
-            both = None
-            if dy_tensor is None:
-                both = K.gemm_backward_fused(w2, src, src_coeff, fly, pooled, src_stats,
-                                             need_dx=i > 0 or need_dx, lin_w=lin_w)
-            if lin_w is not None and both is None:
+            fused = None if "dy" in grad else K.gemm_backward_fused(
+                ws[i], src, src_coeff, xstats=src_stats, need_dx=i > 0 or need_dx, lin_w=lin_w, **grad)
+            if fused is not None:
+                dsrc, dw, below = fused  # below: BatchNorm-backward sums of layer i-1
+            elif lin_w is not None:
                 raise RuntimeError("the virtual first layer needs the fused backward kernel of the second")
-            below = None
-            if both is None and pooled is None and lin_w is None and (i > 0 or need_dx):
-                # the small layers: both GEMMs in one launch (no BatchNorm sums for the layer below)
-                pair = K.gemm_backward_small(w2, src, src_coeff, dy=dy_tensor, fly=fly)
-                if pair is not None:
-                    both = (pair[0], pair[1], None)
-            if both is not None:
-                below = both[2]  # BatchNorm-backward sums of layer i-1 (None for the first layer)
-                grads[5 * i] = both[1].view_as(w)
-                if i == 0:
-                    dx = both[0].view_as(x) if need_dx else None
-                else:
-                    dz = both[0]
-            elif i == 0:
-                if isinstance(dz, K.GatedSums):
-                    # the layer above never wrote the gradient w.r.t. this virtual layer's output: its
-                    # one-pass backward left the gated sums the weight gradient needs (and `below`)
-                    dw0 = K.wgrad_first4_from_gated(w2, dz, mean, invstd, coef, ctx.moments)
-                else:
-                    dw0 = K.wgrad_first4(w2, x, fly, ctx.moments) if (fly is not None and not need_dx) else None
-                if dw0 is None and virtual0:
-                    raise RuntimeError("the virtual first layer needs mlp_wgrad_first4")
-                if dw0 is None:
-                    dw0 = K.gemm_wgrad(m, k, x, None, dy_tensor, fly, pooled)
-                grads[0 + 5 * i] = dw0.view_as(w)
-                dx = K.gemm_dgrad(w2, dy_tensor, fly, pooled).view_as(x) if need_dx else None
+            elif i == 0 and not need_dx:  # the weight gradient alone
+                dsrc, below = None, None
+                dw = K.wgrad_first4(ws[0], x, grad["fly"]) if "fly" in grad else None
+                if dw is None:
+                    dw = K.gemm_wgrad(ws[0].shape[0], ws[0].shape[1], x, None, **grad)
             else:
-                grads[5 * i] = K.gemm_wgrad(m, k, src, src_coeff, dy_tensor, fly, pooled).view_as(w)
-                dz = K.gemm_dgrad(w2, dy_tensor, fly, pooled)  # gradient w.r.t. relu(bn(y_{i-1}))
-        return (dx if need_dx else None, None, None, None, None, None, None, *grads)
+                (dw, dsrc), below = K.both(ws[i], src, src_coeff, **grad), None
+            grads[5 * i] = dw.view_as(params[5 * i])
+            dz = dsrc  # gradient w.r.t. relu(bn(y_{i-1})) (the gated sums for a virtual layer 0), or dx
+        return (dz if need_dx else None, None, None, None, None, None, None, *grads)
 
 
 _deferred_counters = None
@@ -586,7 +540,7 @@ class SharedMLP(nn.Sequential):
         xyz (B,N,3), new_xyz (B,m,3), features (B,C,N), idx (B,m,ns) int32, inverse = its
         _ext.group_inverse; -> (B, C', m)."""
         src = _PackPoints.apply(xyz, new_xyz, features, float(scale))
-        return self._run(src, pool=True, pre=(idx, inverse, xyz.shape[1]))
+        return self._run(src, pool=True, pre=Pregathered(idx, inverse, xyz.shape[1]))
 
     def interp_first_ok(self, features, idx):
         """forward_pooled_interp covers: features without gradient, the MFMA chain, two layers or
@@ -611,7 +565,7 @@ class SharedMLP(nn.Sequential):
         pass, for the weight gradient."""
         shape = (features.shape[0], list(self)[0].conv.weight.shape[0], npoint, nsample)
         return self._run(features.contiguous(), pool=True,
-                         pre=("interp", idx.contiguous(), weight.contiguous(), rel.contiguous(), shape))
+                         pre=Interpolated(idx.contiguous(), weight.contiguous(), rel.contiguous(), shape))
 
     def forward_pooled(self, x):
         """max over the last axis of forward(x): (B, C, npoint, nsample) -> (B, C', npoint)."""
@@ -688,20 +642,6 @@ class EvalPlan(object):
             else:
                 self.img = K.eval_stored_prepare(w[1], w[2], self.img)
 
-    def _layer0(self, x, pre):
-        """Layer 0's raw output (B, 128, m, ns) exactly as _FusedMLPChain.forward forms it in eval mode."""
-        from pointnet2 import _mlp_ext as K
-        w0 = self._weights()[0]
-        if pre is not None and isinstance(pre[0], str):
-            from pointnet2 import _ext
-            _, q_idx, q_weight, rel, shape = pre
-            z = K.gemm_forward(w0[:, 3:].contiguous(), x)
-            return _ext.three_interpolate_affine(z, q_idx, q_weight, w0[:, :3].contiguous(), rel).view(shape)
-        if pre is not None:
-            idx, _, npts = pre
-            return K.pregather_forward(K.gemm_forward(w0, x), idx, npts)
-        return K.gemm_forward(w0, x) if x.dim() == 4 else None
-
     def run(self, x, pre):
         """The pooled output, or None where the one-pass kernel does not apply (the caller then runs
         the plain path)."""
@@ -718,19 +658,13 @@ class EvalPlan(object):
                 return None
             self.hits += 1
             return K.eval_lin4_pool(x, self.img, self.coeffs[1], self.coeffs[2])
-        if pre is not None and isinstance(pre[0], str):
-            b, _, m, ns = pre[4]
-        elif pre is not None:
-            b, m, ns = pre[0].shape
-        elif x.dim() == 4:
-            b, _, m, ns = x.shape
-        else:
+        if pre is None and x.dim() != 4:
             return None
+        b, m, ns = pre.extent if pre is not None else (x.shape[0], x.shape[2], x.shape[3])
         if not K.eval_stored_supported(b, c1, c2, c3, m, ns):
             return None
-        y0 = self._layer0(x, pre)
-        if y0 is None:
-            return None
+        w0 = self._weights()[0]  # layer 0's raw output as the plain path forms it
+        y0 = pre.forward(w0, x) if pre is not None else K.gemm_forward(w0, x)
         self.hits += 1
         return K.eval_stored_pool(y0.contiguous(), self.coeffs[0], self.img, self.coeffs[1], self.coeffs[2])
 

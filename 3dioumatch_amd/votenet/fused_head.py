@@ -71,33 +71,15 @@ class _HeadChain(Function):
         w1m, w2m, w3m = (w.reshape(w.shape[0], -1) for w in (w1, w2, w3))
         db3 = dy3.sum(dim=(0, 2)) if ctx.has_bias[2] else None
 
-        def both(wm, src, src_coeff, need_dx=True, **grad):
-            """(dw, d src) of one layer: one launch for the two GEMMs where the layer is small"""
-            pair = K.gemm_backward_small(wm, src, src_coeff, need_dx=need_dx, **grad)
-            if pair is not None:
-                return pair[1], pair[0]
-            dwm = K.gemm_wgrad(wm.shape[0], wm.shape[1], src, src_coeff, **grad)
-            return dwm, (K.gemm_dgrad(wm, **grad) if need_dx else None)
-
-        def through_bn(wm, y, dz, gamma, scale, shift, mean, invstd):
-            """BatchNorm + ReLU backward of (y, dz) as the gradient operand of the layer's GEMMs:
-            (dgamma, dbeta, coef, operand keywords) -- dy written once where the pair launch would
-            otherwise re-form it in every tile (_mlp_ext.small_backward_prefers_dy), else on the fly"""
-            if K.small_backward_prefers_dy(wm, y):
-                dy, dg, dbe = K.bn_relu_backward(y, dz, gamma, scale, shift, mean, invstd, training,
-                                                 ctx.tickets)
-                return dg, dbe, None, dict(dy=dy)
-            dg, dbe, coef = K.bn_relu_backward_stats(y, dz, gamma, scale, shift, mean, invstd, training,
-                                                     ctx.tickets)
-            return dg, dbe, coef, dict(fly=(y, dz, scale, shift, mean, invstd, coef))
-
-        dw3, dz2 = both(w3m, y2, (scale2, shift2), dy=dy3)
+        dw3, dz2 = K.both(w3m, y2, (scale2, shift2), dy=dy3)
         dw3 = dw3.view_as(w3)
-        dg2, dbe2, coef2, grad2 = through_bn(w2m, y2, dz2, g2, scale2, shift2, mean2, invstd2)
-        dw2, dz1 = both(w2m, y1, (scale1, shift1), **grad2)
+        dg2, dbe2, coef2, grad2 = K.through_bn(w2m, y2, dz2, g2, scale2, shift2, mean2, invstd2, training,
+                                               ctx.tickets)
+        dw2, dz1 = K.both(w2m, y1, (scale1, shift1), **grad2)
         dw2 = dw2.view_as(w2)
-        dg1, dbe1, coef1, grad1 = through_bn(w1m, y1, dz1, g1, scale1, shift1, mean1, invstd1)
-        dw1, dx = both(w1m, x, None, need_dx=ctx.needs_input_grad[0], **grad1)
+        dg1, dbe1, coef1, grad1 = K.through_bn(w1m, y1, dz1, g1, scale1, shift1, mean1, invstd1, training,
+                                               ctx.tickets)
+        dw1, dx = K.both(w1m, x, None, need_dx=ctx.needs_input_grad[0], **grad1)
         dw1 = dw1.view_as(w1)
         dx = dx.view_as(x) if dx is not None else None
 

@@ -877,6 +877,9 @@ def test_pooled_backward_from_the_gram_matrix(b, m, ns, kin, mout, monkeypatch):
     dgamma_g, dbeta_g, coef_g = K.bn_relu_pool_backward_stats(None, dpooled, argmax, ymax, g3, sc3, sh3,
                                                               mean3, invstd3, True, ns=ns)
     assert torch.equal(coef_g, coef3) and torch.equal(dgamma_g, dgamma)
+    # the size threshold is the forward's decision alone: restored before the backward (most of these
+    # shapes are below it), the backward must still run
+    monkeypatch.delenv("MLP_POOL_GRAM256_MIN_CHUNKS")
     dx, dw, below = K.pool_gram_backward(w3, y2, c2, g2, coef3, (mean3, invstd3, sc3, sh3), dpooled, argmax,
                                          ymax, ns, True)
     rel = lambda a_, b_: float((a_ - b_).norm() / (b_.norm() + 1e-20))  # noqa: E731
