@@ -17,21 +17,15 @@
 //    scan runs on the device in a single wavefront, so nms needs no device->host mask copy.
 #include "common.h"
 #include "box_geom.h"
+#include "iou3d_pair.h"
 #include <mutex>
 
 namespace {
 
 using boxgeom::BoxPre;
 
-constexpr int kPolySlots = boxgeom::kMaxPoly * 3;  // x, y, angle per vertex
-
-// polygon store in LDS: element (slot s, lane t) at base[s*256 + t]
-struct LdsPoly {
-  float *base;
-  __device__ __forceinline__ float &x(int i) { return base[(i * 3 + 0) * 256]; }
-  __device__ __forceinline__ float &y(int i) { return base[(i * 3 + 1) * 256]; }
-  __device__ __forceinline__ float &a(int i) { return base[(i * 3 + 2) * 256]; }
-};
+using iou3d_pair::kPolySlots;
+using iou3d_pair::LdsPoly;
 
 struct HostPoly {
   float vx[boxgeom::kMaxPoly], vy[boxgeom::kMaxPoly], va[boxgeom::kMaxPoly];
@@ -51,19 +45,7 @@ __device__ __forceinline__ float pair_value(const float *a, const float *b, cons
     const float ov = boxgeom::overlap_area(A, B, st);
     return ov / fmaxf(sa + sb - ov, 1e-8f);
   }
-  // boxes_iou3d_gpu epilogue, iou3d_nms_utils.py:60-79
-  const float a_max = a[2] + a[5] / 2, a_min = a[2] - a[5] / 2;
-  const float b_max = b[2] + b[5] / 2, b_min = b[2] - b[5] / 2;
-  const float max_of_min = a_min > b_min ? a_min : b_min;
-  const float min_of_max = a_max < b_max ? a_max : b_max;
-  float h = min_of_max - max_of_min;
-  if (h < 0.f) h = 0.f;
-  const float ov_bev = h > 0.f ? boxgeom::overlap_area(A, B, st) : 0.f;
-  const float ov3d = ov_bev * h;
-  const float vol_a = a[3] * a[4] * a[5], vol_b = b[3] * b[4] * b[5];
-  float den = vol_a + vol_b - ov3d;
-  if (den < 1e-6f) den = 1e-6f;
-  return ov3d / den;
+  return iou3d_pair::iou3d(a, b, A, B, st);  // boxes_iou3d_gpu epilogue, iou3d_nms_utils.py:60-79
 }
 
 // ans[i,j] for a 16x16 tile; threadIdx.x = 16*row + col

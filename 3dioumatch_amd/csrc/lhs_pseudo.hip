@@ -20,53 +20,30 @@
 // mask); discrete outputs can differ from it only where two keys or a threshold are one ulp apart.
 #include "common.h"
 #include "../../include/lhs_hip.h"
+#include "pseudo_rank.h"
 
 namespace {
 
 constexpr int kSlots = 64;      // MAX_NUM_OBJ
 constexpr int kMaxK = 1024;
 
-__device__ __forceinline__ int first_max(const float *row, int n) {
-  int best = 0;
-  float m = row[0];
-  for (int j = 1; j < n; ++j)
-    if (row[j] > m) { m = row[j]; best = j; }
-  return best;
-}
+using pseudo_rank::first_max;
 
 __global__ void __launch_bounds__(256) pseudo_select_kernel(LhsPseudoArgs a) {
   __shared__ float key[kMaxK];
   const int s = blockIdx.x, tid = threadIdx.x;
   // pass 1: the key of every proposal (kept in LDS for the ranking)
   for (int k = tid; k < a.K; k += 256) {
-    const long long sk = (long long)s * a.K + k;
-    const float s0 = a.objectness[sk * 2], s1 = a.objectness[sk * 2 + 1];
-    const float m = s0 > s1 ? s0 : s1;
-    const float e0 = expf(s0 - m), e1 = expf(s1 - m);
-    const float pos = e1 / (e0 + e1);
-    const float *sem = a.sem_cls + sk * a.NC;
-    const int cls = first_max(sem, a.NC);
-    float sum = 0.0f;
-    for (int j = 0; j < a.NC; ++j) sum += expf(sem[j] - sem[cls]);
-    const float max_cls = 1.0f / sum;
-    const float x = a.iou[sk * a.NI + (a.NI > 1 ? cls : 0)];
-    const float iou = 1.0f / (1.0f + expf(-x));
-    const bool ok = max_cls > a.cls_threshold && pos > a.obj_threshold && iou > a.iou_threshold;
-    // (a NaN / Inf logit makes the key NaN: every comparison of the ranking below is then false,
-    //  several proposals take rank 0 and other slots are never written -- the tensor path's
-    //  argsort always yields a permutation.  Such a proposal is not a pseudo label: key 0.)
-    const float v = pos * max_cls;
-    key[k] = (ok && isfinite(v)) ? v : 0.0f;
+    int cls;
+    float iou;
+    key[k] = pseudo_rank::key(a.objectness, a.sem_cls, a.iou, a.NC, a.NI, (long long)s * a.K + k,
+                              a.obj_threshold, a.cls_threshold, a.iou_threshold, &cls, &iou);
   }
   __syncthreads();
   // pass 2: rank, and the slots
   for (int k = tid; k < a.K; k += 256) {
     const float mine = key[k];
-    int rank = 0;
-    for (int j = 0; j < a.K; ++j) {
-      const float o = key[j];
-      rank += (o > mine || (o == mine && j < k)) ? 1 : 0;
-    }
+    const int rank = pseudo_rank::rank(key, a.K, k);
     if (rank >= kSlots) continue;
     const long long sk = (long long)s * a.K + k, slot = (long long)s * kSlots + rank;
     // (recomputed: cheaper than keeping six values per proposal in LDS)

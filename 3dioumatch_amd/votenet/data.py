@@ -65,13 +65,24 @@ def make_batch(batch_size, num_points, config, seed=0, num_objects=12, device="c
     }
 
 
-def make_semi_batch(labeled, unlabeled, num_points, config, seed=0, num_objects=12, device="cpu"):
+BOX_LABEL_KEYS = ('center_label', 'heading_class_label', 'heading_residual_label', 'size_class_label',
+                  'size_residual_label', 'sem_cls_label', 'box_label_mask')
+
+
+def make_semi_batch(labeled, unlabeled, num_points, config, seed=0, num_objects=12, device="cpu",
+                    unlabeled_labels=False):
     """A stage-2 batch as train.py:321-325 collates it: `labeled` + `unlabeled` scenes.
     point_clouds / ema_point_clouds / the augmentation keys / supervised_mask / scan_idx have
     batch labeled+unlabeled (labeled first), the label tensors batch `labeled`.  The student sees
     the flipped / rotated / scaled cloud (and, for labeled scenes, labels in that frame), the EMA
     teacher an independent, un-augmented subsample of the same scene
-    (scannet_ssl_dataset.py:90-128,177)."""
+    (scannet_ssl_dataset.py:90-128,177).
+
+    unlabeled_labels=True: the seven box-label keys (BOX_LABEL_KEYS) cover every scene, the
+    unlabeled rows after the labeled ones and in the teacher's (un-augmented) frame -- what
+    ScannetSSLUnlabeledDataset(load_labels=True) delivers for view_stats (scannet_ssl_dataset.py:
+    272-279).  The vote labels stay labeled-only; every other tensor and every random draw is the
+    default's."""
     total = labeled + unlabeled
     base = make_batch(total, num_points, config, seed=seed, num_objects=num_objects)
     g = np.random.default_rng(seed + 7919)
@@ -113,16 +124,18 @@ def make_semi_batch(labeled, unlabeled, num_points, config, seed=0, num_objects=
             vote[b] = np.tile(moved * base['vote_label_mask'][b].numpy()[:, None], (1, 3))
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
     lab = slice(0, labeled)
+    box = slice(0, total) if unlabeled_labels else lab
     out = {
         'point_clouds': t(student_pc), 'ema_point_clouds': t(ema_pc),
         'flip_x_axis': t(flip_x), 'flip_y_axis': t(flip_y), 'rot_mat': t(rot_mat),
         'rot_angle': t(rot_angle), 'scale': t(scale),
         'supervised_mask': t(np.array([1] * labeled + [0] * unlabeled, np.int64)),
         'scan_idx': torch.arange(total, dtype=torch.int64, device=device),
-        'center_label': t(center[lab]), 'size_residual_label': t(size_res[lab]),
+        'center_label': t(center[box]), 'size_residual_label': t(size_res[box]),
         'vote_label': t(vote[lab]),
     }
     for k in ('heading_class_label', 'heading_residual_label', 'size_class_label', 'sem_cls_label',
-              'box_label_mask', 'vote_label_mask'):
-        out[k] = base[k][lab].to(device)
+              'box_label_mask'):
+        out[k] = base[k][box].to(device)
+    out['vote_label_mask'] = base['vote_label_mask'][lab].to(device)
     return out

@@ -3,8 +3,19 @@
 Host-side mirror of the reference models/loss_helper_unlabeled.py: trans_center :24-36,
 trans_size :39-51, trans_angle :54-64, compute_objectness_loss :137-196,
 compute_box_and_sem_cls_loss :199-289, get_pseudo_detection_loss :292-361, get_pseudo_labels
-:364-538, get_unlabeled_loss :541-600 (the `view_stats` branches, which peek at ground truth for
-logging only, are not mirrored) -- same end_points keys, thresholds and loss weights.
+:364-538, get_unlabeled_loss :541-600 -- same end_points keys, thresholds and loss weights.
+
+`view_stats` (config_dict; run_train.sh passes --view_stats) mirrors the reference's logging branches
+(get_pseudo_labels :392-414, :525-553; compute_objectness_gt :82-134 with :354-359): the teacher's
+pseudo labels against the ground truth of the unlabeled scenes -- twelve scalars and the (S,K) IoU
+labels in end_points, for logging only.  The label tensors then cover ALL scenes, labeled rows first
+and the unlabeled ones in the teacher's (un-augmented) frame (make_semi_batch(unlabeled_labels=True),
+ScannetSSLUnlabeledDataset(load_labels=True)).  Two things of the reference are deliberately not
+copied: it transforms the batch's center_label / size_residual_label rows of the unlabeled scenes IN
+PLACE (here nothing writes into the caller's label tensors), and it overwrites end_points['pred_bbox']
+with the teacher's boxes (here it keeps the labeled loss' value).  The losses and pseudo labels are the
+same with the flag on or off.  On the GPU's fused path the numbers come from one more pair of launches
+(pseudo_nms.pseudo_label_stats_gpu); the tensor formulation below is its oracle.
 
 What differs is WHERE it runs: the reference's pseudo-label filter leaves the device (per-scene
 numpy loops over 64 boxes for get_3d_box + lhs_3d_faster_samecls, boolean-mask assignments that
@@ -19,8 +30,10 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .losses import (FAR_THRESHOLD, NEAR_THRESHOLD, _masked_mean, _objectness_weights, huber_loss,
-                     nn_distance)
+from .losses import (FAR_THRESHOLD, NEAR_THRESHOLD, _masked_mean, _objectness_weights, compute_iou_labels,
+                     huber_loss, nn_distance)
+
+from .data import BOX_LABEL_KEYS as GT_KEYS  # what view_stats reads for the unlabeled scenes too
 
 MAX_NUM_OBJ = 64
 
@@ -63,6 +76,8 @@ def get_pseudo_labels(end_points, ema_end_points, labeled_num, pred_center, pred
                       pred_size_scores, pred_size_residuals, pred_vote_xyz, config_dict):
     """Teacher predictions of the unlabeled scenes -> at most 64 pseudo boxes per scene."""
     config = config_dict['dataset_config']
+    raw = (pred_vote_xyz, pred_center, pred_sem_cls, pred_objectness, pred_heading_scores,
+           pred_heading_residuals, pred_size_scores, pred_size_residuals)  # (view_stats decodes them)
     pred_objectness = torch.softmax(pred_objectness, dim=2)
     pos_obj, neg_obj = pred_objectness[:, :, 1], pred_objectness[:, :, 0]
     objectness_mask = pos_obj > config_dict['obj_threshold']
@@ -113,6 +128,10 @@ def get_pseudo_labels(end_points, ema_end_points, labeled_num, pred_center, pred
                         config_dict['use_old_type_nms'])
         final_mask_sorted = final_mask_sorted & keep
 
+    if config_dict.get('view_stats'):
+        end_points.update(_teacher_view_stats(end_points, labeled_num, *raw, iou_pred, argmax_cls, inds,
+                                              final_mask_sorted, config_dict))
+
     label_mask = final_mask_sorted.long()
     gone = torch.full_like(center_label, -1000)
     center_label = torch.where(final_mask_sorted.unsqueeze(-1), center_label, gone)
@@ -120,6 +139,85 @@ def get_pseudo_labels(end_points, ema_end_points, labeled_num, pred_center, pred
                                      torch.gather(pred_vote_xyz, 1, inds3), gone)
     return (label_mask, center_label, sem_cls_label, heading_label, heading_residual_label,
             size_label, size_residual_label, false_center_label, iou_label)
+
+
+def _unlabeled_ground_truth(end_points, labeled_num, unlabeled):
+    """The box labels of every row, checked: view_stats needs those of the unlabeled scenes too."""
+    rows = labeled_num + unlabeled
+    for key in GT_KEYS:
+        t = end_points.get(key)
+        if t is None or t.shape[0] != rows:
+            raise ValueError(
+                "view_stats compares the pseudo labels with the ground truth of the unlabeled scenes: "
+                "'%s' must have %d rows (%d labeled + %d unlabeled, e.g. make_semi_batch(..., "
+                "unlabeled_labels=True)), got %s" % (key, rows, labeled_num, unlabeled,
+                                                     None if t is None else tuple(t.shape)))
+    return {key: end_points[key] for key in GT_KEYS}
+
+
+def _teacher_view_stats(end_points, labeled_num, pred_vote_xyz, pred_center, pred_sem_cls,
+                        pred_objectness, pred_heading_scores, pred_heading_residuals, pred_size_scores,
+                        pred_size_residuals, iou_pred, argmax_cls, inds, final_mask_sorted, config_dict):
+    """The teacher-side view_stats of get_pseudo_labels (:392-414, :525-553), in the teacher's frame
+    against the untransformed GT of the unlabeled scenes.  compute_iou_labels gets a copy of the label
+    dict, so its 'pred_bbox' never reaches end_points."""
+    gt = _unlabeled_ground_truth(end_points, labeled_num, pred_center.shape[0])
+    tail = slice(labeled_num, None)
+    args = [t.detach() for t in (pred_vote_xyz, pred_center, pred_sem_cls, pred_objectness,
+                                 pred_heading_scores, pred_heading_residuals, pred_size_scores,
+                                 pred_size_residuals)]
+    iou_labels, objectness_label, object_assignment = compute_iou_labels(dict(gt), tail, *args, config_dict)
+    gt_to_pseudo_iou = compute_iou_labels(dict(gt), tail, *args, config_dict, reverse=True,
+                                          with_objectness=False)
+    out = {'unlabeled_iou_labels': iou_labels,
+           'unlabeled_pred_iou_value': torch.sum(iou_labels) / iou_labels.view(-1).shape[0]}
+    obj_true_num = torch.sum(objectness_label) + 1e-6
+    out['unlabeled_pred_iou_obj_value'] = torch.sum(iou_labels * objectness_label) / obj_true_num
+    iou_acc = torch.abs(iou_pred.detach() - iou_labels)
+    out['unlabeled_iou_acc'] = torch.sum(iou_acc) / iou_acc.view(-1).shape[0]
+    out['unlabeled_iou_obj_acc'] = torch.sum(iou_acc * objectness_label) / obj_true_num
+
+    # the kept pseudo labels (after the NMS) against the GT
+    selected_objectness_label = torch.gather(objectness_label, 1, inds)
+    selected_object_assignment = torch.gather(object_assignment, 1, inds)
+    gt_count = gt['box_label_mask'].sum()   # ALL rows, labeled ones included: the reference's divisor
+    picked_iou_labels = torch.gather(iou_labels, 1, inds)
+    kept = torch.sum(final_mask_sorted) + 1e-6
+    kept_obj = torch.sum(final_mask_sorted * selected_objectness_label) + 1e-6
+    out['final_iou_avg_value'] = torch.sum(picked_iou_labels * final_mask_sorted).float() / kept
+    out['final_iou_avg_obj_value'] = torch.sum(
+        picked_iou_labels * final_mask_sorted * selected_objectness_label).float() / kept_obj
+    selected_cls_pred = torch.gather(argmax_cls, 1, inds)
+    selected_cls_gt = torch.gather(gt['sem_cls_label'][tail], 1, selected_object_assignment)
+    correct_cls = selected_cls_pred == selected_cls_gt
+    out['final_cls_value'] = torch.sum(correct_cls * final_mask_sorted).float() / kept
+    out['final_cls_obj_value'] = torch.sum(
+        correct_cls * final_mask_sorted * selected_objectness_label).float() / kept_obj
+
+    # coverage: the best IoU(GT box, kept pseudo box) of every GT slot
+    n_gt = gt_to_pseudo_iou.shape[1]
+    gt_to_pseudo_iou = torch.gather(gt_to_pseudo_iou, 2, inds.unsqueeze(1).expand(-1, n_gt, -1))
+    gt_to_pseudo_iou = (gt_to_pseudo_iou * final_mask_sorted.unsqueeze(1)).max(dim=2)[0]
+    out['final_coverage_0.25_value'] = torch.sum((gt_to_pseudo_iou > 0.25).float()) / gt_count
+    out['final_coverage_0.5_value'] = torch.sum((gt_to_pseudo_iou > 0.5).float()) / gt_count
+    return out
+
+
+def _student_view_stats(end_points, labeled_num, aug):
+    """compute_objectness_gt (:82-134) and :354-359: the student's objectness arg-max against the
+    GT centres of the unlabeled scenes in the student's frame (trans_center, then -1000 for empty
+    slots).  Reads the label tensors; writes none of them."""
+    tail = slice(labeled_num, None)
+    gt_center = trans_center(end_points['center_label'][tail][:, :, 0:3], *aug)
+    empty = (1 - end_points['box_label_mask'][tail]).unsqueeze(-1).bool()
+    gt_center = torch.where(empty, torch.full_like(gt_center, -1000), gt_center)
+    dist1, _, _, _ = nn_distance(end_points['aggregated_vote_xyz'][tail].detach(), gt_center)
+    dist = torch.sqrt(dist1 + 1e-6)
+    label = (dist < NEAR_THRESHOLD).long()
+    mask = ((dist < NEAR_THRESHOLD) | (dist > FAR_THRESHOLD)).float()
+    pred = torch.argmax(end_points['objectness_scores'][tail].detach(), 2)
+    acc = torch.sum((pred == label).float() * mask) / (torch.sum(mask) + 1e-6)
+    return {'true_unlabeled_obj_acc': acc, 'unlabeled_obj_acc': acc}
 
 
 def compute_objectness_loss(end_points, labeled_num):
@@ -217,12 +315,12 @@ def get_pseudo_detection_loss(end_points, labeled_num, config):
     return loss, end_points
 
 
-def default_config_dict(config, dataset='scannet', unlabeled_batch_size=8):
-    """The filter settings of train.py:263-275."""
+def default_config_dict(config, dataset='scannet', unlabeled_batch_size=8, view_stats=False):
+    """The filter settings of train.py:263-275 (`view_stats`: run_train.sh's --view_stats)."""
     return {'dataset_config': config, 'unlabeled_batch_size': unlabeled_batch_size,
             'dataset': dataset, 'nms_iou': 0.25, 'use_old_type_nms': False, 'obj_threshold': 0.9,
             'cls_threshold': 0.9, 'use_lhs': True, 'iou_threshold': 0.25, 'samecls_match': False,
-            'view_stats': False}
+            'view_stats': bool(view_stats)}
 
 
 def get_unlabeled_loss(end_points, ema_end_points, config, config_dict, labels_only=False):
@@ -234,6 +332,9 @@ def get_unlabeled_loss(end_points, ema_end_points, config, config_dict, labels_o
         labeled_num = int(torch.count_nonzero(end_points['supervised_mask']))
     tail = slice(labeled_num, None)
     aug = [end_points[k][tail] for k in ('flip_x_axis', 'flip_y_axis', 'rot_mat', 'scale')]
+    view_stats = bool(config_dict.get('view_stats'))
+    if view_stats:  # (fails before anything runs if the unlabeled scenes' labels are missing)
+        gt = _unlabeled_ground_truth(end_points, labeled_num, ema_end_points['center'].shape[0] - labeled_num)
     fused = None
     if ema_end_points['center'].is_cuda and os.environ.get("VOTENET_FUSED_PSEUDO_LABELS", "1") != "0":
         from . import pseudo_nms
@@ -262,6 +363,12 @@ def get_unlabeled_loss(end_points, ema_end_points, config, config_dict, labels_o
                                                                        'size_label'))
         heading_residual_label, size_residual_label, iou_label = (
             fused[k] for k in ('heading_residual_label', 'size_residual_label', 'iou_label'))
+        if view_stats:  # two more launches: every view_stats number (pseudo_nms.pseudo_label_stats_gpu)
+            end_points.update(pseudo_nms.pseudo_label_stats_gpu(
+                *teacher[:7], ema_end_points['center'][tail], teacher[7], config.mean_size(aug[3].device),
+                label_mask, gt, labeled_num, end_points['objectness_scores'][tail],
+                end_points['aggregated_vote_xyz'][tail], *aug, config_dict['obj_threshold'],
+                config_dict['cls_threshold'], config_dict['iou_threshold']))
     else:
         (label_mask, center_label, sem_cls_label, heading_label, heading_residual_label, size_label,
          size_residual_label, false_center_label, iou_label) = get_pseudo_labels(
@@ -273,6 +380,8 @@ def get_unlabeled_loss(end_points, ema_end_points, config, config_dict, labels_o
         center_label = trans_center(center_label, *aug)
         false_center_label = trans_center(false_center_label, *aug)
         size_residual_label = trans_size(size_label, size_residual_label, aug[3], config)
+        if view_stats:  # (the teacher's half came with the pseudo labels)
+            end_points.update(_student_view_stats(end_points, labeled_num, aug))
     if config_dict['dataset'] == 'sunrgbd':
         heading_label, heading_residual_label = trans_angle(
             heading_label, heading_residual_label, aug[0], aug[1], end_points['rot_angle'][tail],

@@ -156,3 +156,80 @@ def pseudo_labels_gpu(objectness, sem_cls, iou_scores, heading_scores, heading_r
             a.picked = picked.data_ptr()
         _L.check(_lib.lhs_pseudo_finish(ctypes.byref(a), stream), "lhs_pseudo_finish")
     return out
+
+
+class LhsStatsArgs(ctypes.Structure):  # field order == include/lhs_hip.h
+    _fields_ = ([(n, _c_int) for n in ("S", "K", "NC", "NI", "NH", "NS", "labeled", "rows")] +
+                [(n, _c_float) for n in ("obj_threshold", "cls_threshold", "iou_threshold")] +
+                [(n, _vp) for n in ("objectness", "sem_cls", "iou", "heading_scores", "heading_residuals",
+                                    "size_scores", "size_residuals", "center", "vote_xyz", "mean_size",
+                                    "label_mask", "gt_center", "gt_heading_class", "gt_heading_residual",
+                                    "gt_size_class", "gt_size_residual", "gt_sem_cls", "gt_box_mask",
+                                    "student_objectness", "student_vote_xyz", "flip_x", "flip_y", "rot_mat",
+                                    "scale", "iou_labels", "stats", "workspace")])
+
+
+# order of the kernel's `stats` output (include/lhs_hip.h LHS_STAT_*)
+STAT_KEYS = ("unlabeled_pred_iou_value", "unlabeled_pred_iou_obj_value", "unlabeled_iou_acc",
+             "unlabeled_iou_obj_acc", "final_iou_avg_value", "final_iou_avg_obj_value", "final_cls_value",
+             "final_cls_obj_value", "final_coverage_0.25_value", "final_coverage_0.5_value",
+             "true_unlabeled_obj_acc", "unlabeled_obj_acc")
+
+
+def pseudo_label_stats_gpu(objectness, sem_cls, iou_scores, heading_scores, heading_residuals, size_scores,
+                           size_residuals, center, vote_xyz, mean_size, label_mask, gt, labeled,
+                           student_objectness, student_vote_xyz, flip_x, flip_y, rot_mat, scale,
+                           obj_threshold, cls_threshold, iou_threshold, assignment=False):
+    """The view_stats numbers of get_pseudo_labels / compute_objectness_gt in two launches
+    (include/lhs_hip.h lhs_pseudo_stats), to run after pseudo_labels_gpu: teacher outputs and
+    augmentation as pseudo_labels_gpu takes them, `label_mask` (S,64) its output, `gt` the seven
+    box-label tensors (data.BOX_LABEL_KEYS) of ALL rows -- `labeled` rows first, then the S unlabeled scenes in the
+    teacher's frame -- and the student's objectness scores / aggregated votes of the unlabeled scenes.
+    Returns {'unlabeled_iou_labels': (S,K) f32, one 0-dim f32 tensor per STAT_KEYS entry} (with
+    `assignment`, also 'unlabeled_iou_assignment': the (S,K) first GT index of each IoU label);
+    nothing leaves the device and no input is written."""
+    dev = center.device
+    s, k = center.shape[:2]
+    keep = []
+
+    def inp(t, dt, shape=None):
+        if t.dtype != dt or t.device != dev:
+            raise RuntimeError("pseudo_label_stats_gpu: expected %s tensors on %s" % (dt, dev))
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise RuntimeError("pseudo_label_stats_gpu: shape %s, expected %s" % (tuple(t.shape), shape))
+        t = t.detach().contiguous()
+        keep.append(t)
+        return t.data_ptr()
+    rows = labeled + s
+    a = LhsStatsArgs()
+    a.S, a.K, a.labeled, a.rows = s, k, labeled, rows
+    a.NC, a.NI, a.NH, a.NS = sem_cls.shape[2], iou_scores.shape[2], heading_scores.shape[2], size_scores.shape[2]
+    a.obj_threshold, a.cls_threshold, a.iou_threshold = float(obj_threshold), float(cls_threshold), float(iou_threshold)
+    f32, i64 = torch.float32, torch.int64
+    for name, t, shape in (("objectness", objectness, (s, k, 2)), ("sem_cls", sem_cls, None), ("iou", iou_scores, None),
+                           ("heading_scores", heading_scores, None), ("heading_residuals", heading_residuals, None),
+                           ("size_scores", size_scores, None), ("size_residuals", size_residuals, None),
+                           ("center", center, (s, k, 3)), ("vote_xyz", vote_xyz, (s, k, 3)),
+                           ("mean_size", mean_size, (a.NS, 3)), ("student_objectness", student_objectness, (s, k, 2)),
+                           ("student_vote_xyz", student_vote_xyz, (s, k, 3)), ("rot_mat", rot_mat, (s, 3, 3)),
+                           ("scale", scale, (s, 1, 3))):
+        setattr(a, name, inp(t, f32, shape))
+    a.flip_x, a.flip_y = inp(flip_x, i64, (s,)), inp(flip_y, i64, (s,))
+    a.label_mask = inp(label_mask, i64, (s, 64))
+    for name, key, dt, tail in (("gt_center", "center_label", f32, (3,)), ("gt_heading_class", "heading_class_label", i64, ()),
+                                ("gt_heading_residual", "heading_residual_label", f32, ()),
+                                ("gt_size_class", "size_class_label", i64, ()),
+                                ("gt_size_residual", "size_residual_label", f32, (3,)),
+                                ("gt_sem_cls", "sem_cls_label", i64, ()), ("gt_box_mask", "box_label_mask", f32, ())):
+        setattr(a, name, inp(gt[key], dt, (rows, 64) + tail))
+    iou_labels = torch.empty((s, k), dtype=f32, device=dev)
+    stats = torch.empty((len(STAT_KEYS),), dtype=f32, device=dev)
+    workspace = torch.empty((int(_lib.lhs_pseudo_stats_workspace_bytes(s, k)),), dtype=torch.uint8, device=dev)
+    a.iou_labels, a.stats, a.workspace = iou_labels.data_ptr(), stats.data_ptr(), workspace.data_ptr()
+    with torch.cuda.device(dev):
+        _L.check(_lib.lhs_pseudo_stats(ctypes.byref(a), _L.current_stream_ptr(dev)), "lhs_pseudo_stats")
+    out = {"unlabeled_iou_labels": iou_labels}
+    out.update({name: stats[i] for i, name in enumerate(STAT_KEYS)})
+    if assignment:  # (the first S*K int32 of the workspace, include/lhs_hip.h)
+        out["unlabeled_iou_assignment"] = workspace[:4 * s * k].view(torch.int32).view(s, k).long()
+    return out

@@ -28,6 +28,7 @@ from pointnet2._mlp_ext import deferred_weight_reductions
 from pointnet2.pytorch_utils import deferred_bn_counters, zero_grads_none
 
 from .detector import VoteNet
+from .data import BOX_LABEL_KEYS
 from .losses import get_labeled_loss
 
 
@@ -703,7 +704,12 @@ class SemiSupervisedStep(SupervisedStep):
     next batch run one step ahead on a side stream (G0), forward/backward of both networks and all
     losses replay as one HIP graph (G1), Adam and the EMA update as another (G2).  The EMA weight
     a = min(1 - 1/(step+1), ema_decay) lives in a device scalar that is refreshed before G2.
-    The teacher's parameters are a second flat buffer, so the EMA update is a single lerp."""
+    The teacher's parameters are a second flat buffer, so the EMA update is a single lerp.
+
+    config_dict['view_stats'] (run_train.sh's --view_stats) adds the reference's pseudo-label
+    statistics to the returned end_points (static buffers, like every other key): the batch then
+    carries the box labels of all scenes (make_semi_batch(unlabeled_labels=True)), the losses still
+    read the labeled rows, and G1 gains the two launches of lhs_pseudo_stats -- logging only."""
 
     def __init__(self, cfg, device, world_size=1, num_proposal=256, lr=2e-3, seed=0, graphs=None,
                  unlabeled_loss_weight=2.0, ema_decay=0.999, dataset="scannet", config_dict=None,
@@ -798,20 +804,31 @@ class SemiSupervisedStep(SupervisedStep):
         if labeled is None:
             labeled = self._host_info(batch)["labeled_num"]
         end_points["labeled_num"] = labeled
+        # A batch for view_stats carries the box labels of the unlabeled scenes too
+        # (make_semi_batch(unlabeled_labels=True)): the losses read the labeled rows -- views, the
+        # tensors they read without them -- and only get_unlabeled_loss's statistics see all rows.
+        all_rows = {k: end_points[k] for k in BOX_LABEL_KEYS
+                    if torch.is_tensor(end_points.get(k)) and end_points[k].shape[0] > labeled}
+        labeled_rows = {k: v[:labeled] for k, v in all_rows.items()}
+        end_points.update(labeled_rows)
+
+        def unlabeled_loss(**kw):
+            end_points.update(all_rows)
+            out = get_unlabeled_loss(end_points, ema_end_points, self.cfg, self.config_dict, **kw)
+            out[1].update(labeled_rows)
+            return out
         from . import fused_loss
         if fused_loss.semi_loss_supported(end_points, labeled):
             # both losses as ONE autograd node over one gradient buffer per head output
             # (fused_loss._FusedSemiLoss); the pseudo labels first, without their loss
-            _, end_points = get_unlabeled_loss(end_points, ema_end_points, self.cfg, self.config_dict,
-                                               labels_only=True)
+            _, end_points = unlabeled_loss(labels_only=True)
             loss, end_points = fused_loss.get_semi_loss_fused(end_points, self.cfg, labeled,
                                                               self.unlabeled_loss_weight)
         else:
             detection_loss, end_points = get_labeled_loss(end_points, self.cfg,
                                                           {"dataset_config": self.cfg})
-            unlabeled_loss, end_points = get_unlabeled_loss(end_points, ema_end_points, self.cfg,
-                                                            self.config_dict)
-            loss = detection_loss + unlabeled_loss * self.unlabeled_loss_weight
+            unlabeled, end_points = unlabeled_loss()
+            loss = detection_loss + unlabeled * self.unlabeled_loss_weight
             end_points["loss"] = loss
         from pointnet2 import _mlp_ext as K
         # (the student's images were rebuilt at the head of its forward pass)

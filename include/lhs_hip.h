@@ -2,6 +2,7 @@
  * section 8(f) rank 1).  Plain pointers to DEVICE memory, explicit stream, returns hipError_t. */
 #ifndef LHS_HIP_H
 #define LHS_HIP_H
+#include <stddef.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -71,6 +72,60 @@ int lhs_pseudo_select(const LhsPseudoArgs *args, void *stream);
 /* NMS verdict, -1000 placeholders, labels in the student's frame
  * (models/loss_helper_unlabeled.py:489-538 with trans_center :24-36 and trans_size :39-51) */
 int lhs_pseudo_finish(const LhsPseudoArgs *args, void *stream);
+
+/* The `view_stats` logging of the semi-supervised step: the teacher's pseudo labels against the
+ * ground truth of the unlabeled scenes (never against the loss).  Order of `stats`: */
+enum {
+  LHS_STAT_PRED_IOU = 0,        /* unlabeled_pred_iou_value        */
+  LHS_STAT_PRED_IOU_OBJ,        /* unlabeled_pred_iou_obj_value    */
+  LHS_STAT_IOU_ACC,             /* unlabeled_iou_acc               */
+  LHS_STAT_IOU_OBJ_ACC,         /* unlabeled_iou_obj_acc           */
+  LHS_STAT_FINAL_IOU,           /* final_iou_avg_value             */
+  LHS_STAT_FINAL_IOU_OBJ,       /* final_iou_avg_obj_value         */
+  LHS_STAT_FINAL_CLS,           /* final_cls_value                 */
+  LHS_STAT_FINAL_CLS_OBJ,       /* final_cls_obj_value             */
+  LHS_STAT_COVERAGE_25,         /* final_coverage_0.25_value       */
+  LHS_STAT_COVERAGE_50,         /* final_coverage_0.5_value        */
+  LHS_STAT_TRUE_OBJ_ACC,        /* true_unlabeled_obj_acc          */
+  LHS_STAT_OBJ_ACC,             /* unlabeled_obj_acc (the same value) */
+  LHS_STAT_COUNT
+};
+typedef struct LhsStatsArgs {
+  int S, K, NC, NI, NH, NS;            /* as LhsPseudoArgs; 64 GT slots per scene */
+  int labeled;                         /* label rows before the unlabeled scenes' */
+  int rows;                            /* label rows in all: labeled + S */
+  float obj_threshold, cls_threshold, iou_threshold;   /* the filter's (for the slot ranks) */
+  /* teacher outputs of the unlabeled scenes, as LhsPseudoArgs */
+  const float *objectness, *sem_cls, *iou, *heading_scores, *heading_residuals, *size_scores,
+      *size_residuals, *center, *vote_xyz, *mean_size;
+  const long long *label_mask;         /* (S,64) of lhs_pseudo_finish: post-NMS slot mask */
+  /* ground truth of ALL rows (labeled first), un-augmented frame for the unlabeled rows */
+  const float *gt_center;              /* (rows,64,3) */
+  const long long *gt_heading_class;   /* (rows,64)   */
+  const float *gt_heading_residual;    /* (rows,64)   */
+  const long long *gt_size_class;      /* (rows,64)   */
+  const float *gt_size_residual;       /* (rows,64,3) */
+  const long long *gt_sem_cls;         /* (rows,64)   */
+  const float *gt_box_mask;            /* (rows,64)   */
+  /* the student's outputs of the unlabeled scenes and their augmentation */
+  const float *student_objectness;     /* (S,K,2) */
+  const float *student_vote_xyz;       /* (S,K,3) aggregated votes */
+  const long long *flip_x, *flip_y;    /* (S)     */
+  const float *rot_mat;                /* (S,3,3) */
+  const float *scale;                  /* (S,3)   */
+  /* outputs and scratch (lhs_pseudo_stats_workspace_bytes(S, K) bytes, no initialisation; it starts
+   * with the (S,K) int32 first GT index of every IoU label) */
+  float *iou_labels;                   /* (S,K) best same-scene IoU of every teacher proposal */
+  float *stats;                        /* (LHS_STAT_COUNT) */
+  void *workspace;
+} LhsStatsArgs;
+/* get_pseudo_labels with view_stats (models/loss_helper_unlabeled.py:392-414, :525-553; IoU labels
+ * of models/loss_helper_iou.py:52-112, forward and reverse=True) and the ground-truth objectness of
+ * compute_objectness_gt (models/loss_helper_unlabeled.py:82-134, :354-359) in two launches: one
+ * over (scene, 16-proposal group) and (scene, 16-GT group) tiles, one workgroup for the sums. */
+int lhs_pseudo_stats(const LhsStatsArgs *args, void *stream);
+/* bytes of `workspace` for S scenes of K proposals (models/loss_helper_unlabeled.py:392-414) */
+size_t lhs_pseudo_stats_workspace_bytes(int S, int K);
 
 #ifdef __cplusplus
 }
