@@ -180,6 +180,12 @@ _RESTYPE = {"pn2_ball_query_workspace_bytes": _sz, "lhs_pseudo_stats_workspace_b
 
 EXPORTS = tuple(_SIGNATURES)
 
+# the ScanNet batch builder (include/scene_hip.h): the data loader's entry point, bound with the rest
+# but outside EXPORTS, which is the drop-in surface of the reference's kernels
+_LOADER_SIGNATURES = {
+    "scene_batch_build": [_vp, _vp],
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -192,7 +198,7 @@ def _load():
     # first launch -- seen with __graft_entry__.build() followed by smoke() in one interpreter)
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in _SIGNATURES.items():
+    for name, argtypes in list(_SIGNATURES.items()) + list(_LOADER_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError here == ABI mismatch, fail loudly
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, _c_int)

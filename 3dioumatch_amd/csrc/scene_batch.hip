@@ -1,0 +1,318 @@
+// 3dioumatch_amd/csrc/scene_batch.hip -- ScanNet train / eval batches built on the device from the
+// resident scene store (include/scene_hip.h; votenet/scannet_data.py is the host restatement).
+//
+// Three launches per batch, all small grids (they run beside the train step on its side stream):
+//   scene_boxes_kernel    one workgroup per row: the row's draws (flip x / flip y / angle / scale ->
+//                         flip_x_axis, flip_y_axis, rot_angle, rot_mat, scale), its box labels
+//                         (flip, rotate_aligned_boxes, scale in float64 as model_util_scannet.py:
+//                         85-106 does), scan_idx / supervised_mask, and -- for a vote row -- the
+//                         clear of its instance table.
+//   scene_points_kernel   (chunks of 2048 sample slots) x rows x (student, teacher): the sample
+//                         index of each slot (keyed Feistel bijection + cycle walking when the
+//                         scene has >= N points, i.i.d. draws otherwise), the gathered row, the
+//                         student's augmentation (float64, rounded to float32 after each stage as
+//                         the reference's float32 cloud is), and for vote rows the per-instance
+//                         extents of the chunk: order-preserving integer keys min / max'ed in an
+//                         LDS table (7 words per instance), merged into the row's global table
+//                         with one set of integer atomics per instance the chunk touched.
+//   scene_votes_kernel    one lane per (vote row, slot): 0.5 (min + max) - x of its instance, masked
+//                         by the semantic label at the instance's FIRST sampled position
+//                         (scannet_ssl_dataset.py:136-147).  Integer atomics make the result
+//                         independent of arrival order: bit-reproducible.
+#include "common.h"
+#include "../../include/scene_hip.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kPerThread = 8;
+constexpr int kChunk = kBlock * kPerThread;  // sample slots per workgroup of scene_points_kernel
+constexpr int kTableWords = 8;               // minx miny minz maxx maxy maxz first pad
+
+__constant__ int kNyu40ids[18] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39};
+
+__device__ __forceinline__ unsigned mix32(unsigned h) {  // murmur3 finaliser
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
+// key of (seed, counter, row, draw): every random quantity of a batch derives from one of these
+__device__ __forceinline__ unsigned draw_key(unsigned seed, unsigned counter, unsigned row,
+                                             unsigned draw) {
+  unsigned h = mix32(seed * 0x9E3779B9u + 0x85EBCA6Bu);
+  h = mix32(h ^ (counter * 0xC2B2AE35u + 0x27D4EB2Fu));
+  h = mix32(h ^ (row * 0x165667B1u + 0xD3A2646Cu));
+  return mix32(h ^ (draw * 0xFD7046C5u + 0xB55A4F09u));
+}
+
+__device__ __forceinline__ unsigned element(unsigned key, unsigned j) {
+  return mix32(key ^ (j * 0x9E3779B9u + 0x7F4A7C15u));
+}
+
+// 4-round balanced Feistel network on 2h bits: a bijection of [0, 4^h)
+__device__ __forceinline__ unsigned feistel(unsigned x, int h, unsigned key) {
+  const unsigned mask = (1u << h) - 1u;
+  unsigned l = x >> h, r = x & mask;
+  for (unsigned round = 0; round < 4; ++round) {
+    const unsigned f = mix32(r ^ element(key, round)) & mask;
+    const unsigned nl = r;
+    r = l ^ f;
+    l = nl;
+  }
+  return (l << h) | r;
+}
+
+__device__ __forceinline__ int feistel_half_bits(int n) {  // smallest h with 4^h >= n, h >= 1
+  int h = 1;  // n < 2^30 (checked at load)
+  while (h < 15 && (1u << (2 * h)) < (unsigned)n) ++h;
+  return h;
+}
+
+// slot j of a draw of N of n points: distinct for n >= N (slots 0..N-1 of the cycle-walked
+// bijection), i.i.d. with replacement otherwise (pc_util.random_sampling: replace = n < N)
+__device__ __forceinline__ int sample_index(unsigned key, int j, int n, int N, int h) {
+  if (n < N) return (int)(((unsigned long long)element(key, (unsigned)j) * (unsigned)n) >> 32);
+  unsigned x = feistel((unsigned)j, h, key);
+  while (x >= (unsigned)n) x = feistel(x, h, key);
+  return (int)x;
+}
+
+__device__ __forceinline__ double uniform_of(const SceneBatchArgs &a, int row, int k) {
+  if (a.u_in) return a.u_in[row * 4 + k];
+  return (double)draw_key(a.seed, a.counter, (unsigned)row, SB_DRAW_FLIP_X + k) * 0x1p-32;
+}
+
+struct Aug {
+  int fx, fy;
+  double c, s, angle, scale;
+};
+
+__device__ __forceinline__ Aug row_aug(const SceneBatchArgs &a, int row) {
+  Aug g;
+  g.fx = uniform_of(a, row, 0) > 0.5;
+  g.fy = uniform_of(a, row, 1) > 0.5;
+  g.angle = (uniform_of(a, row, 2) * M_PI) / 18.0 - M_PI / 36.0;  // -5 ~ +5 degree
+  g.scale = uniform_of(a, row, 3) * 0.3 + 0.85;
+  g.c = cos(g.angle);
+  g.s = sin(g.angle);
+  return g;
+}
+
+__device__ __forceinline__ unsigned order_key(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float from_order_key(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+__device__ __forceinline__ bool is_nyu40(int id) {
+  bool hit = false;
+#pragma unroll
+  for (int i = 0; i < 18; ++i) hit |= kNyu40ids[i] == id;
+  return hit;
+}
+
+__global__ void __launch_bounds__(kBlock) scene_boxes_kernel(const SceneBatchArgs a) {
+  const int row = blockIdx.x, t = threadIdx.x;
+  const int scene = a.scene[row];
+  const bool train = a.augment != 0;
+  Aug g;
+  if (train) g = row_aug(a, row);
+  if (t == 0) {
+    if (a.supervised_mask) a.supervised_mask[row] = a.supervised[row];
+    if (a.scan_idx_out) a.scan_idx_out[row] = a.scan_idx[row];
+    if (a.flip_x_axis) {
+      a.flip_x_axis[row] = train ? g.fx : 0;
+      a.flip_y_axis[row] = train ? g.fy : 0;
+      a.rot_angle[row] = train ? (float)g.angle : 0.0f;
+      const double c = train ? g.c : 1.0, s = train ? g.s : 0.0;
+      float *m = a.rot_mat + row * 9;
+      m[0] = (float)c; m[1] = (float)-s; m[2] = 0.0f;
+      m[3] = (float)s; m[4] = (float)c;  m[5] = 0.0f;
+      m[6] = 0.0f;     m[7] = 0.0f;      m[8] = 1.0f;
+      const float sc = train ? (float)g.scale : 1.0f;
+      a.scale[row * 3 + 0] = sc;
+      a.scale[row * 3 + 1] = sc;
+      a.scale[row * 3 + 2] = sc;
+    }
+  }
+  if (row < a.vote_rows) {  // the instance table the points kernel fills
+    const int words = a.ninst[scene] * kTableWords;
+    unsigned *tab = a.table + (size_t)row * SB_MAX_INST * kTableWords;
+    for (int i = t; i < words; i += kBlock) {
+      const int w = i % kTableWords;
+      tab[i] = (w < 3 || w == 6) ? 0xFFFFFFFFu : 0u;
+    }
+  }
+  if (row >= a.box_rows || t >= SB_MAX_OBJ) return;
+  const int nb = a.nbox[scene];
+  const double *src = a.boxes + ((size_t)scene * SB_MAX_OBJ + t) * SB_BOX_COLS;
+  double cx = 0.0, cy = 0.0, cz = 0.0, dx = 0.0, dy = 0.0, dz = 0.0;
+  int cls = 0;
+  if (t < nb) {
+    cx = src[0]; cy = src[1]; cz = src[2]; dx = src[3]; dy = src[4]; dz = src[5];
+    cls = (int)src[6];
+  }
+  if (train && row < a.box_aug_rows) {
+    if (g.fx) cx = -1.0 * cx;
+    if (g.fy) cy = -1.0 * cy;
+    // rotate_aligned_boxes: centres by rot_mat, x/y extent = 2 x the largest rotated half-corner
+    const double c = g.c, s = g.s;
+    const double ncx = cx * c + cy * -s + cz * 0.0;
+    const double ncy = cx * s + cy * c + cz * 0.0;
+    const double ncz = cx * 0.0 + cy * 0.0 + cz * 1.0;
+    const double hx = dx / 2.0, hy = dy / 2.0;
+    double mx = -INFINITY, my = -INFINITY;
+    const double sx[4] = {-1.0, 1.0, 1.0, -1.0}, sy[4] = {-1.0, -1.0, 1.0, 1.0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double px = sx[k] * hx, py = sy[k] * hy;
+      mx = fmax(mx, px * c + py * -s + 0.0 * 0.0);
+      my = fmax(my, px * s + py * c + 0.0 * 0.0);
+    }
+    cx = ncx * g.scale; cy = ncy * g.scale; cz = ncz * g.scale;
+    dx = (2.0 * mx) * g.scale; dy = (2.0 * my) * g.scale; dz = dz * g.scale;
+  }
+  const size_t o = (size_t)row * SB_MAX_OBJ + t;
+  a.center_label[o * 3 + 0] = (float)cx;
+  a.center_label[o * 3 + 1] = (float)cy;
+  a.center_label[o * 3 + 2] = (float)cz;
+  a.heading_class_label[o] = 0;
+  a.heading_residual_label[o] = 0.0f;
+  a.size_class_label[o] = t < nb ? cls : 0;
+  a.sem_cls_label[o] = t < nb ? cls : 0;
+  a.box_label_mask[o] = t < nb ? 1.0f : 0.0f;
+  const double *mean = a.mean_size + 3 * (t < nb ? cls : 0);
+  a.size_residual_label[o * 3 + 0] = t < nb ? (float)(dx - mean[0]) : 0.0f;
+  a.size_residual_label[o * 3 + 1] = t < nb ? (float)(dy - mean[1]) : 0.0f;
+  a.size_residual_label[o * 3 + 2] = t < nb ? (float)(dz - mean[2]) : 0.0f;
+}
+
+__global__ void __launch_bounds__(kBlock) scene_points_kernel(const SceneBatchArgs a) {
+  __shared__ unsigned s_tab[7 * SB_MAX_INST];
+  __shared__ Aug s_aug;
+  const int chunk = blockIdx.x, row = blockIdx.y, teacher = blockIdx.z, t = threadIdx.x;
+  const int scene = a.scene[row];
+  const int n = a.count[scene], N = a.N, C = a.C;
+  const bool augment = !teacher && a.augment;
+  const bool votes = !teacher && row < a.vote_rows;
+  const int ninst = votes ? a.ninst[scene] : 0;
+  if (t == 0 && augment) s_aug = row_aug(a, row);
+  for (int i = t; i < 7 * ninst; i += kBlock) s_tab[i] = (i < 3 * ninst || i >= 6 * ninst) ? 0xFFFFFFFFu : 0u;
+  __syncthreads();
+  Aug g{};
+  if (augment) g = s_aug;
+  const float *cloud = a.cloud + a.offset[scene] * C;
+  const int *given = teacher ? a.ema_idx_in : a.idx_in;
+  const unsigned key = draw_key(a.seed, a.counter, (unsigned)row, teacher ? SB_DRAW_EMA : SB_DRAW_STUDENT);
+  const int h = feistel_half_bits(n);
+  float *out = (teacher ? a.ema_point_clouds : a.point_clouds) + (size_t)row * N * C;
+  for (int k = 0; k < kPerThread; ++k) {
+    const int j = chunk * kChunk + k * kBlock + t;
+    if (j >= N) break;
+    const int p = given ? given[(size_t)row * N + j] : sample_index(key, j, n, N, h);
+    const float *src = cloud + (size_t)p * C;
+    float v[7];  // channels 3..6 only ever move as a whole: constant indices, no scratch
+#pragma unroll
+    for (int c = 0; c < 7; ++c) v[c] = c < C ? src[c] : 0.0f;
+    if (augment) {
+      if (g.fx) v[0] = -v[0];
+      if (g.fy) v[1] = -v[1];
+      const double x = v[0], y = v[1], z = v[2];
+      const float rx = (float)(x * g.c + y * -g.s + z * 0.0);
+      const float ry = (float)(x * g.s + y * g.c + z * 0.0);
+      const float rz = (float)(x * 0.0 + y * 0.0 + z * 1.0);
+      v[0] = (float)((double)rx * g.scale);
+      v[1] = (float)((double)ry * g.scale);
+      v[2] = (float)((double)rz * g.scale);
+#pragma unroll
+      for (int c = 3; c < 7; ++c)
+        if (a.has_height && c == C - 1) v[c] = (float)((double)v[c] * g.scale);
+    }
+#pragma unroll
+    for (int c = 0; c < 7; ++c)
+      if (c < C) out[(size_t)j * C + c] = v[c];
+    if (votes) {
+      a.idx_out[(size_t)row * N + j] = p;
+      const int i = a.inst[a.offset[scene] + p];
+      for (int c = 0; c < 3; ++c) {
+        atomicMin(&s_tab[c * ninst + i], order_key(v[c]));
+        atomicMax(&s_tab[(3 + c) * ninst + i], order_key(v[c]));
+      }
+      atomicMin(&s_tab[6 * ninst + i], (unsigned)j);
+    }
+  }
+  if (!votes) return;
+  __syncthreads();
+  unsigned *tab = a.table + (size_t)row * SB_MAX_INST * kTableWords;
+  for (int i = t; i < ninst; i += kBlock) {
+    if (s_tab[6 * ninst + i] == 0xFFFFFFFFu) continue;  // not in this chunk
+    unsigned *e = tab + (size_t)i * kTableWords;
+    for (int c = 0; c < 3; ++c) {
+      atomicMin(&e[c], s_tab[c * ninst + i]);
+      atomicMax(&e[3 + c], s_tab[(3 + c) * ninst + i]);
+    }
+    atomicMin(&e[6], s_tab[6 * ninst + i]);
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) scene_votes_kernel(const SceneBatchArgs a) {
+  const int row = blockIdx.y, j = blockIdx.x * kBlock + threadIdx.x;
+  const int N = a.N, C = a.C;
+  if (j >= N) return;
+  const int scene = a.scene[row];
+  const long long off = a.offset[scene];
+  const int *idx = a.idx_out + (size_t)row * N;
+  const int i = a.inst[off + idx[j]];
+  const unsigned *e = a.table + ((size_t)row * SB_MAX_INST + i) * kTableWords;
+  const bool hit = is_nyu40(a.sem[off + idx[e[6]]]);
+  const float *pt = a.point_clouds + ((size_t)row * N + j) * C;
+  float vote[3];
+  for (int c = 0; c < 3; ++c) {
+    const float centre = 0.5f * (from_order_key(e[c]) + from_order_key(e[3 + c]));
+    vote[c] = hit ? centre - pt[c] : 0.0f;
+  }
+  float *dst = a.vote_label + ((size_t)row * N + j) * 9;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) dst[r * 3 + c] = vote[c];
+  a.vote_label_mask[(size_t)row * N + j] = hit ? 1 : 0;
+}
+
+bool valid(const SceneBatchArgs *a) {
+  if (!a || a->B < 1 || a->B > SB_MAX_B || a->N < 1 || a->C < 3 || a->C > 7) return false;
+  if (a->vote_rows < 0 || a->vote_rows > a->B || a->box_rows < 0 || a->box_rows > a->B) return false;
+  if (a->box_aug_rows < 0 || a->box_aug_rows > a->box_rows) return false;
+  if (!a->cloud || !a->inst || !a->sem || !a->offset || !a->count || !a->ninst || !a->point_clouds)
+    return false;
+  if (a->ema && !a->ema_point_clouds) return false;
+  if (a->vote_rows && (!a->idx_out || !a->table || !a->vote_label || !a->vote_label_mask))
+    return false;
+  if (a->box_rows && (!a->boxes || !a->nbox || !a->mean_size || !a->center_label ||
+                      !a->heading_class_label || !a->heading_residual_label ||
+                      !a->size_class_label || !a->size_residual_label || !a->sem_cls_label ||
+                      !a->box_label_mask))
+    return false;
+  if (a->flip_x_axis && (!a->flip_y_axis || !a->rot_angle || !a->rot_mat || !a->scale)) return false;
+  return true;
+}
+
+}  // namespace
+
+PN2_API int scene_batch_build(const SceneBatchArgs *args, void *stream) {
+  if (!valid(args)) return (int)hipErrorInvalidValue;
+  const hipStream_t s = (hipStream_t)stream;
+  const SceneBatchArgs &a = *args;
+  hipLaunchKernelGGL(scene_boxes_kernel, dim3(a.B), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(scene_points_kernel, dim3(pn2_ceil_div(a.N, kChunk), a.B, a.ema ? 2 : 1),
+                     dim3(kBlock), 0, s, a);
+  if (a.vote_rows > 0)
+    hipLaunchKernelGGL(scene_votes_kernel, dim3(pn2_ceil_div(a.N, kBlock), a.vote_rows),
+                       dim3(kBlock), 0, s, a);
+  return (int)hipGetLastError();
+}

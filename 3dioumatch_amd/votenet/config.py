@@ -16,12 +16,20 @@ class DatasetConfig(object):
     # hard-codes THIS class's class2angle_gpu; a subclass that overrides the decoding must set it False
     fused_heading_decode = True
 
-    def __init__(self, num_class, num_heading_bin, num_size_cluster, seed=0):
+    def __init__(self, num_class, num_heading_bin, num_size_cluster, seed=0, mean_size_arr=None):
         self.num_class = num_class
         self.num_heading_bin = num_heading_bin
         self.num_size_cluster = num_size_cluster
-        g = np.random.default_rng(seed)
-        self.mean_size_arr = g.uniform(0.3, 1.8, (num_size_cluster, 3)).astype(np.float32)
+        if mean_size_arr is None:
+            g = np.random.default_rng(seed)
+            self.mean_size_arr = g.uniform(0.3, 1.8, (num_size_cluster, 3)).astype(np.float32)
+        else:  # the dataset's own (e.g. scannet_means.npz['arr_0'] next to the preprocessed scans)
+            arr = np.asarray(mean_size_arr)
+            if arr.shape != (num_size_cluster, 3):
+                raise ValueError("mean_size_arr has shape %s, expected (%d, 3)" % (arr.shape, num_size_cluster))
+            self.mean_size_arr = arr.astype(np.float32)
+            # the reference's size residuals are float64 (dims - mean_size_arr): the loader uses these
+            self.mean_size_arr_f64 = arr.astype(np.float64)
         self._mean_size_dev = {}
 
     def mean_size(self, device):
@@ -78,8 +86,12 @@ class DatasetConfig(object):
         return self.mean_size(residual.device)[pred_cls, :] + residual
 
 
-def scannet_config():
-    return DatasetConfig(num_class=18, num_heading_bin=1, num_size_cluster=18, seed=18)
+def scannet_config(mean_size_arr=None):
+    """ScanNet's constants.  mean_size_arr: the (18, 3) mean sizes of the dataset (the `arr_0` of the
+    scannet_means.npz beside the preprocessed data, model_util_scannet.py:31); None keeps the
+    synthetic, seeded ones."""
+    return DatasetConfig(num_class=18, num_heading_bin=1, num_size_cluster=18, seed=18,
+                         mean_size_arr=mean_size_arr)
 
 
 def sunrgbd_config():
