@@ -26,7 +26,9 @@ LAYERS = [("sa1_l2", 64, 64, 2048, 64, False), ("sa1_l3", 128, 64, 2048, 64, Tru
           ("sa2_l3", 256, 128, 1024, 32, True), ("sa3_l1", 128, 259, 512, 16, False),
           ("sa3_l2", 128, 128, 512, 16, False), ("sa3_l3", 256, 128, 512, 16, True),
           ("sa4_l1", 128, 259, 256, 16, False), ("sa4_l2", 128, 128, 256, 16, False),
-          ("sa4_l3", 256, 128, 256, 16, True)]
+          ("sa4_l3", 256, 128, 256, 16, True),
+          # the pooled (128,128) layers (gemm_bwd_x6_kernel, OP_POOLDY form): vote aggregation, IoU branch
+          ("vote_l3", 128, 128, 256, 16, True), ("iou_l3", 128, 128, 512, 64, True)]
 only = [a for a in sys.argv[1:] if not a.startswith("--") and not a.endswith(".json")]
 res = {}
 for name, m, k, groups, ns, pooled in LAYERS:
