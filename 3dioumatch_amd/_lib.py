@@ -180,10 +180,12 @@ _RESTYPE = {"pn2_ball_query_workspace_bytes": _sz, "lhs_pseudo_stats_workspace_b
 
 EXPORTS = tuple(_SIGNATURES)
 
-# the ScanNet batch builder (include/scene_hip.h): the data loader's entry point, bound with the rest
-# but outside EXPORTS, which is the drop-in surface of the reference's kernels
+# the batch builders (include/scene_hip.h: ScanNet, include/sunrgbd_hip.h: SUN RGB-D): the data
+# loaders' entry points, bound with the rest but outside EXPORTS, which is the drop-in surface of the
+# reference's kernels
 _LOADER_SIGNATURES = {
     "scene_batch_build": [_vp, _vp],
+    "scene_sunrgbd_batch_build": [_vp, _vp],
 }
 
 

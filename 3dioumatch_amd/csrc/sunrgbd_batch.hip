@@ -1,0 +1,277 @@
+// 3dioumatch_amd/csrc/sunrgbd_batch.hip -- SUN RGB-D train / eval batches built on the device from
+// the resident scene store (include/sunrgbd_hip.h; votenet/sunrgbd_data.py is the host restatement).
+//
+// Two launches per batch, both small grids (they run beside the train step on its side stream):
+//   sun_boxes_kernel    one 64-lane workgroup per row, one lane per box slot: the row's draws
+//                       (flip / angle / scale -> flip_x_axis, flip_y_axis = 0, rot_angle, rot_mat,
+//                       scale), its oriented-box labels in float64 in the reference's operation
+//                       order (sunrgbd_detection_dataset.py:155-226: centre flip / rotate / scale,
+//                       heading pi - theta, theta - rot_angle, angle2class with Python's float
+//                       modulo, size residual of 2 x the half size against the class's mean size),
+//                       masks, scan_idx and supervised_mask.
+//   sun_points_kernel   (chunks of 2048 sample slots) x rows x (student, teacher): the sample index
+//                       of each slot, the gathered cloud row, the unlabeled rows' colour / 256, the
+//                       detection dataset's colour augmentation (per-point draws keyed by the
+//                       SOURCE index, so only sampled points are computed), flip / rotate / scale
+//                       rounded to float32 after each stage as the reference's float32 cloud is,
+//                       and on vote rows the gathered (mask, 3 votes) row carried through the same
+//                       flip, rotation and scale.  rot(p + v) - rot(p) is computed as rot(v): the
+//                       two differ by the float32 rounding of the rotated point only.
+// No atomics, no scratch tables: a slot's outputs depend on its own source row alone.
+#include "common.h"
+#include "scene_common.h"
+#include "../../include/sunrgbd_hip.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kPerThread = 8;
+constexpr int kChunk = kBlock * kPerThread;  // sample slots per workgroup of sun_points_kernel
+
+__device__ __forceinline__ double sun_uniform(const SunBatchArgs &a, int row, int k) {
+  if (a.u_in) return a.u_in[row * 3 + k];
+  return (double)draw_key(a.seed, a.counter, (unsigned)row, SUN_DRAW_FLIP + k) * 0x1p-32;
+}
+
+struct SunAug {
+  int fx;
+  double c, s, angle, scale;
+};
+
+__device__ __forceinline__ SunAug sun_row_aug(const SunBatchArgs &a, int row) {
+  SunAug g;
+  g.fx = sun_uniform(a, row, 0) > 0.5;
+  g.angle = (sun_uniform(a, row, 1) * M_PI) / 3.0 - M_PI / 6.0;  // -30 ~ +30 degree
+  g.scale = sun_uniform(a, row, 2) * 0.3 + 0.85;
+  g.c = cos(g.angle);
+  g.s = sin(g.angle);
+  return g;
+}
+
+// Python's float modulo for a positive divisor: the result takes the divisor's sign
+__device__ __forceinline__ double py_mod(double x, double y) {
+  double m = fmod(x, y);
+  if (m != 0.0) {
+    if (m < 0.0) m += y;
+  } else {
+    m = 0.0;
+  }
+  return m;
+}
+
+__global__ void __launch_bounds__(SUN_MAX_OBJ) sun_boxes_kernel(const SunBatchArgs a) {
+  const int row = blockIdx.x, t = threadIdx.x;
+  const int scene = a.scene[row];
+  const bool train = a.augment != 0;
+  SunAug g;
+  if (train) g = sun_row_aug(a, row);
+  if (t == 0) {
+    if (a.supervised_mask) a.supervised_mask[row] = a.supervised[row];
+    if (a.scan_idx_out) a.scan_idx_out[row] = a.scan_idx[row];
+    if (a.flip_x_axis) {
+      a.flip_x_axis[row] = train ? g.fx : 0;
+      a.flip_y_axis[row] = 0;
+      a.rot_angle[row] = train ? (float)g.angle : 0.0f;
+      const double c = train ? g.c : 1.0, s = train ? g.s : 0.0;
+      float *m = a.rot_mat + row * 9;
+      m[0] = (float)c; m[1] = (float)-s; m[2] = 0.0f;
+      m[3] = (float)s; m[4] = (float)c;  m[5] = 0.0f;
+      m[6] = 0.0f;     m[7] = 0.0f;      m[8] = 1.0f;
+      const float sc = train ? (float)g.scale : 1.0f;
+      a.scale[row * 3 + 0] = sc;
+      a.scale[row * 3 + 1] = sc;
+      a.scale[row * 3 + 2] = sc;
+    }
+  }
+  if (row >= a.box_rows) return;
+  const int nb = a.nbox[scene];
+  const bool live = t < nb;
+  const double *src = a.boxes + ((size_t)scene * SUN_MAX_OBJ + t) * SUN_BOX_COLS;
+  double cx = 0.0, cy = 0.0, cz = 0.0, hx = 0.0, hy = 0.0, hz = 0.0, heading = 0.0;
+  int cls = 0;
+  if (live) {
+    cx = src[0]; cy = src[1]; cz = src[2]; hx = src[3]; hy = src[4]; hz = src[5];
+    heading = src[6];
+    cls = (int)src[7];
+  }
+  if (train && row < a.box_aug_rows) {
+    if (g.fx) {
+      cx = -1.0 * cx;
+      heading = M_PI - heading;
+    }
+    const double c = g.c, s = g.s;
+    const double ncx = cx * c + cy * -s + cz * 0.0;
+    const double ncy = cx * s + cy * c + cz * 0.0;
+    const double ncz = cx * 0.0 + cy * 0.0 + cz * 1.0;
+    heading -= g.angle;
+    cx = ncx * g.scale; cy = ncy * g.scale; cz = ncz * g.scale;
+    hx = hx * g.scale; hy = hy * g.scale; hz = hz * g.scale;
+  }
+  // angle2class (model_util_sunrgbd.py:92-108)
+  const double two_pi = 2.0 * M_PI;
+  const double per = two_pi / (double)a.num_heading_bin;
+  const double shifted = py_mod(py_mod(heading, two_pi) + per / 2.0, two_pi);
+  const int head_cls = (int)(shifted / per);
+  const double head_res = shifted - ((double)head_cls * per + per / 2.0);
+  const size_t o = (size_t)row * SUN_MAX_OBJ + t;
+  a.center_label[o * 3 + 0] = (float)cx;
+  a.center_label[o * 3 + 1] = (float)cy;
+  a.center_label[o * 3 + 2] = (float)cz;
+  a.heading_class_label[o] = live ? head_cls : 0;
+  a.heading_residual_label[o] = live ? (float)head_res : 0.0f;
+  a.size_class_label[o] = live ? cls : 0;
+  a.sem_cls_label[o] = live ? cls : 0;
+  a.box_label_mask[o] = live ? 1.0f : 0.0f;
+  const double *mean = a.mean_size + 3 * (live ? cls : 0);
+  a.size_residual_label[o * 3 + 0] = live ? (float)(hx * 2.0 - mean[0]) : 0.0f;
+  a.size_residual_label[o * 3 + 1] = live ? (float)(hy * 2.0 - mean[1]) : 0.0f;
+  a.size_residual_label[o * 3 + 2] = live ? (float)(hz * 2.0 - mean[2]) : 0.0f;
+}
+
+struct SunColor {
+  double bright[3], shift[3];
+};
+
+__device__ __forceinline__ double sun_color_uniform(const SunBatchArgs &a, int row, int k) {
+  if (a.u_color_in) return a.u_color_in[row * 6 + k];
+  return (double)draw_key(a.seed, a.counter, (unsigned)row, SUN_DRAW_COLOR + k) * 0x1p-32;
+}
+
+__global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a) {
+  __shared__ SunAug s_aug;
+  __shared__ SunColor s_col;
+  const int chunk = blockIdx.x, row = blockIdx.y, teacher = blockIdx.z, t = threadIdx.x;
+  const int scene = a.scene[row];
+  const int n = a.count[scene], N = a.N, C = a.C;
+  const bool augment = !teacher && a.augment;
+  const bool votes = !teacher && row < a.vote_rows;
+  const bool color = augment && a.color_aug && C >= 6;
+  const bool div256 = row >= a.div256_from && C >= 6;
+  if (t == 0 && augment) s_aug = sun_row_aug(a, row);
+  if (t < 3 && color) {
+    s_col.bright[t] = 1.0 + 0.4 * sun_color_uniform(a, row, t) - 0.2;
+    s_col.shift[t] = 0.1 * sun_color_uniform(a, row, 3 + t) - 0.05;
+  }
+  __syncthreads();
+  SunAug g{};
+  if (augment) g = s_aug;
+  SunColor col{};
+  if (color) col = s_col;
+  const long long off = a.offset[scene];
+  const float *cloud = a.cloud + off * C;
+  const float *vrow = a.votes + off * SUN_VOTE_COLS;
+  const int *given = teacher ? a.ema_idx_in : a.idx_in;
+  const unsigned key = draw_key(a.seed, a.counter, (unsigned)row, teacher ? SUN_DRAW_EMA : SUN_DRAW_STUDENT);
+  const unsigned key_jit = draw_key(a.seed, a.counter, (unsigned)row, SUN_DRAW_JITTER);
+  const unsigned key_drop = draw_key(a.seed, a.counter, (unsigned)row, SUN_DRAW_DROP);
+  const double *u_point = a.u_point_in ? a.u_point_in + (size_t)row * 2 * a.u_point_stride : nullptr;
+  const int h = feistel_half_bits(n);
+  float *out = (teacher ? a.ema_point_clouds : a.point_clouds) + (size_t)row * N * C;
+  for (int k = 0; k < kPerThread; ++k) {
+    const int j = chunk * kChunk + k * kBlock + t;
+    if (j >= N) break;
+    const int p = given ? given[(size_t)row * N + j] : sample_index(key, j, n, N, h);
+    const float *src = cloud + (size_t)p * C;
+    float v[7];  // constant indices only: registers, no scratch
+#pragma unroll
+    for (int c = 0; c < 7; ++c) v[c] = c < C ? src[c] : 0.0f;
+    float2 w[5];  // mask x1 | y1 z1 | x2 y2 | z2 x3 | y3 z3 (rows are 8-byte aligned)
+    if (votes) {
+      const float2 *vs = reinterpret_cast<const float2 *>(vrow + (size_t)p * SUN_VOTE_COLS);
+#pragma unroll
+      for (int q = 0; q < 5; ++q) w[q] = vs[q];
+    }
+    if (div256) {
+      v[3] *= 0.00390625f;
+      v[4] *= 0.00390625f;
+      v[5] *= 0.00390625f;
+    }
+    if (augment) {
+      if (g.fx) v[0] = -v[0];
+      const double x = v[0], y = v[1], z = v[2];
+      const float rx = (float)(x * g.c + y * -g.s + z * 0.0);
+      const float ry = (float)(x * g.s + y * g.c + z * 0.0);
+      const float rz = (float)(x * 0.0 + y * 0.0 + z * 1.0);
+      if (color) {
+        const double uj = u_point ? u_point[p] : (double)element(key_jit, (unsigned)p) * 0x1p-32;
+        const double ud = u_point ? u_point[a.u_point_stride + p]
+                                  : (double)element(key_drop, (unsigned)p) * 0x1p-32;
+        const double jitter = 0.05 * uj - 0.025;
+        const double keep = ud > 0.3 ? 1.0 : 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          double rgb = (double)v[3 + c] + 0.5;
+          rgb = rgb * col.bright[c];
+          rgb = rgb + col.shift[c];
+          rgb = rgb + jitter;
+          rgb = fmin(fmax(rgb, 0.0), 1.0);
+          rgb = rgb * keep;
+          v[3 + c] = (float)(rgb - 0.5);
+        }
+      }
+      v[0] = (float)((double)rx * g.scale);
+      v[1] = (float)((double)ry * g.scale);
+      v[2] = (float)((double)rz * g.scale);
+#pragma unroll
+      for (int c = 3; c < 7; ++c)
+        if (a.has_height && c == C - 1) v[c] = (float)((double)v[c] * g.scale);
+    }
+#pragma unroll
+    for (int c = 0; c < 7; ++c)
+      if (c < C) out[(size_t)j * C + c] = v[c];
+    if (votes) {
+      const float vx[3] = {w[0].y, w[2].x, w[3].y};
+      const float vy[3] = {w[1].x, w[2].y, w[4].x};
+      const float vz[3] = {w[1].y, w[3].x, w[4].y};
+      float *dst = a.vote_label + ((size_t)row * N + j) * 9;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        double x = vx[q], y = vy[q], z = vz[q];
+        if (augment) {
+          if (g.fx) x = -1.0 * x;
+          const double rx = x * g.c + y * -g.s + z * 0.0;
+          const double ry = x * g.s + y * g.c + z * 0.0;
+          const double rz = x * 0.0 + y * 0.0 + z * 1.0;
+          x = rx * g.scale;
+          y = ry * g.scale;
+          z = rz * g.scale;
+        }
+        dst[q * 3 + 0] = (float)x;
+        dst[q * 3 + 1] = (float)y;
+        dst[q * 3 + 2] = (float)z;
+      }
+      a.vote_label_mask[(size_t)row * N + j] = (long long)w[0].x;
+    }
+  }
+}
+
+bool valid(const SunBatchArgs *a) {
+  if (!a || a->B < 1 || a->B > SUN_MAX_B || a->N < 1 || a->C < 3 || a->C > 7) return false;
+  if (a->vote_rows < 0 || a->vote_rows > a->B || a->box_rows < 0 || a->box_rows > a->B) return false;
+  if (a->box_aug_rows < 0 || a->box_aug_rows > a->box_rows) return false;
+  if (a->div256_from < 0 || a->num_heading_bin < 1) return false;
+  if (!a->cloud || !a->offset || !a->count || !a->point_clouds) return false;
+  if (a->ema && !a->ema_point_clouds) return false;
+  if (a->color_aug && a->C < 6) return false;
+  if (a->u_point_in && a->u_point_stride < 1) return false;
+  if (a->vote_rows && (!a->votes || !a->vote_label || !a->vote_label_mask)) return false;
+  if (a->box_rows && (!a->boxes || !a->nbox || !a->mean_size || !a->center_label ||
+                      !a->heading_class_label || !a->heading_residual_label ||
+                      !a->size_class_label || !a->size_residual_label || !a->sem_cls_label ||
+                      !a->box_label_mask))
+    return false;
+  if (a->flip_x_axis && (!a->flip_y_axis || !a->rot_angle || !a->rot_mat || !a->scale)) return false;
+  return true;
+}
+
+}  // namespace
+
+PN2_API int scene_sunrgbd_batch_build(const SunBatchArgs *args, void *stream) {
+  if (!valid(args)) return (int)hipErrorInvalidValue;
+  const hipStream_t s = (hipStream_t)stream;
+  const SunBatchArgs &a = *args;
+  hipLaunchKernelGGL(sun_boxes_kernel, dim3(a.B), dim3(SUN_MAX_OBJ), 0, s, a);
+  hipLaunchKernelGGL(sun_points_kernel, dim3(pn2_ceil_div(a.N, kChunk), a.B, a.ema ? 2 : 1),
+                     dim3(kBlock), 0, s, a);
+  return (int)hipGetLastError();
+}

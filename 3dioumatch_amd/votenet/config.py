@@ -94,5 +94,8 @@ def scannet_config(mean_size_arr=None):
                          mean_size_arr=mean_size_arr)
 
 
-def sunrgbd_config():
-    return DatasetConfig(num_class=10, num_heading_bin=12, num_size_cluster=10, seed=10)
+def sunrgbd_config(mean_size_arr=None):
+    """SUN RGB-D's constants.  mean_size_arr: the (10, 3) mean sizes of the dataset's classes in class
+    order (model_util_sunrgbd.py:28-41); None keeps the synthetic, seeded ones."""
+    return DatasetConfig(num_class=10, num_heading_bin=12, num_size_cluster=10, seed=10,
+                         mean_size_arr=mean_size_arr)

@@ -1,0 +1,578 @@
+"""SUN RGB-D train / eval batches built on the GPU from a resident scene store.
+
+The reference's loaders (sunrgbd/sunrgbd_detection_dataset.py:119-246 and
+sunrgbd/sunrgbd_ssl_dataset.py:53-181, :221-312) redo per-scene numpy work in every __getitem__ on
+the WHOLE 50k-point scan before they sample it.  Here the preprocessed scans (`<name>_pc.npz`,
+`<name>_bbox.npy`, `<name>_votes.npz`, the sunrgbd_pc_bbox_votes_50k_v1_{train,val} folders) are
+read ONCE into flat device arrays (`SunRgbdScenes`), and a batch is two kernel launches
+(csrc/sunrgbd_batch.hip, include/sunrgbd_hip.h) on the train step's side stream (scannet_data.feed).
+
+What differs from the ScanNet loader: boxes are oriented (heading class / residual of 12 bins, size
+residuals from 2 x the stored half sizes), the vote labels are INPUT data carried through the
+augmentation, the labeled and the unlabeled dataset normalise colour differently (rgb - 0.5 and
+(rgb - 0.5) / 256: the store keeps the first, the second is applied per row at build time), and the
+detection dataset augments colour per point.  The draw hash, the sampler, epoch_plan, feed and
+eval_batches are scannet_data's.
+
+Keys, dtypes and shapes are those of data.make_batch (pretrain, eval) and data.make_semi_batch
+(semi-supervised) for sunrgbd_config(); semi batches also carry `supervised_mask_host`.
+"""
+import ctypes
+import importlib
+import os
+
+import numpy as np
+import torch
+
+from .scannet_data import (SceneError, _element, _stack, draw_key, epoch_plan, eval_batches,  # noqa: F401
+                           feed, rotz, sample_indices)
+
+MAX_NUM_OBJ = 64   # sunrgbd_detection_dataset.py:40
+MAX_BATCH = 64     # scenes per batch (SUN_MAX_B)
+NUM_CLASS = 10     # model_util_sunrgbd.py:21
+MEAN_COLOR_RGB = np.array([0.5, 0.5, 0.5])  # sunrgbd_detection_dataset.py:41 (colour is in 0~1)
+VOTE_COLS = 10     # mask, three votes
+# draw indices of the hash (sunrgbd_hip.h)
+DRAW_STUDENT, DRAW_EMA, DRAW_FLIP, DRAW_ANGLE, DRAW_SCALE, DRAW_COLOR, DRAW_JITTER, DRAW_DROP = \
+    0, 1, 2, 3, 4, 5, 11, 12
+
+_c_int, _c_uint, _vp = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p
+
+
+# ------------------------------------------------------------------ reading scans and splits
+def read_scene(data_dir, name, use_color=False, use_height=True):
+    """One preprocessed scan -> the per-scene state the batches are built from, computed once in the
+    file's dtype as the reference does and then held in float32: cloud (n, C) = xyz, [rgb - 0.5],
+    [z - floor]; the floor height (np.percentile(z, 0.99)); the vote rows (n, 10) float32; the box
+    table (K, 8) float64 = centre, half sizes, heading, class."""
+    paths = {"pc": os.path.join(data_dir, name + "_pc.npz"), "bbox": os.path.join(data_dir, name + "_bbox.npy"),
+             "votes": os.path.join(data_dir, name + "_votes.npz")}
+    for p in paths.values():
+        if not os.path.exists(p):
+            raise SceneError("scan %s: missing %s" % (name, p))
+    with np.load(paths["pc"]) as f:
+        if "pc" not in f.files:
+            raise SceneError("scan %s: %s has no 'pc'" % (name, paths["pc"]))
+        pc = f["pc"]
+    with np.load(paths["votes"]) as f:
+        if "point_votes" not in f.files:
+            raise SceneError("scan %s: %s has no 'point_votes'" % (name, paths["votes"]))
+        votes = f["point_votes"]
+    bbox = np.load(paths["bbox"])
+    if pc.ndim != 2 or pc.shape[1] < (6 if use_color else 3):
+        raise SceneError("scan %s: pc has shape %s, expected (n, %s)"
+                         % (name, pc.shape, ">= 6" if use_color else ">= 3"))
+    n = pc.shape[0]
+    if n == 0 or n >= 1 << 30:
+        raise SceneError("scan %s: %d points" % (name, n))
+    if votes.ndim != 2 or votes.shape[0] != n or votes.shape[1] != VOTE_COLS:
+        raise SceneError("scan %s: %d points but point_votes has shape %s, expected (%d, %d)"
+                         % (name, n, votes.shape, n, VOTE_COLS))
+    if bbox.size == 0:
+        bbox = np.zeros((0, 8))
+    elif bbox.ndim != 2 or bbox.shape[1] != 8:
+        raise SceneError("scan %s: _bbox.npy has shape %s, expected (boxes, 8)" % (name, bbox.shape))
+    if bbox.shape[0] > MAX_NUM_OBJ:
+        raise SceneError("scan %s: %d boxes, at most MAX_NUM_OBJ = %d" % (name, bbox.shape[0], MAX_NUM_OBJ))
+    for i, label in enumerate(bbox[:, 7]):
+        if not (0 <= label < NUM_CLASS and label == int(label)):
+            raise SceneError("scan %s: box %d has class %g, not one of 0..%d"
+                             % (name, i, float(label), NUM_CLASS - 1))
+    if pc.dtype not in (np.float32, np.float64):
+        pc = pc.astype(np.float64)
+    if use_color:
+        cloud = np.array(pc[:, 0:6])
+        cloud[:, 3:] = cloud[:, 3:] - MEAN_COLOR_RGB
+    else:
+        cloud = np.array(pc[:, 0:3])
+    floor = np.percentile(cloud[:, 2], 0.99)
+    if use_height:
+        cloud = np.concatenate([cloud, np.expand_dims(cloud[:, 2] - floor, 1)], 1)
+    return {"name": name, "cloud": np.ascontiguousarray(cloud, np.float32), "floor": float(floor),
+            "votes": np.ascontiguousarray(votes, np.float32), "boxes": np.array(bbox, np.float64),
+            "dtype": str(pc.dtype)}
+
+
+def available_scans(data_dir):
+    """The scan names of a folder: the first six characters of its file names
+    (sunrgbd_detection_dataset.py:58-59)."""
+    return sorted(set(os.path.basename(f)[0:6] for f in os.listdir(data_dir)))
+
+
+def _read_list(path):
+    with open(path) as f:
+        return [x.strip() for x in f.read().splitlines() if x.strip()]
+
+
+def labeled_split(data_dir, list_path):
+    """The labeled scans of a list file such as sunrgbd_v1_train_0.05.txt
+    (sunrgbd_ssl_dataset.py:37-40); listed scans without files are skipped."""
+    avail = set(available_scans(data_dir))
+    return [s for s in _read_list(list_path) if s in avail]
+
+
+def unlabeled_split(data_dir, list_path):
+    """train minus labeled, or all of train when the two have equal length
+    (sunrgbd_ssl_dataset.py:193-203); sorted."""
+    train = available_scans(data_dir)
+    labeled = _read_list(list_path)
+    names = list(train) if len(train) == len(labeled) else list(set(train) - set(labeled))
+    return sorted(names)
+
+
+def val_split(val_dir):
+    """Every scan of the val folder (sunrgbd_detection_dataset.py:51-59)."""
+    return available_scans(val_dir)
+
+
+# ------------------------------------------------------------------ the resident store
+class SunRgbdScenes(object):
+    """Every scan of `scan_names` read once and packed into flat device arrays with a per-scene
+    offset / count table: the cloud (P, C) float32, the vote rows (P, 10) float32, the box table
+    (S, 64, 8) float64.  At 50k points a scene is 50k x (4 C + 40) bytes = 2.8 MB with the height
+    channel, 4 MB with colour too.  `device=None` keeps the host copy only (the CPU path)."""
+
+    def __init__(self, data_dir, scan_names, device, use_color=False, use_height=True):
+        if not scan_names:
+            raise SceneError("no scans to load from %s" % data_dir)
+        self.scan_names = list(scan_names)
+        self.use_color, self.use_height = use_color, use_height
+        self.scenes = [read_scene(data_dir, s, use_color, use_height) for s in self.scan_names]
+        self.channels = self.scenes[0]["cloud"].shape[1]
+        self.count = np.array([s["cloud"].shape[0] for s in self.scenes], np.int32)
+        self.offset = np.concatenate([[0], np.cumsum(self.count, dtype=np.int64)[:-1]]).astype(np.int64)
+        self.nbox = np.array([s["boxes"].shape[0] for s in self.scenes], np.int32)
+        self.floor = np.array([s["floor"] for s in self.scenes], np.float64)
+        self.boxes = np.zeros((len(self.scenes), MAX_NUM_OBJ, 8))
+        for i, s in enumerate(self.scenes):
+            self.boxes[i, :s["boxes"].shape[0]] = s["boxes"]
+        self.device = torch.device(device) if device is not None else None
+        self.dev = None
+        if self.device is not None:
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
+            self.dev = {
+                "cloud": t(np.concatenate([s["cloud"] for s in self.scenes])),
+                "votes": t(np.concatenate([s["votes"] for s in self.scenes])),
+                "offset": t(self.offset), "count": t(self.count),
+                "boxes": t(self.boxes), "nbox": t(self.nbox),
+            }
+
+    def __len__(self):
+        return len(self.scan_names)
+
+    def index(self, names):
+        where = {s: i for i, s in enumerate(self.scan_names)}
+        return np.array([where[s] for s in names], np.int64)
+
+
+# ------------------------------------------------------------------ host restatement
+def augmentation(u):
+    """uniforms -> (flip_x, angle, scale) with the reference's formulas
+    (sunrgbd_detection_dataset.py:155-191)."""
+    return int(u[0] > 0.5), (u[1] * np.pi / 3) - np.pi / 6, u[2] * 0.3 + 0.85
+
+
+def angle2class(angle, num_heading_bin):
+    """model_util_sunrgbd.py:92-108 (float64, Python's float modulo)."""
+    angle = angle % (2 * np.pi)
+    per = 2 * np.pi / float(num_heading_bin)
+    shifted = (angle + per / 2) % (2 * np.pi)
+    class_id = int(shifted / per)
+    return class_id, shifted - (class_id * per + per / 2)
+
+
+def host_scene(scene, idx, u=None, votes=True, boxes="raw", mean_size=None, has_height=True,
+               num_heading_bin=12, div256=False, color=None):
+    """One scene of a batch in numpy, in the reference's arithmetic: the sample `idx`, the
+    augmentation of the uniforms `u` (None: none), the colour augmentation `color` = (u_color (6,),
+    u_jitter (n,), u_drop (n,)) by source point, vote labels, box labels ('aug': in the augmented
+    frame, 'raw': un-augmented, None: none).  Every per-point operation of the reference commutes
+    with the sampling, so only the sampled rows are computed."""
+    idx = np.asarray(idx)
+    pc = scene["cloud"][idx].copy()
+    has_color = pc.shape[1] >= 6
+    if div256 and has_color:
+        pc[:, 3:6] = pc[:, 3:6] / 256.0
+    bb = scene["boxes"].copy()
+    out = {}
+    pv = scene["votes"][idx].astype(np.float64) if votes else None
+    if u is not None:
+        fx, angle, scale = augmentation(u)
+        aug_boxes = boxes == "aug"
+        if fx:
+            pc[:, 0] = -1 * pc[:, 0]
+            if aug_boxes:
+                bb[:, 0] = -1 * bb[:, 0]
+                bb[:, 6] = np.pi - bb[:, 6]
+            if votes:
+                pv[:, [1, 4, 7]] = -1 * pv[:, [1, 4, 7]]
+        rot = rotz(angle)
+        pc[:, 0:3] = np.dot(pc[:, 0:3], np.transpose(rot))
+        if aug_boxes:
+            bb[:, 0:3] = np.dot(bb[:, 0:3], np.transpose(rot))
+            bb[:, 6] -= angle
+        c, s = rot[0, 0], rot[1, 0]
+        if votes:  # rot(p + v) - rot(p) as rot(v), elementwise in the device's order
+            for k in (1, 4, 7):
+                x, y, z = pv[:, k].copy(), pv[:, k + 1].copy(), pv[:, k + 2].copy()
+                pv[:, k] = x * c + y * -s + z * 0.0
+                pv[:, k + 1] = x * s + y * c + z * 0.0
+                pv[:, k + 2] = x * 0.0 + y * 0.0 + z * 1.0
+        if color is not None and has_color:
+            u_color, u_jit, u_drop = color
+            rgb = pc[:, 3:6] + MEAN_COLOR_RGB
+            rgb *= (1 + 0.4 * np.asarray(u_color[0:3]) - 0.2)
+            rgb += (0.1 * np.asarray(u_color[3:6]) - 0.05)
+            rgb += np.expand_dims((0.05 * np.asarray(u_jit)[idx] - 0.025), -1)
+            rgb = np.clip(rgb, 0, 1)
+            rgb *= np.expand_dims(np.asarray(u_drop)[idx] > 0.3, -1)
+            pc[:, 3:6] = rgb - MEAN_COLOR_RGB
+        scale_ratio = np.expand_dims(np.tile(scale, 3), 0)
+        pc[:, 0:3] *= scale_ratio
+        if aug_boxes:
+            bb[:, 0:3] *= scale_ratio
+            bb[:, 3:6] *= scale_ratio
+        if votes:
+            for k in (1, 4, 7):
+                pv[:, k:k + 3] *= scale_ratio
+        if has_height:
+            pc[:, -1] *= scale_ratio[0, 0]
+        out.update(flip_x_axis=fx, flip_y_axis=0, rot_mat=rot.astype(np.float32),
+                   rot_angle=np.float32(angle), scale=scale_ratio.astype(np.float32))
+    else:
+        out.update(flip_x_axis=0, flip_y_axis=0, rot_mat=np.identity(3, np.float32),
+                   rot_angle=np.float32(0), scale=np.ones((1, 3), np.float32))
+    out["point_clouds"] = pc.astype(np.float32)
+    if votes:
+        out["vote_label"] = pv[:, 1:].astype(np.float32)
+        out["vote_label_mask"] = pv[:, 0].astype(np.int64)
+    if boxes is not None:
+        nb = bb.shape[0]
+        target = np.zeros((MAX_NUM_OBJ, 6))
+        target[:nb] = bb[:, 0:6]
+        angle_classes, angle_residuals = np.zeros(MAX_NUM_OBJ), np.zeros(MAX_NUM_OBJ)
+        size_classes, size_residuals = np.zeros(MAX_NUM_OBJ), np.zeros((MAX_NUM_OBJ, 3))
+        mask = np.zeros(MAX_NUM_OBJ, np.float32)
+        mask[:nb] = 1
+        for i in range(nb):
+            cls = int(bb[i, 7])
+            angle_classes[i], angle_residuals[i] = angle2class(bb[i, 6], num_heading_bin)
+            size_classes[i] = cls
+            size_residuals[i] = bb[i, 3:6] * 2 - mean_size[cls]
+        out.update(center_label=target.astype(np.float32)[:, 0:3],
+                   heading_class_label=angle_classes.astype(np.int64),
+                   heading_residual_label=angle_residuals.astype(np.float32),
+                   size_class_label=size_classes.astype(np.int64),
+                   size_residual_label=size_residuals.astype(np.float32),
+                   sem_cls_label=size_classes.astype(np.int64), box_label_mask=mask)
+    return out
+
+
+_BOX_KEYS = ("center_label", "heading_class_label", "heading_residual_label", "size_class_label",
+             "size_residual_label", "sem_cls_label", "box_label_mask")
+_DRAW_KEYS = ("flip_x_axis", "flip_y_axis", "rot_mat", "rot_angle", "scale")
+
+
+def uniforms(seed, counter, row):
+    """The three uniforms in [0, 1) of a row: flip, angle, scale (float64, 32 bits)."""
+    return draw_key(seed, counter, row, DRAW_FLIP + np.arange(3)).astype(np.float64) * 2.0 ** -32
+
+
+def color_uniforms(seed, counter, row):
+    """The six colour uniforms of a row: brightness rgb, shift rgb."""
+    return draw_key(seed, counter, row, DRAW_COLOR + np.arange(6)).astype(np.float64) * 2.0 ** -32
+
+
+def point_uniforms(seed, counter, row, n):
+    """(2, n): the jitter and the drop uniform of every SOURCE point of a row's scene."""
+    p = np.arange(n, dtype=np.uint32)
+    return np.stack([_element(draw_key(seed, counter, row, d), p).astype(np.float64) * 2.0 ** -32
+                     for d in (DRAW_JITTER, DRAW_DROP)])
+
+
+# ------------------------------------------------------------------ batches
+class _Args(ctypes.Structure):  # field order == include/sunrgbd_hip.h SunBatchArgs
+    _fields_ = ([(n, _c_int) for n in ("B", "N", "C", "has_height", "augment", "color_aug", "ema",
+                                       "vote_rows", "box_rows", "box_aug_rows", "div256_from", "NS",
+                                       "num_heading_bin", "u_point_stride")] +
+                [("seed", _c_uint), ("counter", _c_uint)] +
+                [(n, _c_int * MAX_BATCH) for n in ("scene", "scan_idx", "supervised")] +
+                [(n, _vp) for n in ("cloud", "votes", "offset", "count", "boxes", "nbox", "mean_size",
+                                    "idx_in", "ema_idx_in", "u_in", "u_color_in", "u_point_in",
+                                    "point_clouds", "ema_point_clouds", "vote_label", "vote_label_mask",
+                                    "center_label", "heading_class_label", "heading_residual_label",
+                                    "size_class_label", "size_residual_label", "sem_cls_label",
+                                    "box_label_mask", "supervised_mask", "scan_idx_out", "flip_x_axis",
+                                    "flip_y_axis", "rot_angle", "rot_mat", "scale")])
+
+
+class SunRgbdLoader(object):
+    """Batches of `num_points` points per scene from `scenes`, with the semantics of the reference's
+    datasets:
+
+      pretrain_batch   SunrgbdDetectionVotesDataset('train', augment=True), with its per-point colour
+                       augmentation when the store has colour
+      semi_batch       SunrgbdSSLLabeledDataset + SunrgbdSSLUnlabeledDataset rows (augment=True)
+      eval_batch       SunrgbdDetectionVotesDataset('val', augment=False)
+
+    `labeled` / `unlabeled`: the scan names of each list (default: every scan of the store); ids
+    passed to the builders index these lists and are what scan_idx reports.  `config.mean_size_arr`
+    (sunrgbd_config(mean_size_arr=...)) gives the size residuals, in float64 as the reference.
+    Device draws are keyed by (seed, counter, batch row, draw index), per-point colour draws
+    additionally by the source point index; `draws=` replaces them with explicit ones:
+    {'idx': (B, N) ints, 'ema_idx': (B, N), 'u': (B, 3) float64 uniforms (flip, angle, scale),
+    'u_color': (B, 6), 'u_point': (B, 2, n_max) jitter and drop by source point}."""
+
+    def __init__(self, scenes, config, num_points, seed=0, labeled=None, unlabeled=None):
+        self.scenes, self.config, self.num_points, self.seed = scenes, config, int(num_points), int(seed)
+        self.mean_size = np.asarray(getattr(config, "mean_size_arr_f64", config.mean_size_arr), np.float64)
+        self.labeled = scenes.index(labeled) if labeled is not None else np.arange(len(scenes))
+        self.unlabeled = scenes.index(unlabeled) if unlabeled is not None else np.arange(len(scenes))
+        self._mean_dev = None
+        if scenes.device is not None:
+            self._mean_dev = torch.from_numpy(np.ascontiguousarray(self.mean_size)).to(scenes.device)
+
+    # ---------------------------------------------------------------- layouts
+    def _layout(self, kind, nl, nu=0, unlabeled_labels=False):
+        N, C = self.num_points, self.scenes.channels
+        B = nl + nu
+        f, i64 = torch.float32, torch.int64
+        shapes = {"point_clouds": ((B, N, C), f), "supervised_mask": ((B,), i64), "scan_idx": ((B,), i64)}
+        vote_rows = nl
+        box_rows = B if (kind == "semi" and unlabeled_labels) else nl
+        shapes.update({"vote_label": ((vote_rows, N, 9), f), "vote_label_mask": ((vote_rows, N), i64),
+                       "center_label": ((box_rows, MAX_NUM_OBJ, 3), f),
+                       "heading_class_label": ((box_rows, MAX_NUM_OBJ), i64),
+                       "heading_residual_label": ((box_rows, MAX_NUM_OBJ), f),
+                       "size_class_label": ((box_rows, MAX_NUM_OBJ), i64),
+                       "size_residual_label": ((box_rows, MAX_NUM_OBJ, 3), f),
+                       "sem_cls_label": ((box_rows, MAX_NUM_OBJ), i64),
+                       "box_label_mask": ((box_rows, MAX_NUM_OBJ), f)})
+        if kind == "semi":
+            shapes.update({"ema_point_clouds": ((B, N, C), f), "flip_x_axis": ((B,), i64),
+                           "flip_y_axis": ((B,), i64), "rot_angle": ((B,), f), "rot_mat": ((B, 3, 3), f),
+                           "scale": ((B, 1, 3), f)})
+        return shapes, vote_rows, box_rows
+
+    def allocate(self, kind, nl, nu=0, unlabeled_labels=False):
+        """One output set (batch tensors; this builder needs no scratch) on the store's device."""
+        shapes, _, _ = self._layout(kind, nl, nu, unlabeled_labels)
+        dev = self.scenes.device
+        return {k: torch.empty(s, dtype=d, device=dev) for k, (s, d) in shapes.items()}, {}
+
+    # ---------------------------------------------------------------- device builds
+    def _rows(self, kind, labeled_ids, unlabeled_ids):
+        lab = np.asarray(labeled_ids, np.int64).reshape(-1)
+        unl = np.asarray(unlabeled_ids if unlabeled_ids is not None else [], np.int64).reshape(-1)
+        if kind == "semi":
+            scene = np.concatenate([self.labeled[lab], self.unlabeled[unl]])
+        else:
+            scene = self.labeled[lab]
+        scan_idx = np.concatenate([lab, unl])
+        if not 1 <= len(scene) <= MAX_BATCH:
+            raise ValueError("a batch holds 1..%d scenes, got %d" % (MAX_BATCH, len(scene)))
+        return scene, scan_idx, len(lab), len(unl)
+
+    def _color_aug(self, kind):
+        return kind == "pretrain" and self.scenes.use_color
+
+    def _build(self, kind, labeled_ids, unlabeled_ids=None, counter=0, unlabeled_labels=False,
+               out=None, draws=None, stream=None):
+        scene, scan_idx, nl, nu = self._rows(kind, labeled_ids, unlabeled_ids)
+        B, N, C = len(scene), self.num_points, self.scenes.channels
+        given = {}
+        n_max = int(self.scenes.count[scene].max())
+        if draws is not None:  # bounds: checked on the host before anything is launched
+            counts = self.scenes.count[scene]
+            for key in ("idx", "ema_idx"):
+                if key in draws:
+                    v = np.asarray(draws[key]).reshape(B, N)
+                    if (v < 0).any() or (v >= counts[:, None]).any():
+                        raise ValueError("explicit draws %r out of range of the scenes' point counts" % key)
+                    given[key] = np.ascontiguousarray(v, np.int32)
+            if "u" in draws:
+                given["u"] = np.ascontiguousarray(np.asarray(draws["u"], np.float64).reshape(B, 3))
+            if "u_color" in draws:
+                given["u_color"] = np.ascontiguousarray(np.asarray(draws["u_color"], np.float64).reshape(B, 6))
+            if "u_point" in draws:
+                v = np.asarray(draws["u_point"], np.float64)
+                if v.ndim != 3 or v.shape[0] != B or v.shape[1] != 2 or v.shape[2] < n_max:
+                    raise ValueError("explicit draws 'u_point' have shape %s, expected (%d, 2, >= %d)"
+                                     % (v.shape, B, n_max))
+                given["u_point"] = np.ascontiguousarray(v)
+        if self.scenes.dev is None:
+            raise RuntimeError("SunRgbdLoader: the store has no device copy (device=None); use host_batch")
+        _L = importlib.import_module("3dioumatch_amd._lib")
+        shapes, vote_rows, box_rows = self._layout(kind, nl, nu, unlabeled_labels)
+        current = torch.cuda.current_stream(self.scenes.device)
+        if stream is None:
+            stream = current
+        fresh = out is None
+        if fresh:
+            out = self.allocate(kind, nl, nu, unlabeled_labels)
+        batch = out[0]
+        for k, (s, d) in shapes.items():
+            if k not in batch or tuple(batch[k].shape) != s or batch[k].dtype != d:
+                raise ValueError("output set does not match the batch layout at %r" % k)
+        a = _Args()
+        a.B, a.N, a.C = B, N, C
+        a.has_height = int(self.scenes.use_height)
+        a.augment = int(kind != "eval")
+        a.color_aug = int(self._color_aug(kind))
+        a.ema = int(kind == "semi")
+        a.vote_rows, a.box_rows = vote_rows, box_rows
+        a.box_aug_rows = vote_rows if kind != "eval" else 0
+        a.div256_from = nl if kind == "semi" else B
+        a.NS = self.mean_size.shape[0]
+        a.num_heading_bin = int(self.config.num_heading_bin)
+        a.seed, a.counter = self.seed & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF
+        for r in range(B):
+            a.scene[r], a.scan_idx[r], a.supervised[r] = int(scene[r]), int(scan_idx[r]), int(r < nl)
+        d = self.scenes.dev
+        for k in ("cloud", "votes", "offset", "count", "boxes", "nbox"):
+            setattr(a, k, d[k].data_ptr())
+        a.mean_size = self._mean_dev.data_ptr()
+        keep = []  # device memory this call allocates on the current stream and `stream` writes or reads
+        for key, field in (("idx", "idx_in"), ("ema_idx", "ema_idx_in"), ("u", "u_in"),
+                           ("u_color", "u_color_in"), ("u_point", "u_point_in")):
+            if key in given:
+                t = torch.from_numpy(given[key]).to(self.scenes.device)
+                keep.append(t)
+                setattr(a, field, t.data_ptr())
+        if "u_point" in given:
+            a.u_point_stride = given["u_point"].shape[2]
+        if fresh:
+            keep += list(batch.values())
+        for k in ("point_clouds", "ema_point_clouds", "vote_label", "vote_label_mask", "center_label",
+                  "heading_class_label", "heading_residual_label", "size_class_label",
+                  "size_residual_label", "sem_cls_label", "box_label_mask", "supervised_mask",
+                  "flip_x_axis", "flip_y_axis", "rot_angle", "rot_mat", "scale"):
+            if k in batch:
+                setattr(a, k, batch[k].data_ptr())
+        a.scan_idx_out = batch["scan_idx"].data_ptr()
+        if keep and stream != current:
+            stream.wait_stream(current)  # the blocks just allocated may have been freed by queued work
+        with torch.cuda.device(self.scenes.device):
+            _L.check(_L.lib.scene_sunrgbd_batch_build(ctypes.byref(a), stream.cuda_stream),
+                     "scene_sunrgbd_batch_build")
+        for t in keep:  # not handed to another allocation before `stream` is done with them
+            t.record_stream(stream)
+        result = dict(batch)
+        result["supervised_mask_host"] = tuple([1] * nl + [0] * nu)
+        return result
+
+    def pretrain_batch(self, ids, counter=0, out=None, draws=None, stream=None):
+        return self._build("pretrain", ids, None, counter, out=out, draws=draws, stream=stream)
+
+    def semi_batch(self, labeled_ids, unlabeled_ids, counter=0, unlabeled_labels=False, out=None,
+                   draws=None, stream=None):
+        return self._build("semi", labeled_ids, unlabeled_ids, counter, unlabeled_labels, out=out,
+                           draws=draws, stream=stream)
+
+    def eval_batch(self, ids, counter=0, out=None, draws=None, stream=None):
+        return self._build("eval", ids, None, counter, out=out, draws=draws, stream=stream)
+
+    # ---------------------------------------------------------------- the host restatement
+    def host_draws(self, kind, labeled_ids, unlabeled_ids=None, counter=0):
+        """The device's own draws of a batch, on the host (exact)."""
+        scene, _, nl, nu = self._rows(kind, labeled_ids, unlabeled_ids)
+        B, N = len(scene), self.num_points
+        n = self.scenes.count[scene]
+        draws = {"idx": np.stack([sample_indices(self.seed, counter, r, DRAW_STUDENT, n[r], N) for r in range(B)])}
+        if kind == "semi":
+            draws["ema_idx"] = np.stack([sample_indices(self.seed, counter, r, DRAW_EMA, n[r], N)
+                                         for r in range(B)])
+        if kind != "eval":
+            draws["u"] = np.stack([uniforms(self.seed, counter, r) for r in range(B)])
+        if self._color_aug(kind):
+            draws["u_color"] = np.stack([color_uniforms(self.seed, counter, r) for r in range(B)])
+            up = np.zeros((B, 2, int(n.max())))
+            for r in range(B):
+                up[r, :, :n[r]] = point_uniforms(self.seed, counter, r, n[r])
+            draws["u_point"] = up
+        return draws
+
+    def host_batch(self, kind, labeled_ids, unlabeled_ids=None, counter=0, unlabeled_labels=False,
+                   draws=None):
+        """numpy restatement of pretrain_batch / semi_batch / eval_batch (kind = 'pretrain' | 'semi' |
+        'eval'): the same outputs for the same draws (default: the device's, host_draws)."""
+        scene, scan_idx, nl, nu = self._rows(kind, labeled_ids, unlabeled_ids)
+        if draws is None:
+            draws = self.host_draws(kind, labeled_ids, unlabeled_ids, counter)
+        hh = self.scenes.use_height
+        rows = []
+        for r, s in enumerate(scene):
+            sc = self.scenes.scenes[s]
+            u = np.asarray(draws["u"])[r] if kind != "eval" else None
+            lab = r < nl
+            box = ("aug" if kind != "eval" else "raw") if lab else ("raw" if unlabeled_labels else None)
+            color = None
+            if self._color_aug(kind):
+                up = np.asarray(draws["u_point"])[r]
+                color = (np.asarray(draws["u_color"])[r], up[0], up[1])
+            div256 = kind == "semi" and not lab
+            row = host_scene(sc, np.asarray(draws["idx"][r]), u, votes=lab, boxes=box,
+                             mean_size=self.mean_size, has_height=hh,
+                             num_heading_bin=self.config.num_heading_bin, div256=div256, color=color)
+            if kind == "semi":
+                ema = sc["cloud"][np.asarray(draws["ema_idx"][r])].astype(np.float32)
+                if div256 and self.scenes.use_color:
+                    ema[:, 3:6] = ema[:, 3:6] / 256.0
+                row["ema_point_clouds"] = ema
+            rows.append(row)
+        out = _stack(rows, ["point_clouds"])
+        out.update(_stack(rows[:nl], ("vote_label", "vote_label_mask"), self.num_points))
+        box_rows = nl + nu if (kind == "semi" and unlabeled_labels) else nl
+        out.update(_stack(rows[:box_rows], _BOX_KEYS))
+        if kind == "semi":
+            out.update(_stack(rows, ("ema_point_clouds",) + _DRAW_KEYS))
+            out["rot_angle"] = out["rot_angle"].astype(np.float32)
+        out["supervised_mask"] = np.array([1] * nl + [0] * nu, np.int64)
+        out["scan_idx"] = scan_idx.astype(np.int64)
+        return out
+
+
+# ------------------------------------------------------------------ synthetic scans
+def write_synthetic_scans(data_dir, names, num_points=50000, boxes=12, seed=0, dtype=np.float32):
+    """Seeded SUN RGB-D-sized stand-ins in the on-disk layout (for tests and tools/, where no dataset
+    is at hand): `boxes` oriented boxes, some of them overlapping; two thirds of the points fall
+    inside a box; a point's vote row holds the offsets to the centres of the first three boxes that
+    contain it (one box: the vote three times; two: first, second, first), mask 1."""
+    g = np.random.default_rng(seed)
+    for name in names:
+        box = np.zeros((boxes, 8))
+        box[:, 0:3] = g.random((boxes, 3)) * [5.0, 4.0, 1.5] + [-2.5, 1.0, -1.0]
+        if boxes > 2:  # overlapping boxes: points with two and three votes
+            box[1, 0:3] = box[0, 0:3] + [0.1, -0.1, 0.05]
+            box[2, 0:3] = box[0, 0:3] + [-0.1, 0.05, 0.0]
+        box[:, 3:6] = g.random((boxes, 3)) * 0.6 + 0.15
+        box[:, 6] = g.random(boxes) * 2 * np.pi - np.pi
+        box[:, 7] = g.integers(0, NUM_CLASS, boxes)
+        xyz = g.random((num_points, 3)) * [6.0, 5.0, 2.5] + [-3.0, 0.5, -1.3]
+        if boxes:
+            inside = np.where(g.random(num_points) < 2.0 / 3.0)[0]
+            b = g.integers(0, boxes, inside.size)
+            local = (g.random((inside.size, 3)) * 2 - 1) * box[b, 3:6]
+            c, s = np.cos(box[b, 6]), np.sin(box[b, 6])
+            xyz[inside, 0] = box[b, 0] + local[:, 0] * c + local[:, 1] * s
+            xyz[inside, 1] = box[b, 1] - local[:, 0] * s + local[:, 1] * c
+            xyz[inside, 2] = box[b, 2] + local[:, 2]
+        xyz = xyz.astype(dtype)
+        votes = np.zeros((num_points, VOTE_COLS))
+        hits = np.zeros(num_points, np.int64)
+        for k in range(boxes):
+            d = xyz.astype(np.float64) - box[k, 0:3]
+            c, s = np.cos(box[k, 6]), np.sin(box[k, 6])
+            lx, ly = d[:, 0] * c - d[:, 1] * s, d[:, 0] * s + d[:, 1] * c
+            within = (np.abs(lx) <= box[k, 3] + 1e-9) & (np.abs(ly) <= box[k, 4] + 1e-9) & \
+                (np.abs(d[:, 2]) <= box[k, 5] + 1e-9)
+            first, second, third = within & (hits == 0), within & (hits == 1), within & (hits == 2)
+            votes[first, 0] = 1.0
+            votes[first, 1:10] = np.tile(-d[first], (1, 3))
+            votes[second, 4:7] = -d[second]
+            votes[third, 7:10] = -d[third]
+            hits += within
+        rgb = g.random((num_points, 3)).astype(dtype)
+        np.savez(os.path.join(data_dir, name + "_pc.npz"), pc=np.concatenate([xyz, rgb], 1))
+        np.save(os.path.join(data_dir, name + "_bbox.npy"), box)
+        np.savez(os.path.join(data_dir, name + "_votes.npz"), point_votes=votes)
