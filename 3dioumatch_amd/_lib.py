@@ -11,6 +11,18 @@ LIB_PATH = os.path.join(_HERE, "lib3dioumatch_hip%s.so" % os.environ.get("PN2_LI
 
 _c_int, _c_float, _vp, _sz = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
+
+class MlpOperand(ctypes.Structure):  # field order == include/mlp_hip.h
+    _fields_ = [("mode", _c_int), ("x", _vp), ("dz", _vp), ("scale", _vp), ("shift", _vp), ("mean", _vp),
+                ("invstd", _vp), ("coef", _vp), ("argmax", _vp), ("ns", _c_int), ("groups", _c_int),
+                ("lin_w", _vp)]
+
+
+# an operand of the shared-MLP GEMMs: a typed pointer, so that anything but a record (or None) in its
+# place -- an argument list in another order, an old positional call -- is a ctypes.ArgumentError
+# before the call instead of an address the library reads
+_op = ctypes.POINTER(MlpOperand)
+
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 _SIGNATURES = {
     "pn2_furthest_point_sampling": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp],
@@ -68,24 +80,14 @@ _SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mlp_bn_relu_backward_stats": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "mlp_gemm_forward": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp],
+    # the GEMM family: (b, m, k, r), then pointers; _op = a MlpOperand record
+    "mlp_gemm_forward": [_c_int] * 4 + [_vp, _vp, _op, _vp, _vp, _vp],
     "mlp_gemm_forward_stats_parts": [_c_int, _c_int, _c_int, _c_int, _vp],
-    "mlp_gemm_forward_stats": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp],
     "mlp_bn_finalize_pairs": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_float, _c_float, _vp, _vp,
                               _vp, _vp, _vp, _vp, _vp, _vp],
     "mlp_bn_finalize_pairs_scratch_bytes": [_c_int],
-    "mlp_gemm_dgrad": [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
-                       _vp, _vp, _vp, _vp],
-    "mlp_gemm_wgrad": [_c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                       _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp],
-    "mlp_gemm_dgrad_nt": [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
-                          _vp, _vp, _vp, _vp],
-    "mlp_gemm_dgrad_pooled_nt": [_c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp,
-                                 _vp, _vp, _vp, _vp, _vp, _vp],
-    "mlp_gemm_dgrad_pooled": [_c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
-                              _vp, _vp, _vp, _vp, _vp],
-    "mlp_gemm_wgrad_pooled": [_c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
-                              _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mlp_gemm_dgrad": [_c_int] * 4 + [_vp, _op, _vp, _vp],
+    "mlp_gemm_wgrad": [_c_int] * 4 + [_op, _op, _vp, _vp, _vp],
     "mlp_gemm_wgrad_workspace_floats": [_c_int, _c_int, _c_int, _c_int],
     "mlp_gemm_forward_stats_pool_supported": [_c_int, _c_int, _c_int, _c_int, _c_int],
     "mlp_gemm_forward_stats_pool": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_int,
@@ -122,9 +124,7 @@ _SIGNATURES = {
     "mlp_gemm_forward_stats_lin4": [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mlp_gemm_backward_fused_supported": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int],
     "mlp_gemm_backward_fused_workspace_floats": [_c_int, _c_int, _c_int, _c_int],
-    "mlp_gemm_backward_fused": [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _c_int,
-                                _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
-                                _vp, _vp, _vp, _vp, _vp],
+    "mlp_gemm_backward_fused": [_c_int] * 4 + [_vp, _op, _op] + [_vp] * 5,
     "mlp_gemm_backward_fused_stats_parts": [_c_int, _c_int, _c_int, _c_int],
     "mlp_bn_backward_finalize": [_c_int, _c_int, ctypes.c_double, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp],
@@ -132,17 +132,12 @@ _SIGNATURES = {
     "mlp_weight_image_elems": [_c_int, _c_int],
     "mlp_weight_images_build": [_c_int, _vp, _vp, _vp, _vp, _vp, _vp],
     "mlp_gemm_image_supported": [_c_int, _c_int],
-    "mlp_gemm_forward_img": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp],
-    "mlp_gemm_backward_small_img": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp,
-                                    _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "mlp_gemm_backward_small": [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp,
-                                _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mlp_gemm_backward_small": [_c_int] * 4 + [_vp, _vp, _op, _op] + [_vp] * 4,
     "mlp_pregather_supported": [_c_int, _c_int, _c_int, _c_int, _c_int],
     "mlp_pregather_pack": [_c_int, _c_int, _c_int, _c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp],
     "mlp_pregather_unpack_grad": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp],
     "mlp_pregather_forward": [_c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
-    "mlp_pregather_backward": [_c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
-                               _vp, _vp, _vp, _vp],
+    "mlp_pregather_backward": [_c_int] * 5 + [_op, _vp, _vp, _vp],
     "mlp_defer_weight_reductions": [_c_int],
     "mlp_flush_weight_reductions": [],
     "lhs_nms3d_aabb": [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _c_int, _vp,

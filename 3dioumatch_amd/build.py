@@ -30,7 +30,9 @@ def sources():
 
 
 def headers_mtime():
-    return max(os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC)
+    # csrc/*.h and the C ABI's headers, whose argument records the sources include (include/*.h)
+    include = os.path.join(os.path.dirname(HERE), "include")
+    return max(os.path.getmtime(os.path.join(d, f)) for d in (CSRC, include) for f in os.listdir(d)
                if f.endswith(".h"))
 
 

@@ -789,7 +789,7 @@ MLP_API int mlp_bn_train_stats(int b, int c, int r, const float *y, const float 
 }
 
 // Training-mode coefficients from the (mean, M2) pairs the forward GEMM left behind
-// (mlp_gemm_forward_stats): the statistics pass over y is gone.  scratch: device memory of
+// (mlp_gemm_forward with pairs): the statistics pass over y is gone.  scratch: device memory of
 // mlp_bn_finalize_pairs_scratch_bytes(c) bytes.
 MLP_API size_t mlp_bn_finalize_pairs_scratch_bytes(int c) {
   return sizeof(double) * 3 * (size_t)kPairSlices * (size_t)(c > 0 ? c : 0);

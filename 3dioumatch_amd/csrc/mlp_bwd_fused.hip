@@ -699,17 +699,19 @@ MLP_API size_t mlp_gemm_backward_fused_workspace_floats(int b, int m, int k, int
 }
 
 // dq (b,k,r) = W^T * P[b] and dw (m,k) = sum_b P[b] * Q[b]^T in one pass.
-// pmode 2: P from (y, dz) (b,m,r); pmode 3: from y, dz = dpooled (b,m,r/ns) and argmax.
-// qmode 1: Q = relu(x*xscale + xshift); qmode 0: Q = x.
-MLP_API int mlp_gemm_backward_fused(int b, int m, int k, int r, const float *w, int pmode,
-                                    const float *y, const float *dz, const int *argmax, int ns,
-                                    const float *scale, const float *shift, const float *mean,
-                                    const float *invstd, const float *coef, int qmode,
-                                    const float *x, const float *xscale, const float *xshift,
-                                    const float *xmean, const float *xinvstd, const float *xlin_w,
-                                    float *dq, float *dw, float *workspace, float *stats_part,
-                                    void *stream_) {
-  if (!mlp_gemm_backward_fused_supported(b, m, k, r, pmode, qmode, ns)) return (int)hipErrorInvalidValue;
+// P = dy: mode 2 (from (y, dz) (b,m,r)) or 3 (from y, dz = dpooled (b,m,r/ns) and argmax).
+// Q = x: mode 1 (relu(x*scale + shift)), 0 (x) or 4 (the virtual first layer below, recomputed).
+MLP_API int mlp_gemm_backward_fused(int b, int m, int k, int r, const float *w, const MlpOperand *dy,
+                                    const MlpOperand *x, float *dq, float *dw, float *workspace,
+                                    float *stats_part, void *stream_) {
+  if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
+  OperandB P, Q;
+  int orc = operand_from_abi(dy, op_bit(OP_DY) | op_bit(OP_POOLDY), r, &P);
+  if (!orc) orc = operand_from_abi(x, op_bit(OP_DIRECT) | op_bit(OP_BNRELU) | op_bit(OP_LIN4), r, &Q);
+  if (orc) return orc;
+  const int pmode = dy->mode, qmode = x->mode;
+  if (qmode != OP_DIRECT && (!Q.mean || !Q.invstd)) return (int)hipErrorInvalidValue;
+  if (!mlp_gemm_backward_fused_supported(b, m, k, r, pmode, qmode, P.ns)) return (int)hipErrorInvalidValue;
   FusedShape s;
   fused_shape(m, k, &s);
   if (dq == nullptr && !(m == 128 && k == 259)) return (int)hipErrorInvalidValue;
@@ -717,10 +719,6 @@ MLP_API int mlp_gemm_backward_fused(int b, int m, int k, int r, const float *w, 
   const int cpc = r / s.tn;
   const int total = b * cpc;
   const int g = fused_workgroups(s, total);
-  OperandB P = {y, dz, scale, shift, mean, invstd, coef, argmax, ns, ns > 0 ? r / ns : 0};
-  if ((qmode == OP_BNRELU || qmode == OP_LIN4) && (!xmean || !xinvstd)) return (int)hipErrorInvalidValue;
-  if (qmode == OP_LIN4 && !xlin_w) return (int)hipErrorInvalidValue;
-  OperandB Q = {x, nullptr, xscale, xshift, xmean, xinvstd, nullptr, nullptr, 0, 0, xlin_w};
   {  // the bf16-split kernel with its operands split at staging, where it covers the shape
     int gx = 0;
     const int rcx = mlp_bwd_x6_try(b, m, k, r, pmode, qmode, P, Q, w, dq, workspace,

@@ -1169,14 +1169,18 @@ void launch_stats(bool a_vec, int r, int b, hipStream_t stream, int rows, int k,
   }
 }
 
+// columns (batch x points) up to which a layer runs on the small 64 x 64 kernels (read per call so
+// that the tests can steer both regimes; a getenv costs nothing next to a launch)
+static long long small_gemm_cols() {
+  const char *env = getenv("MLP_SMALL_GEMM_COLS");
+  return env ? atoll(env) : 16384;
+}
+
 template <int MODE, bool A_TRANS = false>
 int launch_nn(int b, int m, int k, int r, const float *a, int lda, const OperandB &op, float *c,
               size_t in_stride, size_t out_stride, hipStream_t stream, float *stats = nullptr,
               const AImage img = AImage{nullptr, 0, 0}) {
-  // (read per call so that the tests can steer both kernels; a getenv costs nothing next to a launch)
-  const char *env = getenv("MLP_SMALL_GEMM_COLS");
-  const long long small_cols = env ? atoll(env) : 16384;
-  if ((long long)b * r <= small_cols) {  // a few hundred columns per cloud: latency-bound regime
+  if ((long long)b * r <= small_gemm_cols()) {  // a few hundred columns per cloud: latency-bound regime
     // (measured, tools/small_gemm_bench.py: the transposed form with a plain operand gains from the
     //  split at two workgroups per CU, 20 -> 15.6 us; with the on-the-fly dY operand it spills and does not)
     if ((!A_TRANS || MODE == OP_DIRECT) && img.p != nullptr)
@@ -1323,7 +1327,6 @@ MLP_API int mlp_weight_images_build(int n, const void *const *w, const int *m, c
   return pn2_launch_status();
 }
 
-// mode: 0 = X given directly, 1 = X = relu(bn(Yprev)) via (scale, shift)
 int mlp_reduce_partials(int count, int parts, const float *part, float *out, hipStream_t stream) {
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(pn2_ceil_div((long long)count, 32)), dim3(256), 0,
                      stream, count, parts, part, out);
@@ -1385,47 +1388,16 @@ MLP_API int mlp_flush_weight_reductions(void) {
   return reduce_queue_launch();
 }
 
-MLP_API int mlp_gemm_forward(int b, int m, int k, int r, const float *w, const float *x, int mode,
-                             const float *scale, const float *shift, float *y, void *stream_) {
-  if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
-  OperandB op = {x, nullptr, scale, shift, nullptr, nullptr, nullptr};
-  const size_t in_stride = (size_t)k * r, out_stride = (size_t)m * r;
-  if (mode == OP_DIRECT)
-    return launch_nn<OP_DIRECT>(b, m, k, r, w, k, op, y, in_stride, out_stride, (hipStream_t)stream_);
-  return launch_nn<OP_BNRELU>(b, m, k, r, w, k, op, y, in_stride, out_stride, (hipStream_t)stream_);
-}
-
-// 1 when the layer runs on the small 64 x 64 kernel in its bf16 form, i.e. when
-// mlp_gemm_forward_img / mlp_gemm_backward_small_img can take their weight from an image
+// 1 when the layer runs on the small 64 x 64 kernel in its bf16 form, i.e. when mlp_gemm_forward /
+// mlp_gemm_backward_small can take their weight from an image
 MLP_API int mlp_gemm_image_supported(int b, int r) {
-  const char *env = getenv("MLP_SMALL_GEMM_COLS");
-  const long long small_cols = env ? atoll(env) : 16384;
-  return b > 0 && r > 0 && (long long)b * r <= small_cols;
-}
-
-// mlp_gemm_forward with the weight ALSO given as the bf16 image mlp_weight_images_build made of it
-// (img: the [plane][m][k] order): same result bit for bit, the kernel neither stages nor splits w
-MLP_API int mlp_gemm_forward_img(int b, int m, int k, int r, const float *w, const void *img,
-                                 const float *x, int mode, const float *scale, const float *shift,
-                                 float *y, void *stream_) {
-  if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
-  if (!img || !mlp_gemm_image_supported(b, r)) return (int)hipErrorInvalidValue;
-  OperandB op = {x, nullptr, scale, shift, nullptr, nullptr, nullptr};
-  const size_t in_stride = (size_t)k * r, out_stride = (size_t)m * r;
-  const AImage ai = {reinterpret_cast<const unsigned short *>(img), pad64(k), (size_t)pad64(m) * pad64(k)};
-  if (mode == OP_DIRECT)
-    return launch_nn<OP_DIRECT>(b, m, k, r, w, k, op, y, in_stride, out_stride, (hipStream_t)stream_,
-                                nullptr, ai);
-  return launch_nn<OP_BNRELU>(b, m, k, r, w, k, op, y, in_stride, out_stride, (hipStream_t)stream_,
-                              nullptr, ai);
+  return b > 0 && r > 0 && (long long)b * r <= small_gemm_cols();
 }
 
 // Can the forward GEMM of this shape leave BatchNorm partials behind?  Returns the number of
 // (mean, M2) pairs per channel (0: no -- use mlp_bn_train_stats on y) and the columns each covers.
 MLP_API int mlp_gemm_forward_stats_parts(int b, int m, int k, int r, int *cols_per_part) {
-  const char *env = getenv("MLP_SMALL_GEMM_COLS");
-  const long long small_cols = env ? atoll(env) : 16384;
-  if (b <= 0 || r % 256 != 0 || (long long)b * r <= small_cols) return 0;
+  if (b <= 0 || r % 256 != 0 || (long long)b * r <= small_gemm_cols()) return 0;
   int tn;
   if (m == 256) tn = 64;            // one 256 x 64 tile per column block
   else if (m > 32 && m <= 128) tn = 128; // one 128 x 128 / 64 x 128 tile
@@ -1434,20 +1406,27 @@ MLP_API int mlp_gemm_forward_stats_parts(int b, int m, int k, int r, int *cols_p
   return b * (r / tn);
 }
 
-// mlp_gemm_forward that also writes the (mean, M2) pairs of every output channel per part into
-// `pairs` (parts x m x 2 floats, parts from mlp_gemm_forward_stats_parts)
-MLP_API int mlp_gemm_forward_stats(int b, int m, int k, int r, const float *w, const float *x,
-                                   int mode, const float *scale, const float *shift, float *y,
-                                   float *pairs, void *stream_) {
+// y = w * x.  img: the weight ALSO as the bf16 image mlp_weight_images_build made of it (the
+// [plane][m][k] order): same result bit for bit, the kernel neither stages nor splits w.  pairs: the
+// (mean, M2) pairs of every output channel per part (parts x m x 2 floats, parts from
+// mlp_gemm_forward_stats_parts).  The two regimes are disjoint.
+MLP_API int mlp_gemm_forward(int b, int m, int k, int r, const float *w, const void *img,
+                             const MlpOperand *x, float *y, float *pairs, void *stream_) {
   if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
-  if (!pairs || mlp_gemm_forward_stats_parts(b, m, k, r, nullptr) == 0) return (int)hipErrorInvalidValue;
-  OperandB op = {x, nullptr, scale, shift, nullptr, nullptr, nullptr};
+  OperandB op;
+  const int rc = operand_from_abi(x, op_bit(OP_DIRECT) | op_bit(OP_BNRELU), r, &op);
+  if (rc) return rc;
+  if ((img && pairs) || (img && !mlp_gemm_image_supported(b, r)) ||
+      (pairs && mlp_gemm_forward_stats_parts(b, m, k, r, nullptr) == 0))
+    return (int)hipErrorInvalidValue;
   const size_t in_stride = (size_t)k * r, out_stride = (size_t)m * r;
-  if (mode == OP_DIRECT)
-    return launch_nn<OP_DIRECT>(b, m, k, r, w, k, op, y, in_stride, out_stride,
-                                (hipStream_t)stream_, pairs);
+  const AImage ai = {reinterpret_cast<const unsigned short *>(img), img ? pad64(k) : 0,
+                     img ? (size_t)pad64(m) * pad64(k) : 0};
+  if (x->mode == OP_DIRECT)
+    return launch_nn<OP_DIRECT>(b, m, k, r, w, k, op, y, in_stride, out_stride, (hipStream_t)stream_,
+                                pairs, ai);
   return launch_nn<OP_BNRELU>(b, m, k, r, w, k, op, y, in_stride, out_stride, (hipStream_t)stream_,
-                              pairs);
+                              pairs, ai);
 }
 
 // 1 when mlp_gemm_forward_stats_pool covers the pooled last layer: statistics from the epilogue
@@ -1457,7 +1436,7 @@ MLP_API int mlp_gemm_forward_stats_pool_supported(int b, int m, int k, int r, in
   return (m == 128 || m == 256) && (ns == 16 || ns == 32 || ns == 64) && r % ns == 0 && k % 4 == 0;
 }
 
-// mlp_gemm_forward_stats (mode 1: x = raw output of the previous layer) that also leaves, per
+// mlp_gemm_forward with pairs (mode 1: x = raw output of the previous layer) that also leaves, per
 // channel and group of ns columns, the raw output that wins the max-pool after BatchNorm (gamma:
 // the layer's BatchNorm weight, whose sign decides between largest and smallest) and its first
 // index: ext = 2 planes of b*m*(r/ns) 4-byte values.  y may be NULL: the raw output is then not
@@ -1491,7 +1470,7 @@ MLP_API int mlp_gemm_forward_stats_pool(int b, int m, int k, int r, const float 
   return pn2_launch_status();
 }
 
-// mlp_gemm_forward_stats for the SECOND layer of a chain whose first layer has a 4-channel
+// mlp_gemm_forward with pairs for the SECOND layer of a chain whose first layer has a 4-channel
 // input: the operand relu(bn(W1 x4)) is recomputed from x4 (b,4,r) -- the first layer's output
 // is never stored.  w (64,64), w1 (64,4), scale / shift (64) of the first layer's BatchNorm.
 MLP_API int mlp_gemm_forward_stats_lin4(int b, int r, const float *w, const float *x4,
@@ -1509,37 +1488,21 @@ MLP_API int mlp_gemm_forward_stats_lin4(int b, int r, const float *w, const floa
   return pn2_launch_status();
 }
 
-// dX (b,k,r) = W^T (k x m, given as wt row-major) * dY, with dY either given (mode 0: dy) or
-// formed on the fly from (y, dz) and the per-channel vectors of the BN+ReLU backward (mode 2)
-MLP_API int mlp_gemm_dgrad(int b, int m, int k, int r, const float *wt, int mode, const float *dy,
-                           const float *y, const float *dz, const float *scale,
-                           const float *shift, const float *mean, const float *invstd,
-                           const float *coef, float *dx, void *stream_) {
+// dX (b,k,r) = W^T * dY with the weight as stored, w (m,k) row-major (no transposed copy); dY given
+// (mode 0) or formed on the fly (modes 2 / 3)
+MLP_API int mlp_gemm_dgrad(int b, int m, int k, int r, const float *w, const MlpOperand *dy,
+                           float *dx, void *stream_) {
   if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
+  OperandB op;
+  const int rc = operand_from_abi(dy, op_bit(OP_DIRECT) | op_bit(OP_DY) | op_bit(OP_POOLDY), r, &op);
+  if (rc) return rc;
   const size_t in_stride = (size_t)m * r, out_stride = (size_t)k * r;
-  if (mode == OP_DIRECT) {
-    OperandB op = {dy, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return launch_nn<OP_DIRECT>(b, k, m, r, wt, m, op, dx, in_stride, out_stride, (hipStream_t)stream_);
-  }
-  OperandB op = {y, dz, scale, shift, mean, invstd, coef};
-  return launch_nn<OP_DY>(b, k, m, r, wt, m, op, dx, in_stride, out_stride, (hipStream_t)stream_);
-}
-
-// mlp_gemm_dgrad with the weight as stored, w (m,k) row-major: no transposed copy is needed
-MLP_API int mlp_gemm_dgrad_nt(int b, int m, int k, int r, const float *w, int mode,
-                              const float *dy, const float *y, const float *dz,
-                              const float *scale, const float *shift, const float *mean,
-                              const float *invstd, const float *coef, float *dx, void *stream_) {
-  if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
-  const size_t in_stride = (size_t)m * r, out_stride = (size_t)k * r;
-  if (mode == OP_DIRECT) {
-    OperandB op = {dy, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return launch_nn<OP_DIRECT, true>(b, k, m, r, w, k, op, dx, in_stride, out_stride,
-                                      (hipStream_t)stream_);
-  }
-  OperandB op = {y, dz, scale, shift, mean, invstd, coef};
-  return launch_nn<OP_DY, true>(b, k, m, r, w, k, op, dx, in_stride, out_stride,
-                                (hipStream_t)stream_);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (dy->mode == OP_DIRECT)
+    return launch_nn<OP_DIRECT, true>(b, k, m, r, w, k, op, dx, in_stride, out_stride, stream);
+  if (dy->mode == OP_DY)
+    return launch_nn<OP_DY, true>(b, k, m, r, w, k, op, dx, in_stride, out_stride, stream);
+  return launch_nn<OP_POOLDY, true>(b, k, m, r, w, k, op, dx, in_stride, out_stride, stream);
 }
 
 static bool wgrad_direct_ok(int b, int m, int k, int r, int pmode, int qmode);
@@ -1548,27 +1511,28 @@ static int wgrad_direct_r_per_slice(int b, int m, int k, int r);
 // Both backward GEMMs of a small layer in ONE launch (gemm_small_backward_pair_kernel): 1 when
 // the layer is in the small regime of both kernels.
 MLP_API int mlp_gemm_backward_small_supported(int b, int m, int k, int r, int pmode, int qmode) {
-  const char *env = getenv("MLP_SMALL_GEMM_COLS");
-  const long long small_cols = env ? atoll(env) : 16384;
-  return b > 0 && m > 0 && k > 0 && (long long)b * r <= small_cols &&
+  return b > 0 && m > 0 && k > 0 && (long long)b * r <= small_gemm_cols() &&
          wgrad_direct_ok(b, m, k, r, pmode, qmode);
 }
 
-// dq (b,k,r) = w^T P[b] and dw (m,k) = sum_b P[b] Q[b]^T; P = dy (pmode 0) or formed on the fly
-// from (y, dz) and the BatchNorm / ReLU backward constants (pmode 2); Q = x (qmode 0) or
-// relu(x*xscale + xshift) (qmode 1).  dq == NULL: the weight gradient alone.
+// dq (b,k,r) = w^T P[b] and dw (m,k) = sum_b P[b] Q[b]^T; P = dy (mode 0 or 2), Q = x (mode 0 or 1).
+// dq == NULL: the weight gradient alone.  img_t: the TRANSPOSED weight also as the bf16 image
+// mlp_weight_images_build made of it (the [plane][k][m] order), read by the data-gradient half when
+// the gradient operand is given (mode 0); same results bit for bit.
 // workspace: mlp_gemm_wgrad_workspace_floats(b, m, k, r) floats.
-static int backward_small_impl(int b, int m, int k, int r, const float *w, const void *wt_img, int pmode,
-                               const float *dy_or_y, const float *dz, const float *scale,
-                               const float *shift, const float *mean, const float *invstd,
-                               const float *coef, int qmode, const float *x,
-                               const float *xscale, const float *xshift, float *dq, float *dw,
-                               float *workspace, void *stream_) {
-  if (!mlp_gemm_backward_small_supported(b, m, k, r, pmode, qmode)) return (int)hipErrorInvalidValue;
+MLP_API int mlp_gemm_backward_small(int b, int m, int k, int r, const float *w, const void *img_t,
+                                    const MlpOperand *dy, const MlpOperand *x, float *dq, float *dw,
+                                    float *workspace, void *stream_) {
+  if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
+  OperandB P, Q;
+  int rc = operand_from_abi(dy, op_bit(OP_DIRECT) | op_bit(OP_DY), r, &P);
+  if (!rc) rc = operand_from_abi(x, op_bit(OP_DIRECT) | op_bit(OP_BNRELU), r, &Q);
+  if (rc) return rc;
+  const int pmode = dy->mode, qmode = x->mode;
+  if (!mlp_gemm_backward_small_supported(b, m, k, r, pmode, qmode) ||
+      (img_t && !mlp_gemm_image_supported(b, r)))
+    return (int)hipErrorInvalidValue;
   hipStream_t stream = (hipStream_t)stream_;
-  OperandB P = {dy_or_y, dz, scale, shift, mean, invstd, coef};
-  if (pmode == OP_DIRECT) P = OperandB{dy_or_y, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  OperandB Q = {x, nullptr, xscale, xshift, nullptr, nullptr, nullptr};
   SmallPairArgs t;
   t.m = m; t.k = k; t.r = r;
   t.dgx = pn2_ceil_div(r, 64); t.dgy = pn2_ceil_div(k, 64);
@@ -1578,12 +1542,12 @@ static int backward_small_impl(int b, int m, int k, int r, const float *w, const
   t.wkx = pn2_ceil_div(k, 64); t.wmy = pn2_ceil_div(m, 64);
   t.w = w; t.dq = dq; t.part = workspace;
   // the data-gradient half reads W^T: rows k, reduction over m
-  t.wt_img = AImage{reinterpret_cast<const unsigned short *>(wt_img), pad64(m), (size_t)pad64(k) * pad64(m)};
+  t.wt_img = AImage{reinterpret_cast<const unsigned short *>(img_t), pad64(m), (size_t)pad64(k) * pad64(m)};
   const int nw = t.wkx * t.wmy * b * t.slices;
   const dim3 grid((unsigned)(t.nd + nw));
 #define PAIR(PM, QM, X6D)                                                                        \
   hipLaunchKernelGGL((gemm_small_backward_pair_kernel<PM, QM, X6D>), grid, dim3(256), 0, stream, t, P, Q)
-  if (pmode == OP_DIRECT && wt_img != nullptr) {
+  if (pmode == OP_DIRECT && img_t != nullptr) {
     if (qmode == OP_DIRECT)
       hipLaunchKernelGGL((gemm_small_backward_pair_kernel<OP_DIRECT, OP_DIRECT, true, true>), grid, dim3(256), 0, stream, t, P, Q);
     else
@@ -1594,60 +1558,9 @@ static int backward_small_impl(int b, int m, int k, int r, const float *w, const
   else if (qmode == OP_DIRECT) PAIR(OP_DY, OP_DIRECT, false);
   else PAIR(OP_DY, OP_BNRELU, false);
 #undef PAIR
-  const int rc = pn2_launch_status();
+  rc = pn2_launch_status();
   if (rc) return rc;
   return mlp_reduce_weight_partials(m * k, b * t.slices, workspace, dw, stream);
-}
-
-MLP_API int mlp_gemm_backward_small(int b, int m, int k, int r, const float *w, int pmode,
-                                    const float *dy_or_y, const float *dz, const float *scale,
-                                    const float *shift, const float *mean, const float *invstd,
-                                    const float *coef, int qmode, const float *x,
-                                    const float *xscale, const float *xshift, float *dq, float *dw,
-                                    float *workspace, void *stream_) {
-  return backward_small_impl(b, m, k, r, w, nullptr, pmode, dy_or_y, dz, scale, shift, mean, invstd, coef,
-                             qmode, x, xscale, xshift, dq, dw, workspace, stream_);
-}
-
-// mlp_gemm_backward_small with the TRANSPOSED weight also given as the bf16 image
-// mlp_weight_images_build made of it (img_t: the [plane][k][m] order), read by the data-gradient
-// half when the gradient operand is given (pmode 0); same results bit for bit
-MLP_API int mlp_gemm_backward_small_img(int b, int m, int k, int r, const float *w, const void *img_t,
-                                        int pmode, const float *dy_or_y, const float *dz,
-                                        const float *scale, const float *shift, const float *mean,
-                                        const float *invstd, const float *coef, int qmode,
-                                        const float *x, const float *xscale, const float *xshift,
-                                        float *dq, float *dw, float *workspace, void *stream_) {
-  if (!img_t || !mlp_gemm_image_supported(b, r)) return (int)hipErrorInvalidValue;
-  return backward_small_impl(b, m, k, r, w, img_t, pmode, dy_or_y, dz, scale, shift, mean, invstd, coef,
-                             qmode, x, xscale, xshift, dq, dw, workspace, stream_);
-}
-
-MLP_API int mlp_gemm_dgrad_pooled_nt(int b, int m, int k, int groups, int ns, const float *w,
-                                     const float *y, const float *dpooled, const int *argmax,
-                                     const float *scale, const float *shift, const float *mean,
-                                     const float *invstd, const float *coef, float *dx,
-                                     void *stream_) {
-  if (b <= 0 || m <= 0 || k <= 0 || groups <= 0 || ns <= 0) return 0;
-  const int r = groups * ns;
-  const size_t in_stride = (size_t)m * r, out_stride = (size_t)k * r;
-  OperandB op = {y, dpooled, scale, shift, mean, invstd, coef, argmax, ns, groups};
-  return launch_nn<OP_POOLDY, true>(b, k, m, r, w, k, op, dx, in_stride, out_stride,
-                                    (hipStream_t)stream_);
-}
-
-// the same for the pooled last layer of an SA module: dy from (y, dpooled, argmax) on the fly
-MLP_API int mlp_gemm_dgrad_pooled(int b, int m, int k, int groups, int ns, const float *wt,
-                                  const float *y, const float *dpooled, const int *argmax,
-                                  const float *scale, const float *shift, const float *mean,
-                                  const float *invstd, const float *coef, float *dx,
-                                  void *stream_) {
-  if (b <= 0 || m <= 0 || k <= 0 || groups <= 0 || ns <= 0) return 0;
-  const int r = groups * ns;
-  const size_t in_stride = (size_t)m * r, out_stride = (size_t)k * r;
-  OperandB op = {y, dpooled, scale, shift, mean, invstd, coef, argmax, ns, groups};
-  return launch_nn<OP_POOLDY>(b, k, m, r, wt, m, op, dx, in_stride, out_stride,
-                              (hipStream_t)stream_);
 }
 
 // K is covered by column tiles of 256 / 192 / 128 / 64 (largest first), M by 64-row tiles, and
@@ -1703,12 +1616,10 @@ static int wgrad_direct_r_per_slice(int b, int m, int k, int r) {
 }
 
 static int wgrad_run(int b, int m, int k, int r, int pmode, const OperandB &P, int qmode,
-                     const float *x, const float *xscale, const float *xshift, float *dw,
-                     float *workspace, hipStream_t stream) {
+                     const OperandB &Q, float *dw, float *workspace, hipStream_t stream) {
   if (wgrad_direct_ok(b, m, k, r, pmode, qmode)) {
     const int per = wgrad_direct_r_per_slice(b, m, k, r);
     const int slices = (r + per - 1) / per;
-    OperandB Q = {x, nullptr, xscale, xshift, nullptr, nullptr, nullptr};
     const dim3 grid(pn2_ceil_div(k, 64), pn2_ceil_div(m, 64), b * slices);
 #define WGD(PM, QM)                                                                              \
   hipLaunchKernelGGL((gemm_wgrad_direct_kernel<PM, QM>), grid, dim3(256), 0, stream, m, k, r, per, \
@@ -1724,7 +1635,6 @@ static int wgrad_run(int b, int m, int k, int r, int pmode, const OperandB &P, i
   }
   const int per = wgrad_r_per_slice(b, m, k, r);
   const int slices = (r + per - 1) / per;
-  OperandB Q = {x, nullptr, xscale, xshift, nullptr, nullptr, nullptr};
   const size_t ps = (size_t)m * r, qs = (size_t)k * r;
 #define WG(PM, QM)                                                                              \
   do {                                                                                          \
@@ -1757,29 +1667,14 @@ static int wgrad_run(int b, int m, int k, int r, int pmode, const OperandB &P, i
   return mlp_reduce_weight_partials(m * k, b * slices, workspace, dw, stream);
 }
 
-// dW (m x k) = sum_b dY[b] * X[b]^T; dY given (pmode 0) or on the fly (pmode 2, from y/dz);
-// X given (qmode 0) or relu(bn(Yprev)) (qmode 1, via xscale/xshift).
-MLP_API int mlp_gemm_wgrad(int b, int m, int k, int r, int pmode, const float *dy, const float *y,
-                           const float *dz, const float *scale, const float *shift,
-                           const float *mean, const float *invstd, const float *coef, int qmode,
-                           const float *x, const float *xscale, const float *xshift, float *dw,
-                           float *workspace, void *stream_) {
+// dW (m x k) = sum_b dY[b] * X[b]^T; dY given (mode 0) or formed on the fly (modes 2 / 3);
+// X given (mode 0) or relu(bn(Yprev)) (mode 1).
+MLP_API int mlp_gemm_wgrad(int b, int m, int k, int r, const MlpOperand *dy, const MlpOperand *x,
+                           float *dw, float *workspace, void *stream_) {
   if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
-  OperandB P = pmode == OP_DIRECT ? OperandB{dy, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}
-                                  : OperandB{y, dz, scale, shift, mean, invstd, coef};
-  return wgrad_run(b, m, k, r, pmode == OP_DIRECT ? OP_DIRECT : OP_DY, P, qmode, x, xscale, xshift,
-                   dw, workspace, (hipStream_t)stream_);
-}
-
-// the same for the pooled last layer: dY from (y, dpooled, argmax) on the fly
-MLP_API int mlp_gemm_wgrad_pooled(int b, int m, int k, int groups, int ns, const float *y,
-                                  const float *dpooled, const int *argmax, const float *scale,
-                                  const float *shift, const float *mean, const float *invstd,
-                                  const float *coef, int qmode, const float *x,
-                                  const float *xscale, const float *xshift, float *dw,
-                                  float *workspace, void *stream_) {
-  if (b <= 0 || m <= 0 || k <= 0 || groups <= 0 || ns <= 0) return 0;
-  OperandB P = {y, dpooled, scale, shift, mean, invstd, coef, argmax, ns, groups};
-  return wgrad_run(b, m, k, groups * ns, OP_POOLDY, P, qmode, x, xscale, xshift, dw, workspace,
-                   (hipStream_t)stream_);
+  OperandB P, Q;
+  int rc = operand_from_abi(dy, op_bit(OP_DIRECT) | op_bit(OP_DY) | op_bit(OP_POOLDY), r, &P);
+  if (!rc) rc = operand_from_abi(x, op_bit(OP_DIRECT) | op_bit(OP_BNRELU), r, &Q);
+  if (rc) return rc;
+  return wgrad_run(b, m, k, r, dy->mode, P, x->mode, Q, dw, workspace, (hipStream_t)stream_);
 }

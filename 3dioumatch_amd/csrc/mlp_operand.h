@@ -4,6 +4,7 @@
 // mlp_bwd_fused.hip.
 #pragma once
 #include "common.h"
+#include "../../include/mlp_hip.h"
 
 namespace {
 
@@ -28,6 +29,27 @@ struct OperandB {
 };
 
 constexpr bool is_dy(int mode) { return mode == OP_DY || mode == OP_POOLDY; }
+
+// The C ABI's operand record (include/mlp_hip.h, which says what every mode reads) as the kernels
+// take it.  `modes`: bit i set = the entry point takes mode i; r: the columns per cloud of the
+// call.  hipErrorInvalidValue when the mode is not among them or one of its fields is missing.
+constexpr unsigned op_bit(int mode) { return 1u << mode; }
+
+inline int operand_from_abi(const MlpOperand *a, unsigned modes, int r, OperandB *op) {
+  if (!a || a->mode < OP_DIRECT || a->mode > OP_LIN4 || !(modes & op_bit(a->mode)))
+    return (int)hipErrorInvalidValue;
+  const int mode = a->mode;
+  bool ok = a->x != nullptr;
+  if (mode != OP_DIRECT) ok = ok && a->scale && a->shift;
+  if (is_dy(mode)) ok = ok && a->dz && a->mean && a->invstd && a->coef;
+  if (mode == OP_POOLDY)
+    ok = ok && a->argmax && a->ns > 0 && a->groups > 0 && (long long)a->groups * a->ns == r;
+  if (mode == OP_LIN4) ok = ok && a->lin_w;
+  if (!ok) return (int)hipErrorInvalidValue;
+  *op = OperandB{a->x, a->dz, a->scale, a->shift, a->mean, a->invstd, a->coef, a->argmax,
+                 a->ns, a->groups, a->lin_w};
+  return 0;
+}
 
 // OP_LIN4: the output of a 4 -> rows first layer is never stored; whoever needs row k at column
 // n recomputes y[k][n] = W[k] . x[:, n] with THIS function (one fixed order, so that the ReLU

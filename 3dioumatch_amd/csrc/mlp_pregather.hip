@@ -271,12 +271,13 @@ MLP_API int mlp_pregather_forward(int b, int c, int n, int m, int ns, const floa
   return pn2_launch_status();
 }
 
-MLP_API int mlp_pregather_backward(int b, int c, int n, int m, int ns, const float *y,
-                                   const float *dz, const float *scale, const float *shift,
-                                   const float *mean, const float *invstd, const float *coef,
+MLP_API int mlp_pregather_backward(int b, int c, int n, int m, int ns, const MlpOperand *dy,
                                    const unsigned *inverse, float *dz_ext, void *stream_) {
+  if (b <= 0 || c <= 0 || n <= 0 || m <= 0 || ns <= 0) return 0;
+  OperandB op;
+  const int rc = operand_from_abi(dy, op_bit(OP_DY), m * ns, &op);
+  if (rc) return rc;
   if (!pregather_shape_ok(b, c, n, m, ns)) return (int)hipErrorInvalidValue;
-  OperandB op = {y, dz, scale, shift, mean, invstd, coef, nullptr, 0, 0, nullptr};
   const dim3 grid(c, b);
   hipStream_t stream = (hipStream_t)stream_;
   int chunk = 4;

@@ -5,6 +5,7 @@ No reference counterpart: the reference runs nn.BatchNorm2d / nn.ReLU / F.max_po
 (pointnet2/pytorch_utils.py:14-124, pointnet2/pointnet2_modules.py:256-262).
 """
 import contextlib
+import ctypes
 import os
 
 import torch
@@ -171,6 +172,50 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+MlpOperand = _L.MlpOperand  # the record of one GEMM operand (field order == include/mlp_hip.h)
+
+
+def _operand(mode, ns=0, groups=0, **tensors):
+    """The record of one GEMM operand (include/mlp_hip.h says what each mode reads): field name ->
+    tensor or None.  The record holds the tensors, so they live as long as it does -- keep it until
+    the call it is passed to has returned."""
+    op = MlpOperand(mode=mode, ns=int(ns), groups=int(groups))
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if name != "argmax":
+            _f32c(t, "operand field " + name)
+        elif t.dtype != torch.int32 or not t.is_contiguous() or not t.is_cuda:
+            raise RuntimeError("argmax must be a contiguous int32 GPU tensor")
+        setattr(op, name, t.data_ptr())
+    op.tensors = tensors
+    return op
+
+
+def _grad_operand(dy=None, fly=None, pooled=None):
+    """The gradient operand of a layer's backward GEMMs: dy (B,M,...) given (mode 0), or formed on the
+    fly from fly = (y, dz, scale, shift, mean, invstd, coef) (mode 2) or from pooled = (y (B,M,m,ns),
+    dpooled, argmax, scale, shift, mean, invstd, coef) (mode 3)."""
+    if dy is not None:
+        return _operand(0, x=dy)
+    if pooled is not None:
+        y, dpooled, argmax, scale, shift, mean, invstd, coef = pooled
+        return _operand(3, x=y, dz=dpooled, scale=scale, shift=shift, mean=mean, invstd=invstd,
+                        coef=coef, argmax=argmax, ns=y.shape[3], groups=y.shape[2])
+    y, dz, scale, shift, mean, invstd, coef = fly
+    return _operand(2, x=y, dz=dz, scale=scale, shift=shift, mean=mean, invstd=invstd, coef=coef)
+
+
+def _input_operand(x, xcoeff=None, xstats=None, lin_w=None):
+    """The input operand of a layer's GEMMs: x itself (mode 0), relu(bn(x)) via xcoeff = (scale, shift)
+    (mode 1; xstats = (mean, invstd, ...) of that BatchNorm where the kernel wants them), or with lin_w
+    the recomputed output of the virtual 4 -> 64 layer whose input x is (mode 4)."""
+    mode = 4 if lin_w is not None else (0 if xcoeff is None else 1)
+    scale, shift = xcoeff if xcoeff is not None else (None, None)
+    mean, invstd = xstats[:2] if (mode != 0 and xstats is not None) else (None, None)
+    return _operand(mode, x=x, scale=scale, shift=shift, mean=mean, invstd=invstd, lin_w=lin_w)
+
+
 class WeightImages(object):
     """bf16 images of a set of weights for the SMALL layers' kernels (include/mlp_hip.h
     mlp_weight_images_build): the exact three-term split of every weight, written once per
@@ -182,7 +227,6 @@ class WeightImages(object):
     writes them through raw pointers -- there is no version counter to key a cache on)."""
 
     def __init__(self, weights):
-        import ctypes
         ws = [w for w in weights if w.is_cuda and w.dtype == torch.float32 and w.dim() >= 2
               and w.is_contiguous()]
         self.entries = {}
@@ -254,18 +298,12 @@ def gemm_forward(w, x, coeff=None):
     r = x.numel() // (b * k)
     m = w.shape[0]
     y = torch.empty((b, m) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-    scale, shift = coeff if coeff is not None else (None, None)
     image = _image_of(w, b, r)
-    if image is not None:
-        with torch.cuda.device(x.device):
-            _L.check(_lib.mlp_gemm_forward_img(b, m, k, r, w.data_ptr(), image[0], x.data_ptr(),
-                                               0 if coeff is None else 1, _ptr(scale), _ptr(shift),
-                                               y.data_ptr(), _stream(x)), "mlp_gemm_forward_img")
-        return y
+    op = _input_operand(x, coeff)
     with torch.cuda.device(x.device):
-        _L.check(_lib.mlp_gemm_forward(b, m, k, r, w.data_ptr(), x.data_ptr(),
-                                       0 if coeff is None else 1, _ptr(scale), _ptr(shift),
-                                       y.data_ptr(), _stream(x)), "mlp_gemm_forward")
+        _L.check(_lib.mlp_gemm_forward(b, m, k, r, w.data_ptr(), image[0] if image else None,
+                                       ctypes.byref(op), y.data_ptr(), None, _stream(x)),
+                 "mlp_gemm_forward")
     return y
 
 
@@ -279,7 +317,6 @@ def gemm_forward_bn(w, x, coeff, gamma, beta, running_mean, running_var, momentu
     and the caller pools with bn_relu_pool.
     store=False (pool=True and forward_pool_supported only): y is None -- the raw output is not
     stored at all (its backward then runs from the Gram matrix of its input, pool_gram_backward)."""
-    import ctypes
     _f32c(x, "x"); _f32c(w, "w")
     b, k = x.shape[0], x.shape[1]
     r = x.numel() // (b * k)
@@ -310,10 +347,10 @@ def gemm_forward_bn(w, x, coeff, gamma, beta, running_mean, running_var, momentu
                                                       gamma.data_ptr(), ext.data_ptr(), _stream(x)),
                      "mlp_gemm_forward_stats_pool")
         else:
-            _L.check(_lib.mlp_gemm_forward_stats(b, m, k, r, w.data_ptr(), x.data_ptr(),
-                                                 0 if coeff is None else 1, _ptr(scale),
-                                                 _ptr(shift), y.data_ptr(), pairs.data_ptr(),
-                                                 _stream(x)), "mlp_gemm_forward_stats")
+            op = _input_operand(x, coeff)
+            _L.check(_lib.mlp_gemm_forward(b, m, k, r, w.data_ptr(), None, ctypes.byref(op),
+                                           y.data_ptr(), pairs.data_ptr(), _stream(x)),
+                     "mlp_gemm_forward(pairs)")
         rm = running_mean.data_ptr() if running_mean is not None else None
         rv = running_var.data_ptr() if running_var is not None else None
         _L.check(_lib.mlp_bn_finalize_pairs(m, parts, cols.value, pairs.data_ptr(),
@@ -377,29 +414,14 @@ def gemm_dgrad(w, dy=None, fly=None, pooled=None):
     and dy is formed on the fly."""
     m, k = w.shape
     _f32c(w, "w")  # read as stored: the kernels take A transposed (no w.t().contiguous() copy)
-    src = dy if dy is not None else (fly[0] if fly is not None else pooled[0])
+    op = _grad_operand(dy, fly, pooled)
+    src = op.tensors["x"]  # dy, or the y it is formed from: (B,M,...) either way
     b = src.shape[0]
     r = src.numel() // (b * m)
     dx = torch.empty((b, k) + tuple(src.shape[2:]), dtype=torch.float32, device=src.device)
     with torch.cuda.device(src.device):
-        if dy is not None:
-            _f32c(dy, "dy")
-            rc = _lib.mlp_gemm_dgrad_nt(b, m, k, r, w.data_ptr(), 0, dy.data_ptr(), None, None, None,
-                                     None, None, None, None, dx.data_ptr(), _stream(src))
-        elif pooled is not None:
-            y, dpooled, argmax, scale, shift, mean, invstd, coef = pooled
-            rc = _lib.mlp_gemm_dgrad_pooled_nt(b, m, k, y.shape[2], y.shape[3], w.data_ptr(),
-                                            y.data_ptr(), dpooled.data_ptr(), argmax.data_ptr(),
-                                            scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
-                                            invstd.data_ptr(), coef.data_ptr(), dx.data_ptr(),
-                                            _stream(src))
-        else:
-            y, dz, scale, shift, mean, invstd, coef = fly
-            rc = _lib.mlp_gemm_dgrad_nt(b, m, k, r, w.data_ptr(), 2, None, y.data_ptr(),
-                                     dz.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                     mean.data_ptr(), invstd.data_ptr(), coef.data_ptr(),
-                                     dx.data_ptr(), _stream(src))
-        _L.check(rc, "mlp_gemm_dgrad")
+        _L.check(_lib.mlp_gemm_dgrad(b, m, k, r, w.data_ptr(), ctypes.byref(op), dx.data_ptr(),
+                                     _stream(src)), "mlp_gemm_dgrad")
     return dx
 
 
@@ -453,31 +475,13 @@ def gemm_wgrad(m, k, x, xcoeff=None, dy=None, fly=None, pooled=None):
     b = x.shape[0]
     r = x.numel() // (b * k)
     dw = torch.empty((m, k), dtype=torch.float32, device=x.device)
-    xs, xh = xcoeff if xcoeff is not None else (None, None)
+    p, q = _grad_operand(dy, fly, pooled), _input_operand(x, xcoeff)
     with torch.cuda.device(x.device):
         ws = torch.empty(max(int(_lib.mlp_gemm_wgrad_workspace_floats(b, m, k, r)), 1),
                          dtype=torch.float32, device=x.device)
         _keep_until_flush(ws, dw)
-        if dy is not None:
-            rc = _lib.mlp_gemm_wgrad(b, m, k, r, 0, dy.data_ptr(), None, None, None, None, None,
-                                     None, None, 0 if xcoeff is None else 1, x.data_ptr(),
-                                     _ptr(xs), _ptr(xh), dw.data_ptr(), ws.data_ptr(), _stream(x))
-        elif pooled is not None:
-            y, dpooled, argmax, scale, shift, mean, invstd, coef = pooled
-            rc = _lib.mlp_gemm_wgrad_pooled(b, m, k, y.shape[2], y.shape[3], y.data_ptr(),
-                                            dpooled.data_ptr(), argmax.data_ptr(),
-                                            scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
-                                            invstd.data_ptr(), coef.data_ptr(),
-                                            0 if xcoeff is None else 1, x.data_ptr(), _ptr(xs),
-                                            _ptr(xh), dw.data_ptr(), ws.data_ptr(), _stream(x))
-        else:
-            y, dz, scale, shift, mean, invstd, coef = fly
-            rc = _lib.mlp_gemm_wgrad(b, m, k, r, 2, None, y.data_ptr(), dz.data_ptr(),
-                                     scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
-                                     invstd.data_ptr(), coef.data_ptr(),
-                                     0 if xcoeff is None else 1, x.data_ptr(), _ptr(xs), _ptr(xh),
-                                     dw.data_ptr(), ws.data_ptr(), _stream(x))
-        _L.check(rc, "mlp_gemm_wgrad")
+        _L.check(_lib.mlp_gemm_wgrad(b, m, k, r, ctypes.byref(p), ctypes.byref(q), dw.data_ptr(),
+                                     ws.data_ptr(), _stream(x)), "mlp_gemm_wgrad")
     return dw
 
 
@@ -499,24 +503,17 @@ def gemm_backward_fused(w, x, xcoeff=None, fly=None, pooled=None, xstats=None, n
     _f32c(w, "w"); _f32c(x, "x")
     b = x.shape[0]
     r = x.numel() // (b * (4 if lin_w is not None else k))
-    if pooled is not None:
-        y, dz, argmax, scale, shift, mean, invstd, coef = pooled
-        pmode, ns = 3, y.shape[3]
-    else:
-        y, dz, scale, shift, mean, invstd, coef = fly
-        argmax, pmode, ns = None, 2, 0
-    qmode = 4 if lin_w is not None else (0 if xcoeff is None else 1)
-    if not _lib.mlp_gemm_backward_fused_supported(b, m, k, r, pmode, qmode, ns):
+    p, q = _grad_operand(fly=fly, pooled=pooled), _input_operand(x, xcoeff, xstats, lin_w)
+    qmode = q.mode
+    if not _lib.mlp_gemm_backward_fused_supported(b, m, k, r, p.mode, qmode, p.ns):
         return None
     if not need_dx and (m, k) != (128, 259):  # the weight-gradient-only form exists for this shape
         return None
     if qmode != 0 and xstats is None:
         raise RuntimeError("xstats=(mean, invstd, gamma, training) is required with xcoeff")
-    xs, xh = xcoeff if xcoeff is not None else (None, None)
-    xmean, xinv, xgamma, xtraining = xstats if qmode != 0 else (None, None, None, False)
+    _, xinv, xgamma, xtraining = xstats if qmode != 0 else (None, None, None, False)
     parts = int(_lib.mlp_gemm_backward_fused_stats_parts(b, m, k, r)) if qmode != 0 else 0
     if lin_w is not None:
-        _f32c(lin_w, "lin_w")
         if parts <= 0:
             raise RuntimeError("gemm_backward_fused(lin_w): no partials for this shape")
         dx = torch.empty((parts, k, 4), dtype=torch.float32, device=x.device)  # the gated sums' partials
@@ -529,12 +526,9 @@ def gemm_backward_fused(w, x, xcoeff=None, fly=None, pooled=None, xstats=None, n
                          dtype=torch.float32, device=x.device)
         _keep_until_flush(ws, dw)
         sp = torch.empty((k, parts, 2), dtype=torch.float32, device=x.device) if parts else None
-        _L.check(_lib.mlp_gemm_backward_fused(b, m, k, r, w.data_ptr(), pmode, y.data_ptr(),
-                                              dz.data_ptr(), _ptr(argmax), ns, scale.data_ptr(),
-                                              shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                              coef.data_ptr(), qmode, x.data_ptr(), _ptr(xs),
-                                              _ptr(xh), _ptr(xmean), _ptr(xinv), _ptr(lin_w), _ptr(dx),
-                                              dw.data_ptr(), ws.data_ptr(), _ptr(sp), _stream(x)),
+        _L.check(_lib.mlp_gemm_backward_fused(b, m, k, r, w.data_ptr(), ctypes.byref(p),
+                                              ctypes.byref(q), _ptr(dx), dw.data_ptr(),
+                                              ws.data_ptr(), _ptr(sp), _stream(x)),
                  "mlp_gemm_backward_fused")
         if parts:
             small = torch.empty((5, k), dtype=torch.float32, device=x.device)
@@ -623,14 +617,8 @@ def gemm_backward_small(w, x, xcoeff=None, dy=None, fly=None, need_dx=True):
     qmode = 0 if xcoeff is None else 1
     if not _lib.mlp_gemm_backward_small_supported(b, m, k, r, pmode, qmode):
         return None
-    _f32c(w, "w"); _f32c(x, "x")
-    if dy is not None:
-        _f32c(dy, "dy")
-        p0, pdz, sc, sh, mean, invstd, coef = dy, None, None, None, None, None, None
-    else:
-        p0, pdz, sc, sh, mean, invstd, coef = fly
-        _f32c(p0, "y"); _f32c(pdz, "dz")
-    xs, xh = xcoeff if xcoeff is not None else (None, None)
+    _f32c(w, "w")
+    p, q = _grad_operand(dy, fly), _input_operand(x, xcoeff)
     dx = torch.empty_like(x) if need_dx else None
     dw = torch.empty((m, k), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
@@ -638,17 +626,10 @@ def gemm_backward_small(w, x, xcoeff=None, dy=None, fly=None, need_dx=True):
                          dtype=torch.float32, device=x.device)
         _keep_until_flush(ws, dw)
         image = _image_of(w, b, r) if (pmode == 0 and need_dx) else None
-        if image is not None:
-            _L.check(_lib.mlp_gemm_backward_small_img(
-                b, m, k, r, w.data_ptr(), image[1], pmode, p0.data_ptr(), _ptr(pdz), _ptr(sc), _ptr(sh),
-                _ptr(mean), _ptr(invstd), _ptr(coef), qmode, x.data_ptr(), _ptr(xs), _ptr(xh), _ptr(dx),
-                dw.data_ptr(), ws.data_ptr(), _stream(x)), "mlp_gemm_backward_small_img")
-            return dx, dw
-        _L.check(_lib.mlp_gemm_backward_small(b, m, k, r, w.data_ptr(), pmode, p0.data_ptr(),
-                                              _ptr(pdz), _ptr(sc), _ptr(sh), _ptr(mean),
-                                              _ptr(invstd), _ptr(coef), qmode, x.data_ptr(),
-                                              _ptr(xs), _ptr(xh), _ptr(dx), dw.data_ptr(),
-                                              ws.data_ptr(), _stream(x)), "mlp_gemm_backward_small")
+        _L.check(_lib.mlp_gemm_backward_small(b, m, k, r, w.data_ptr(), image[1] if image else None,
+                                              ctypes.byref(p), ctypes.byref(q), _ptr(dx),
+                                              dw.data_ptr(), ws.data_ptr(), _stream(x)),
+                 "mlp_gemm_backward_small")
     return dx, dw
 
 
@@ -719,7 +700,6 @@ def lin4_supported(w0, w1, x):
 def gemm_forward_bn_lin4(w, x4, w1, coeff1, gamma, beta, running_mean, running_var, momentum, eps):
     """gemm_forward_bn for the second layer (w (64,64)) when the first (w1 (64,4), BatchNorm
     coefficients coeff1 = (scale, shift)) is virtual: its activated output is recomputed from x4."""
-    import ctypes
     _f32c(x4, "x4"); _f32c(w, "w"); _f32c(w1, "w1")
     b = x4.shape[0]
     r = x4.numel() // (b * 4)
@@ -772,7 +752,6 @@ def chain_lin4_forward(x4, w0, coeff0, layer1, layer2, store=True, store_last=Tr
     w1, g1, be1, rm1, rv1, mom1, eps1 = layer1
     w2, g2, be2, rm2, rv2, mom2, eps2 = layer2
     _f32c(w1, "w1"); _f32c(w2, "w2")
-    import ctypes
     cols = ctypes.c_int(0)
     parts = int(_lib.mlp_chain_lin4_parts(b, r, 128, ns, ctypes.byref(cols)))
     if parts <= 0:
@@ -936,8 +915,8 @@ def pregather_forward(z_ext, idx, n, stats=None):
 def pregather_backward(fly, inverse, n):
     """dz_ext (B, c, n + m) from fly = (y, dz, scale, shift, mean, invstd, coef) as gemm_dgrad
     takes it and the inverse index of the layer's idx (_ext.group_inverse)."""
-    y, dz, scale, shift, mean, invstd, coef = fly
-    _f32c(y, "y"); _f32c(dz, "dz")
+    op = _grad_operand(fly=fly)
+    y = op.tensors["x"]
     b, c, m, ns = y.shape
     if (inverse.dtype != torch.int32 or not inverse.is_contiguous() or inverse.device != y.device
             or tuple(inverse.shape) != (b, int(_lib.pn2_group_inverse_entries(m, ns)))):
@@ -945,9 +924,7 @@ def pregather_backward(fly, inverse, n):
                            % (m, ns, y.device))
     out = torch.empty((b, c, n + m), dtype=torch.float32, device=y.device)
     with torch.cuda.device(y.device):
-        _L.check(_lib.mlp_pregather_backward(b, c, n, m, ns, y.data_ptr(), dz.data_ptr(),
-                                             scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
-                                             invstd.data_ptr(), coef.data_ptr(), inverse.data_ptr(),
+        _L.check(_lib.mlp_pregather_backward(b, c, n, m, ns, ctypes.byref(op), inverse.data_ptr(),
                                              out.data_ptr(), _stream(y)), "mlp_pregather_backward")
     return out
 

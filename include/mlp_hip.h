@@ -72,7 +72,7 @@ int mlp_bn_relu_backward(int b, int c, int r, int training, const float *y, cons
 
 /* replaces the autograd backward of max_pool2d + ReLU + BatchNorm2d of the last layer
  * (pointnet2_modules.py:256-262): dpooled (b,c,m) -> dy (b,c,m,ns), dgamma, dbeta.  dy == NULL:
- * only dgamma, dbeta and coef are produced (dy is then formed inside mlp_gemm_*_pooled). */
+ * only dgamma, dbeta and coef are produced (dy is then formed inside the GEMMs: MlpOperand mode 3). */
 int mlp_bn_relu_pool_backward(int b, int c, int m, int ns, int training, const float *y,
                               const float *dpooled, const int *argmax, const float *ymax,
                               const float *gamma, const float *scale, const float *shift,
@@ -92,10 +92,46 @@ int mlp_bn_relu_backward_stats(int b, int c, int r, int training, const float *y
  * X (b,k,r), W (m,k) row-major, Y (b,m,r).  Replaces nn.Conv2d(kernel 1x1, no bias) of a
  * shared-MLP layer (pytorch_utils.py:70-124, built at :14-39) and its autograd backward. */
 
-/* forward: y = W * x, where x is the given tensor (mode 0) or relu(x*scale[k] + shift[k])
- * (mode 1: the previous layer's BatchNorm+ReLU applied on the fly, pytorch_utils.py:108-124) */
-int mlp_gemm_forward(int b, int m, int k, int r, const float *w, const float *x, int mode,
-                     const float *scale, const float *shift, float *y, void *stream);
+/* One operand of these GEMMs: a tensor, or a tensor transformed on its way into the kernel (the
+ * BatchNorm / ReLU algebra of pytorch_utils.py:108-124 and its backward; csrc/mlp_operand.h).
+ * This comment is the one place that says which fields a mode reads; every other field is ignored
+ * (leave it 0).  An entry point that is given a mode it does not take, or a mode whose fields are
+ * not all there (a NULL vector; ns, groups <= 0 or groups * ns != r for mode 3), returns
+ * hipErrorInvalidValue before anything is launched.
+ *   mode 0  the tensor x (b, rows, r) itself
+ *   mode 1  relu(x*scale[row] + shift[row]): x is the raw output of the layer below, (scale, shift)
+ *           that layer's BatchNorm; mlp_gemm_backward_fused also reads mean / invstd of that layer
+ *   mode 2  dy = BatchNorm / ReLU backward of (y, dz) formed on the fly: x = y and dz (b, rows, r),
+ *           scale, shift, mean, invstd of the layer's BatchNorm, coef (rows, 3) as
+ *           mlp_bn_relu_backward_stats leaves it
+ *   mode 3  the same for the pooled last layer of a set-abstraction MLP (F.max_pool2d backward first,
+ *           pointnet2_modules.py:256-262): x = y (b, rows, groups, ns), dz = dpooled and argmax
+ *           (b, rows, groups), ns, groups, the vectors of mode 2 with coef as
+ *           mlp_bn_relu_pool_backward(dy = NULL) leaves it -- neither dz nor dy is written to memory
+ *   mode 4  the output of a VIRTUAL 4 -> rows first layer, never stored: x is that layer's input
+ *           (b, 4, r), lin_w its weight (rows, 4), (scale, shift) its BatchNorm; the operand
+ *           relu((lin_w . x)*scale + shift) is recomputed; mean / invstd as for mode 1 */
+typedef struct MlpOperand {
+  int mode;
+  const float *x;
+  const float *dz;
+  const float *scale;
+  const float *shift;
+  const float *mean;
+  const float *invstd;
+  const float *coef;
+  const int *argmax;
+  int ns;
+  int groups;
+  const float *lin_w;
+} MlpOperand;
+
+/* forward: y = W * x (replaces nn.Conv2d of a shared-MLP layer, pytorch_utils.py:70-124); x: mode 0
+ * or 1.  img (may be NULL): the weight ALSO as the bf16 image of mlp_weight_images_build below
+ * (needs mlp_gemm_image_supported).  pairs (may be NULL): parts x m x 2 floats, the BatchNorm
+ * statistics as a by-product (needs mlp_gemm_forward_stats_parts > 0).  Not both. */
+int mlp_gemm_forward(int b, int m, int k, int r, const float *w, const void *img,
+                     const MlpOperand *x, float *y, float *pairs, void *stream);
 
 /* BatchNorm statistics as a by-product of the convolution (nn.Conv2d + nn.BatchNorm2d of a
  * shared-MLP layer, pytorch_utils.py:70-124, in training mode): the GEMM epilogue reduces every
@@ -103,10 +139,6 @@ int mlp_gemm_forward(int b, int m, int k, int r, const float *w, const float *x,
  * re-read y.  mlp_gemm_forward_stats_parts: pairs per channel for this shape (0 = not covered:
  * use mlp_bn_train_stats) and the columns each pair covers. */
 int mlp_gemm_forward_stats_parts(int b, int m, int k, int r, int *cols_per_part);
-/* mlp_gemm_forward (pytorch_utils.py:70-124) + pairs (parts x m x 2 floats) */
-int mlp_gemm_forward_stats(int b, int m, int k, int r, const float *w, const float *x, int mode,
-                           const float *scale, const float *shift, float *y, float *pairs,
-                           void *stream);
 /* mlp_bn_train_stats (nn.BatchNorm2d training statistics, pytorch_utils.py:14-39) from the pairs;
  * scratch: mlp_bn_finalize_pairs_scratch_bytes(c) bytes of device memory */
 int mlp_bn_finalize_pairs(int c, int parts, int n_part, const float *pairs, const float *gamma,
@@ -116,56 +148,18 @@ int mlp_bn_finalize_pairs(int c, int parts, int n_part, const float *pairs, cons
 /* scratch size of mlp_bn_finalize_pairs (nn.BatchNorm2d keeps no scratch, pytorch_utils.py:14-39) */
 size_t mlp_bn_finalize_pairs_scratch_bytes(int c);
 
-/* input gradient: dx (b,k,r) = W^T * dy; wt is W^T (k,m) row-major.  mode 0: dy is given;
- * mode 2: dy is formed on the fly from (y, dz) and the vectors of mlp_bn_relu_backward_stats
- * (replaces conv2d backward-data + the BatchNorm/ReLU backward, pytorch_utils.py:70-124) */
-int mlp_gemm_dgrad(int b, int m, int k, int r, const float *wt, int mode, const float *dy,
-                   const float *y, const float *dz, const float *scale, const float *shift,
-                   const float *mean, const float *invstd, const float *coef, float *dx,
+/* input gradient: dx (b,k,r) = W^T * dy with the weight as stored, w (m,k) row-major (the kernel
+ * reads it transposed with a swapped lane mapping: no per-call transpose); dy (b,m,r): mode 0, 2
+ * or 3 (replaces conv2d backward-data and, for modes 2 / 3, the BatchNorm / ReLU / F.max_pool2d
+ * backward in front of it, pytorch_utils.py:70-124, pointnet2_modules.py:256-262) */
+int mlp_gemm_dgrad(int b, int m, int k, int r, const float *w, const MlpOperand *dy, float *dx,
                    void *stream);
 
-/* mlp_gemm_dgrad with the weight as stored (w (m,k) row-major) instead of its transposed copy:
- * the kernel reads A transposed with a swapped lane mapping (replaces conv2d backward-data,
- * pytorch_utils.py:70-124, without the per-call transpose of the weight) */
-int mlp_gemm_dgrad_nt(int b, int m, int k, int r, const float *w, int mode, const float *dy,
-                      const float *y, const float *dz, const float *scale, const float *shift,
-                      const float *mean, const float *invstd, const float *coef, float *dx,
-                      void *stream);
-
-/* mlp_gemm_dgrad_pooled with the weight as stored (replaces F.max_pool2d backward + ReLU /
- * BatchNorm2d backward + conv2d backward-data, pointnet2_modules.py:256-262,
+/* weight gradient: dw (m,k) = sum_b dy[b] * x[b]^T; dy (b,m,r): mode 0, 2 or 3; x (b,k,r): mode 0
+ * or 1.  workspace: mlp_gemm_wgrad_workspace_floats floats (replaces conv2d backward-weight,
  * pytorch_utils.py:70-124) */
-int mlp_gemm_dgrad_pooled_nt(int b, int m, int k, int groups, int ns, const float *w, const float *y,
-                             const float *dpooled, const int *argmax, const float *scale,
-                             const float *shift, const float *mean, const float *invstd,
-                             const float *coef, float *dx, void *stream);
-
-/* mlp_gemm_dgrad for the pooled last layer of a set-abstraction MLP: dy (b,m,groups,ns) is formed
- * on the fly from y, dpooled (b,m,groups), argmax (b,m,groups) and the vectors of
- * mlp_bn_relu_pool_backward(dy = NULL) -- neither dz nor dy is written to memory (replaces
- * F.max_pool2d backward + ReLU/BatchNorm2d backward + conv2d backward-data,
- * pointnet2_modules.py:256-262 and pytorch_utils.py:70-124) */
-int mlp_gemm_dgrad_pooled(int b, int m, int k, int groups, int ns, const float *wt, const float *y,
-                          const float *dpooled, const int *argmax, const float *scale,
-                          const float *shift, const float *mean, const float *invstd,
-                          const float *coef, float *dx, void *stream);
-
-/* weight gradient: dw (m,k) = sum_b dy[b] * x[b]^T; dy given (pmode 0) or on the fly (pmode 2);
- * x given (qmode 0) or relu(bn(.)) of the previous layer's output (qmode 1).  workspace:
- * mlp_gemm_wgrad_workspace_floats floats (replaces conv2d backward-weight, pytorch_utils.py:70-124) */
-int mlp_gemm_wgrad(int b, int m, int k, int r, int pmode, const float *dy, const float *y,
-                   const float *dz, const float *scale, const float *shift, const float *mean,
-                   const float *invstd, const float *coef, int qmode, const float *x,
-                   const float *xscale, const float *xshift, float *dw, float *workspace,
-                   void *stream);
-/* mlp_gemm_wgrad for the pooled last layer (dy formed on the fly as in mlp_gemm_dgrad_pooled;
- * replaces F.max_pool2d backward + ReLU/BatchNorm2d backward + conv2d backward-weight,
- * pointnet2_modules.py:256-262 and pytorch_utils.py:70-124); workspace as for r = groups*ns */
-int mlp_gemm_wgrad_pooled(int b, int m, int k, int groups, int ns, const float *y,
-                          const float *dpooled, const int *argmax, const float *scale,
-                          const float *shift, const float *mean, const float *invstd,
-                          const float *coef, int qmode, const float *x, const float *xscale,
-                          const float *xshift, float *dw, float *workspace, void *stream);
+int mlp_gemm_wgrad(int b, int m, int k, int r, const MlpOperand *dy, const MlpOperand *x,
+                   float *dw, float *workspace, void *stream);
 
 /* ---- max over nsample without a second pass over the last layer's output ---------------------
  * relu(y*scale + shift) is monotone in y per channel, so the max-pool over nsample that follows
@@ -176,7 +170,7 @@ int mlp_gemm_wgrad_pooled(int b, int m, int k, int groups, int ns, const float *
 /* 1 when mlp_gemm_forward_stats_pool covers the layer: m 128 or 256, ns 16 / 32 / 64, k % 4 == 0
  * and the epilogue statistics available (dispatch helper for pointnet2_modules.py:256-262) */
 int mlp_gemm_forward_stats_pool_supported(int b, int m, int k, int r, int ns);
-/* mlp_gemm_forward_stats (mode 1) that also writes ext: 2 planes of (b, m, r/ns) -- the raw output
+/* mlp_gemm_forward with pairs (x mode 1) that also writes ext: 2 planes of (b, m, r/ns) -- the raw output
  * that wins the pool per channel and group of ns columns (the largest where gamma >= 0, the
  * smallest where gamma < 0: gamma = the weight of the BatchNorm that follows) and its first
  * index (replaces the read of y in the max-pool of pointnet2_modules.py:256-262).  y may be NULL:
@@ -264,77 +258,59 @@ int mlp_bn_pool_from_extrema(int b, int c, int groups, const float *ext, const f
 /* ---- dgrad + wgrad of one layer in one pass over its activations -----------------------------
  * The two backward GEMMs of a conv(1x1)+BN+ReLU layer (pytorch_utils.py:70-124: the autograd of
  * nn.Conv2d inside SharedMLP, :14-39) both consume the BatchNorm/ReLU backward of the incoming
- * gradient; run separately (mlp_gemm_dgrad_nt + mlp_gemm_wgrad above) both read the pair it is
+ * gradient; run separately (mlp_gemm_dgrad + mlp_gemm_wgrad above) both read the pair it is
  * formed from.  Covered: (m,k) in {(64,64), (128,64), (128,128), (256,128), (128,131), (128,259)},
- * r a multiple of 64 / 32, pmode 2 (from y, dz) or 3 (pooled last layer: (128,64), (256,128),
- * (128,128)),
- * qmode 1 (x = raw output of the previous layer) or 0 (grouped network input: the k = 3+32j
+ * r a multiple of 64 / 32, dy mode 2 or 3 (pooled last layer: (128,64), (256,128), (128,128)),
+ * x mode 1 (x = raw output of the previous layer) or 0 (grouped network input: the k = 3+32j
  * shapes). */
 /* 1 when mlp_gemm_backward_fused covers the layer (replaces nothing by itself: dispatch helper
- * for the conv backward of pytorch_utils.py:70-124); ns = nsample for pmode 3, else 0 */
+ * for the conv backward of pytorch_utils.py:70-124); pmode / qmode: the modes of dy and x;
+ * ns = nsample for pmode 3, else 0 */
 int mlp_gemm_backward_fused_supported(int b, int m, int k, int r, int pmode, int qmode, int ns);
 /* scratch (floats): one partial dW per persistent workgroup (replaces cuDNN's backward-weight
  * workspace behind pytorch_utils.py:70-124) */
 size_t mlp_gemm_backward_fused_workspace_floats(int b, int m, int k, int r);
 /* dq (b,k,r) = w^T * P[b] and dw (m,k) = sum_b P[b] * Q[b]^T (replaces conv2d backward-input AND
- * backward-weight, pytorch_utils.py:70-124).  P as in mlp_gemm_dgrad_nt (pmode 2: y, dz (b,m,r))
- * or mlp_gemm_dgrad_pooled_nt (pmode 3: y, dz = dpooled (b,m,r/ns), argmax); Q as in
- * mlp_gemm_wgrad (qmode 1: relu(x*xscale + xshift), qmode 0: x; qmode 4, (64,64) only: the layer
- * below is a 4 -> 64 first layer whose output is not stored -- x is ITS input (b,4,r), xlin_w its
- * weight (64,4), and Q = relu((xlin_w . x)*xscale + xshift) is recomputed.  With qmode 4 the data
- * gradient is NOT written -- its only readers are the virtual layer's BatchNorm sums (stats_part) and
- * weight gradient: dq then receives the gated sums G = sum_n [gate] dq x^T of that layer as parts
- * partials of (64,4) floats, parts = mlp_gemm_backward_fused_stats_parts(): the input of
+ * backward-weight, pytorch_utils.py:70-124).  P = dy (mode 2 or 3), Q = x (mode 0 or 1; mode 4,
+ * (64,64) only: the layer below is a virtual 4 -> 64 first layer.  With mode 4 the data gradient is
+ * NOT written -- its only readers are the virtual layer's BatchNorm sums (stats_part) and weight
+ * gradient: dq then receives the gated sums G = sum_n [gate] dq x^T of that layer as parts partials
+ * of (64,4) floats, parts = mlp_gemm_backward_fused_stats_parts(): the input of
  * mlp_wgrad_first4_from_gated).
  * dq == NULL (only (128,259)): the weight gradient alone, for a first layer whose input needs no
  * gradient.
- * qmode 1 also needs xmean / xinvstd of the layer that produced x, and, for the k = 64 shapes when
- * stats_part is not NULL, leaves that layer's BatchNorm-backward sums there: stats_part (k, parts, 2) =
- * (sum g, sum g*xhat) with g = dq * [x*xscale + xshift > 0], parts =
+ * x modes 1 and 4 also need mean / invstd of the layer that produced x, and, for the k = 64 shapes
+ * when stats_part is not NULL, leave that layer's BatchNorm-backward sums there: stats_part
+ * (k, parts, 2) = (sum g, sum g*xhat) with g = dq * [x*scale + shift > 0], parts =
  * mlp_gemm_backward_fused_stats_parts() -- the input of mlp_bn_backward_finalize, in place of
  * that layer's mlp_bn_relu_backward_stats pass over (x, dq). */
-int mlp_gemm_backward_fused(int b, int m, int k, int r, const float *w, int pmode, const float *y,
-                            const float *dz, const int *argmax, int ns, const float *scale,
-                            const float *shift, const float *mean, const float *invstd,
-                            const float *coef, int qmode, const float *x, const float *xscale,
-                            const float *xshift, const float *xmean, const float *xinvstd,
-                            const float *xlin_w, float *dq, float *dw, float *workspace,
+int mlp_gemm_backward_fused(int b, int m, int k, int r, const float *w, const MlpOperand *dy,
+                            const MlpOperand *x, float *dq, float *dw, float *workspace,
                             float *stats_part, void *stream);
 /* The same two GEMMs for the SMALL layers (FP modules, vote / proposal / IoU heads, the pre-gather
  * first layers: b*r <= 16384 columns): conv backward-input and backward-weight of
  * pytorch_utils.py:70-124 are independent and neither fills the chip, so one launch runs both
- * (about the larger of the two instead of their sum).  pmode 0: P = dy (b,m,r) given; pmode 2: P
- * formed on the fly from y, dz and the BatchNorm / ReLU backward constants as in
- * mlp_gemm_dgrad_nt; qmode 0 / 1 as in mlp_gemm_wgrad.  dq == NULL: the weight gradient alone.
- * workspace: mlp_gemm_wgrad_workspace_floats(b, m, k, r) floats. */
+ * (about the larger of the two instead of their sum).  dy: mode 0 or 2; x: mode 0 or 1 (pmode /
+ * qmode of the dispatch helper).  dq == NULL: the weight gradient alone.  img_t (may be NULL): the
+ * TRANSPOSED weight also as the bf16 image of mlp_weight_images_build, read by the data-gradient
+ * half when dy is given (mode 0).  workspace: mlp_gemm_wgrad_workspace_floats(b, m, k, r) floats. */
 int mlp_gemm_backward_small_supported(int b, int m, int k, int r, int pmode, int qmode);
-int mlp_gemm_backward_small(int b, int m, int k, int r, const float *w, int pmode,
-                            const float *dy_or_y, const float *dz, const float *scale,
-                            const float *shift, const float *mean, const float *invstd,
-                            const float *coef, int qmode, const float *x, const float *xscale,
-                            const float *xshift, float *dq, float *dw, float *workspace,
-                            void *stream);
+int mlp_gemm_backward_small(int b, int m, int k, int r, const float *w, const void *img_t,
+                            const MlpOperand *dy, const MlpOperand *x, float *dq, float *dw,
+                            float *workspace, void *stream);
 /* bf16 images of the weights of the SMALL layers (FP modules, heads, pre-gather first layers;
  * b*r <= 16384 columns).  Their 64 x 64-tile kernels compute fp32 products as six bf16 MFMAs on an
  * exact three-term split of both operands; every one of a layer's ~128 workgroups split the same
  * weight tile again.  mlp_weight_images_build writes that split ONCE per optimizer step for all
  * weights of a table, in the two orders the forward convolution (pytorch_utils.py:70-124) and its
- * backward-input read; mlp_gemm_forward_img / mlp_gemm_backward_small_img are mlp_gemm_forward /
- * mlp_gemm_backward_small that take the image next to the fp32 weight -- same results bit for bit.
+ * backward-input read; mlp_gemm_forward (img) / mlp_gemm_backward_small (img_t) take the image next
+ * to the fp32 weight -- same results bit for bit.
  * An image is mlp_weight_image_elems(m, k) 2-byte elements (three planes, both dimensions padded
  * to multiples of 64), 16-byte aligned.  w / m / k / img / img_t of the build call: HOST arrays. */
 size_t mlp_weight_image_elems(int m, int k);
 int mlp_weight_images_build(int n, const void *const *w, const int *m, const int *k,
                             void *const *img, void *const *img_t, void *stream);
 int mlp_gemm_image_supported(int b, int r);
-int mlp_gemm_forward_img(int b, int m, int k, int r, const float *w, const void *img, const float *x,
-                         int mode, const float *scale, const float *shift, float *y, void *stream);
-int mlp_gemm_backward_small_img(int b, int m, int k, int r, const float *w, const void *img_t,
-                                int pmode, const float *dy_or_y, const float *dz, const float *scale,
-                                const float *shift, const float *mean, const float *invstd,
-                                const float *coef, int qmode, const float *x, const float *xscale,
-                                const float *xshift, float *dq, float *dw, float *workspace,
-                                void *stream);
 /* partials per channel in stats_part; 0 when the layer leaves none (sizing helper for the
  * BatchNorm backward of pytorch_utils.py:42-50) */
 int mlp_gemm_backward_fused_stats_parts(int b, int m, int k, int r);
@@ -344,7 +320,7 @@ int mlp_gemm_backward_fused_stats_parts(int b, int m, int k, int r);
 int mlp_bn_backward_finalize(int c, int parts, double count, int training, const float *partial,
                              const float *gamma, const float *invstd, float *dgamma, float *dbeta,
                              float *coef, void *stream);
-/* The weight gradients above (mlp_gemm_wgrad*, mlp_gemm_backward_fused) end with a deterministic
+/* The weight gradients above (mlp_gemm_wgrad, mlp_gemm_backward_small, mlp_gemm_backward_fused) end with a deterministic
  * reduction of per-workgroup partials in `workspace`.  A weight gradient's only reader is the
  * optimizer (conv2d backward-weight, pytorch_utils.py:70-124, then train.py's optimizer.step()), so
  * a training step may queue those ~30 small reductions of a backward pass and run them as ONE
@@ -378,14 +354,12 @@ int mlp_pregather_unpack_grad(int b, int n, int m, int c, const float *dsrc_ext,
  * of every (cloud, channel) row for mlp_bn_finalize_pairs (parts = b, n_part = m*ns) */
 int mlp_pregather_forward(int b, int c, int n, int m, int ns, const float *z_ext, const int *idx,
                           float *y, float *pairs, void *stream);
-/* dz_ext (b, c, n+m): the gradient of z_ext.  dy = BatchNorm/ReLU backward of (y, dz) on the fly
- * (operands as mlp_gemm_dgrad_nt's pmode 2), scatter-added over idx through `inverse`
+/* dz_ext (b, c, n+m): the gradient of z_ext.  dy (b,c,m,ns): MlpOperand mode 2 (the BatchNorm/ReLU
+ * backward of (y, dz) on the fly), scatter-added over idx through `inverse`
  * (pn2_group_inverse_build) into columns < n, minus its per-group sums into columns n + j
  * (replaces conv2d backward-input + group_points_grad, group_points_gpu.cu:48-80) */
-int mlp_pregather_backward(int b, int c, int n, int m, int ns, const float *y, const float *dz,
-                           const float *scale, const float *shift, const float *mean,
-                           const float *invstd, const float *coef, const unsigned *inverse,
-                           float *dz_ext, void *stream);
+int mlp_pregather_backward(int b, int c, int n, int m, int ns, const MlpOperand *dy,
+                           const unsigned *inverse, float *dz_ext, void *stream);
 
 /* ---- weight gradient of a 4 -> 64 first layer without its output ------------------------------
  * SA1's first layer (mlp [1+3, 64, ...], pointnet2_modules.py:230-262 / pytorch_utils.py:70-124):
@@ -404,7 +378,7 @@ int mlp_first4_bn(const double *moments, double count, const float *w, const flo
                   const float *beta, float eps, float momentum, float *running_mean,
                   float *running_var, float *mean, float *invstd, float *scale, float *shift,
                   void *stream);
-/* mlp_gemm_forward_stats for the SECOND layer (64 -> 64) of such a chain: the operand
+/* mlp_gemm_forward with pairs for the SECOND layer (64 -> 64) of such a chain: the operand
  * relu(bn(w1 x4)) is recomputed from x4 (b,4,r); the first layer's output is never stored
  * (replaces conv + BatchNorm + ReLU + conv of pytorch_utils.py:14-39 for SA1's first two layers) */
 int mlp_gemm_forward_stats_lin4(int b, int r, const float *w, const float *x4, const float *w1,
@@ -421,7 +395,7 @@ int mlp_wgrad_first4(int b, int r, const float *w, const float *x, const float *
                      const float *scale, const float *shift, const float *mean, const float *invstd,
                      const float *coef, const double *moments, float *dw, void *workspace,
                      void *stream);
-/* The same from gated sums formed elsewhere: mlp_gemm_backward_fused with qmode 4 leaves G = sum_n
+/* The same from gated sums formed elsewhere: mlp_gemm_backward_fused with x mode 4 leaves G = sum_n
  * gate dz x^T as `parts` partials of (64,4) in its dq argument instead of writing dz (the virtual
  * first layer of pytorch_utils.py:14-39: nobody else reads that gradient); moments as above
  * (required), workspace 256 floats */

@@ -8,6 +8,7 @@ The forms with the sums go through gemm_backward_fused; the wrapper always asks 
 relu(bn(.)) input, so the forms without them go through the library handle of the same module
 (mlp_gemm_backward_fused with a null stats_part).  Tolerances: those of
 test_gpu_mlp.py::test_fused_backward_vs_two_gemms (1e-5 dx, 2e-5 dw, 2e-5 the sums)."""
+import ctypes
 import importlib
 
 import numpy as np
@@ -31,24 +32,15 @@ def _fused_without_sums(K, w, x, xcoeff, xstats, fly=None, pooled=None):
     b, k = x.shape[0], x.shape[1]
     m = w.shape[0]
     r = x.numel() // (b * k)
-    if pooled is not None:
-        y, dz, argmax, scale, shift, mean, invstd, coef = pooled
-        pmode, ns = 3, y.shape[3]
-    else:
-        y, dz, scale, shift, mean, invstd, coef = fly
-        argmax, pmode, ns = None, 2, 0
-    assert K._lib.mlp_gemm_backward_fused_supported(b, m, k, r, pmode, 1, ns)
+    p, q = K._grad_operand(fly=fly, pooled=pooled), K._input_operand(x, xcoeff, xstats)
+    assert K._lib.mlp_gemm_backward_fused_supported(b, m, k, r, p.mode, 1, p.ns)
     dx = torch.empty_like(x)
     dw = torch.empty((m, k), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         ws = torch.empty(max(int(K._lib.mlp_gemm_backward_fused_workspace_floats(b, m, k, r)), 1),
                          dtype=torch.float32, device=x.device)
-        K._L.check(K._lib.mlp_gemm_backward_fused(b, m, k, r, w.data_ptr(), pmode, y.data_ptr(),
-                                                  dz.data_ptr(), K._ptr(argmax), ns, scale.data_ptr(),
-                                                  shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                                  coef.data_ptr(), 1, x.data_ptr(), xcoeff[0].data_ptr(),
-                                                  xcoeff[1].data_ptr(), xstats[0].data_ptr(),
-                                                  xstats[1].data_ptr(), None, dx.data_ptr(), dw.data_ptr(),
+        K._L.check(K._lib.mlp_gemm_backward_fused(b, m, k, r, w.data_ptr(), ctypes.byref(p),
+                                                  ctypes.byref(q), dx.data_ptr(), dw.data_ptr(),
                                                   ws.data_ptr(), None, K._stream(x)),
                    "mlp_gemm_backward_fused")
         torch.cuda.synchronize()

@@ -170,7 +170,7 @@ def test_mfma_gemm_primitives_vs_torch(b, m, k, r, small, monkeypatch):
 @pytest.mark.parametrize("offset", [0.0, 40.0])
 def test_forward_gemm_leaves_batchnorm_statistics(b, m, k, r, offset):
     """Training-mode layer with the batch statistics reduced in the GEMM epilogue
-    (mlp_gemm_forward_stats + mlp_bn_finalize_pairs) == the GEMM followed by the statistics pass
+    (mlp_gemm_forward with pairs + mlp_bn_finalize_pairs) == the GEMM followed by the statistics pass
     over y (and == torch): same y, same mean / invstd / scale / shift, same running statistics --
     also when the channel means are 40 standard deviations away from zero (shifted sums)."""
     load_pkg()
@@ -1298,8 +1298,6 @@ def test_small_gemms_from_weight_images(b, m, k, r, monkeypatch):
     images = K.WeightImages([w, torch.ones(7, device=DEV), other])   # (1-D tensors are skipped)
     assert images.n == 2
     images.refresh()
-    calls = []
-    real = K._lib.mlp_gemm_forward_img
     want = [K.gemm_forward(w2, x), K.gemm_forward(w2, x, ck), K.gemm_backward_small(w2, x, ck, dy=dy),
             K.gemm_backward_small(w2, x, None, dy=dy)]
     with K.weight_images(images):
