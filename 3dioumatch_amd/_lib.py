@@ -90,16 +90,12 @@ _SIGNATURES = {
     "mlp_gemm_wgrad": [_c_int] * 4 + [_op, _op, _vp, _vp, _vp],
     "mlp_gemm_wgrad_workspace_floats": [_c_int, _c_int, _c_int, _c_int],
     "mlp_gemm_forward_stats_pool_supported": [_c_int, _c_int, _c_int, _c_int, _c_int],
-    "mlp_gemm_forward_stats_pool": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_int,
-                                    _vp, _vp, _vp],
-    "mlp_pool_gram_supported": [_c_int, _c_int, _c_int, _c_int, _c_int],
-    "mlp_pool_gram_parts": [_c_int, _c_int],
-    "mlp_pool_gram_workspace_floats": [_c_int, _c_int],
-    "mlp_pool_gram_backward": [_c_int, _c_int, _c_int] + [_vp] * 19,
-    "mlp_pool_gram256_supported": [_c_int, _c_int, _c_int, _c_int, _c_int],
-    "mlp_pool_gram256_parts": [_c_int, _c_int],
-    "mlp_pool_gram256_workspace_floats": [_c_int, _c_int, _c_int],
-    "mlp_pool_gram256_backward": [_c_int, _c_int, _c_int] + [_vp] * 19,
+    "mlp_gemm_forward_stats_pool": [_c_int] * 4 + [_vp, _op, _vp, _vp, _c_int, _vp, _vp, _vp],
+    # the pooled last layer's backward from its input's Gram matrix: (b, m, k, r) first
+    "mlp_pool_gram_supported": [_c_int] * 5,
+    "mlp_pool_gram_parts": [_c_int] * 4,
+    "mlp_pool_gram_workspace_floats": [_c_int] * 5,
+    "mlp_pool_gram_backward": [_c_int] * 4 + [_vp, _op, _op] + [_vp] * 6,
     "mlp_eval_lin4_supported": [_c_int] * 6,
     "mlp_eval_lin4_pool": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mlp_eval_stored_supported": [_c_int] * 6,
@@ -121,7 +117,6 @@ _SIGNATURES = {
     "mlp_first4_moments": [_c_int, _c_int, _vp, _vp, _vp],
     "mlp_first4_bn": [_vp, ctypes.c_double, _vp, _vp, _vp, _c_float, _c_float, _vp, _vp, _vp, _vp, _vp, _vp,
                       _vp],
-    "mlp_gemm_forward_stats_lin4": [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mlp_gemm_backward_fused_supported": [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int],
     "mlp_gemm_backward_fused_workspace_floats": [_c_int, _c_int, _c_int, _c_int],
     "mlp_gemm_backward_fused": [_c_int] * 4 + [_vp, _op, _op] + [_vp] * 5,
@@ -171,7 +166,7 @@ _SIGNATURES = {
     "iou3d_nms": [_vp, _c_int, _c_float, _c_int, _vp, _vp, _vp, _vp],
     "iou3d_boxes_iou_bev_cpu": [_c_int, _vp, _c_int, _vp, _vp],
 }
-_RESTYPE = {"pn2_ball_query_workspace_bytes": _sz, "lhs_pseudo_stats_workspace_bytes": _sz, "pn2_grid_bytes": _sz, "pn2_fps_workspace_bytes": _sz, "mlp_bn_workspace_floats": _sz, "mlp_gemm_wgrad_workspace_floats": _sz, "mlp_wgrad_first4_workspace_bytes": _sz, "mlp_gemm_backward_fused_workspace_floats": _sz, "mlp_bn_finalize_pairs_scratch_bytes": _sz, "mlp_chain_lin4_image_bytes": _sz, "mlp_eval_stored_image_bytes": _sz, "mlp_weight_image_elems": _sz, "mlp_pool_gram_workspace_floats": _sz, "mlp_pool_gram256_workspace_floats": _sz, "pn2_error_string": ctypes.c_char_p}
+_RESTYPE = {"pn2_ball_query_workspace_bytes": _sz, "lhs_pseudo_stats_workspace_bytes": _sz, "pn2_grid_bytes": _sz, "pn2_fps_workspace_bytes": _sz, "mlp_bn_workspace_floats": _sz, "mlp_gemm_wgrad_workspace_floats": _sz, "mlp_wgrad_first4_workspace_bytes": _sz, "mlp_gemm_backward_fused_workspace_floats": _sz, "mlp_bn_finalize_pairs_scratch_bytes": _sz, "mlp_chain_lin4_image_bytes": _sz, "mlp_eval_stored_image_bytes": _sz, "mlp_weight_image_elems": _sz, "mlp_pool_gram_workspace_floats": _sz, "pn2_error_string": ctypes.c_char_p}
 
 EXPORTS = tuple(_SIGNATURES)
 

@@ -1410,15 +1410,27 @@ MLP_API int mlp_gemm_forward_stats_parts(int b, int m, int k, int r, int *cols_p
 // [plane][m][k] order): same result bit for bit, the kernel neither stages nor splits w.  pairs: the
 // (mean, M2) pairs of every output channel per part (parts x m x 2 floats, parts from
 // mlp_gemm_forward_stats_parts).  The two regimes are disjoint.
+// x in mode 4 (pairs, no img, (m, k) = (64, 64), w and lin_w 16-byte aligned): the SECOND layer of a
+// chain whose first layer has a 4-channel input -- the operand relu(bn(lin_w x)) is recomputed from
+// x (b,4,r); the first layer's output is never stored.
 MLP_API int mlp_gemm_forward(int b, int m, int k, int r, const float *w, const void *img,
                              const MlpOperand *x, float *y, float *pairs, void *stream_) {
   if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
   OperandB op;
-  const int rc = operand_from_abi(x, op_bit(OP_DIRECT) | op_bit(OP_BNRELU), r, &op);
+  const int rc = operand_from_abi(x, op_bit(OP_DIRECT) | op_bit(OP_BNRELU) | op_bit(OP_LIN4), r, &op);
   if (rc) return rc;
   if ((img && pairs) || (img && !mlp_gemm_image_supported(b, r)) ||
       (pairs && mlp_gemm_forward_stats_parts(b, m, k, r, nullptr) == 0))
     return (int)hipErrorInvalidValue;
+  if (x->mode == OP_LIN4) {
+    if (!pairs || img || m != 64 || k != 64 ||
+        ((reinterpret_cast<size_t>(w) | reinterpret_cast<size_t>(op.lin_w)) & 15) != 0)
+      return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((gemm_nn2_kernel<64, 128, 2, 2, OP_LIN4, false, true, true>),
+                       dim3(r / 128, 1, b), dim3(256), 0, (hipStream_t)stream_, m, k, r, w, k,
+                       (unsigned)(4 * (size_t)m * k), op, y, (size_t)4 * r, (size_t)m * r, pairs, m);
+    return pn2_launch_status();
+  }
   const size_t in_stride = (size_t)k * r, out_stride = (size_t)m * r;
   const AImage ai = {reinterpret_cast<const unsigned short *>(img), img ? pad64(k) : 0,
                      img ? (size_t)pad64(m) * pad64(k) : 0};
@@ -1436,23 +1448,23 @@ MLP_API int mlp_gemm_forward_stats_pool_supported(int b, int m, int k, int r, in
   return (m == 128 || m == 256) && (ns == 16 || ns == 32 || ns == 64) && r % ns == 0 && k % 4 == 0;
 }
 
-// mlp_gemm_forward with pairs (mode 1: x = raw output of the previous layer) that also leaves, per
+// mlp_gemm_forward with pairs (x: mode 1, the raw output of the previous layer) that also leaves, per
 // channel and group of ns columns, the raw output that wins the max-pool after BatchNorm (gamma:
 // the layer's BatchNorm weight, whose sign decides between largest and smallest) and its first
 // index: ext = 2 planes of b*m*(r/ns) 4-byte values.  y may be NULL: the raw output is then not
 // stored (the layer leaves its statistics and extrema only)
-MLP_API int mlp_gemm_forward_stats_pool(int b, int m, int k, int r, const float *w, const float *x,
-                                        const float *scale, const float *shift, float *y,
-                                        float *pairs, int ns, const float *gamma, float *ext,
+MLP_API int mlp_gemm_forward_stats_pool(int b, int m, int k, int r, const float *w, const MlpOperand *x,
+                                        float *y, float *pairs, int ns, const float *gamma, float *ext,
                                         void *stream_) {
-  if (!mlp_gemm_forward_stats_pool_supported(b, m, k, r, ns) || !pairs || !ext || !gamma ||
-      (reinterpret_cast<size_t>(w) & 15) != 0)
-    return (int)hipErrorInvalidValue;
+  if (!mlp_gemm_forward_stats_pool_supported(b, m, k, r, ns)) return (int)hipErrorInvalidValue;
+  OperandB op;
+  const int rc = operand_from_abi(x, op_bit(OP_BNRELU), r, &op);
+  if (rc) return rc;
+  if (!pairs || !ext || !gamma || (reinterpret_cast<size_t>(w) & 15) != 0) return (int)hipErrorInvalidValue;
   hipStream_t stream = (hipStream_t)stream_;
   // (256, 128), nsample 16 / 32: the persistent T-form kernel (same pairs, same ext; y may be NULL)
-  if (mlp_pool_fwd256_supported(b, m, k, r, ns, w, x) && (reinterpret_cast<size_t>(y) & 15) == 0)
-    return mlp_pool_fwd256_launch(b, r, ns, w, x, scale, shift, gamma, y, pairs, ext, stream);
-  OperandB op = {x, nullptr, scale, shift, nullptr, nullptr, nullptr};
+  if (mlp_pool_fwd256_supported(b, m, k, r, ns, w, *x) && (reinterpret_cast<size_t>(y) & 15) == 0)
+    return mlp_pool_fwd256_launch(b, r, ns, w, *x, gamma, y, pairs, ext, stream);
   const size_t in_stride = (size_t)k * r, out_stride = (size_t)m * r;
   const size_t plane = (size_t)b * m * (r / ns);
   const unsigned a_bytes = (unsigned)(4 * (size_t)m * k);
@@ -1467,24 +1479,6 @@ MLP_API int mlp_gemm_forward_stats_pool(int b, int m, int k, int r, const float 
   else if (ns == 32) POOLED(128, 128, 2, 2, 32);
   else POOLED(128, 128, 2, 2, 64);
 #undef POOLED
-  return pn2_launch_status();
-}
-
-// mlp_gemm_forward with pairs for the SECOND layer of a chain whose first layer has a 4-channel
-// input: the operand relu(bn(W1 x4)) is recomputed from x4 (b,4,r) -- the first layer's output
-// is never stored.  w (64,64), w1 (64,4), scale / shift (64) of the first layer's BatchNorm.
-MLP_API int mlp_gemm_forward_stats_lin4(int b, int r, const float *w, const float *x4,
-                                        const float *w1, const float *scale, const float *shift,
-                                        float *y, float *pairs, void *stream_) {
-  const int m = 64, k = 64;
-  if (b <= 0 || r <= 0) return 0;
-  if (!pairs || mlp_gemm_forward_stats_parts(b, m, k, r, nullptr) == 0 ||
-      (reinterpret_cast<size_t>(w) & 15) != 0 || (reinterpret_cast<size_t>(w1) & 15) != 0)
-    return (int)hipErrorInvalidValue;
-  OperandB op = {x4, nullptr, scale, shift, nullptr, nullptr, nullptr, nullptr, 0, 0, w1};
-  hipLaunchKernelGGL((gemm_nn2_kernel<64, 128, 2, 2, OP_LIN4, false, true, true>),
-                     dim3(r / 128, 1, b), dim3(256), 0, (hipStream_t)stream_, m, k, r, w, k,
-                     (unsigned)(4 * (size_t)m * k), op, y, (size_t)4 * r, (size_t)m * r, pairs, m);
   return pn2_launch_status();
 }
 

@@ -33,13 +33,16 @@ constexpr bool is_dy(int mode) { return mode == OP_DY || mode == OP_POOLDY; }
 // The C ABI's operand record (include/mlp_hip.h, which says what every mode reads) as the kernels
 // take it.  `modes`: bit i set = the entry point takes mode i; r: the columns per cloud of the
 // call.  hipErrorInvalidValue when the mode is not among them or one of its fields is missing.
+// OP_NO_Y among the modes (mlp_pool_gram_backward alone): the raw output a mode-3 record would carry
+// as x was never stored, so that record's x may be NULL.
 constexpr unsigned op_bit(int mode) { return 1u << mode; }
+constexpr unsigned OP_NO_Y = 1u << 8;
 
 inline int operand_from_abi(const MlpOperand *a, unsigned modes, int r, OperandB *op) {
   if (!a || a->mode < OP_DIRECT || a->mode > OP_LIN4 || !(modes & op_bit(a->mode)))
     return (int)hipErrorInvalidValue;
   const int mode = a->mode;
-  bool ok = a->x != nullptr;
+  bool ok = a->x != nullptr || (mode == OP_POOLDY && (modes & OP_NO_Y));
   if (mode != OP_DIRECT) ok = ok && a->scale && a->shift;
   if (is_dy(mode)) ok = ok && a->dz && a->mean && a->invstd && a->coef;
   if (mode == OP_POOLDY)
@@ -213,8 +216,19 @@ int mlp_reduce_partials(int count, int parts, const float *part, float *out, hip
 // mlp_flush_weight_reductions() runs every queued one in ONE launch (a backward pass has ~30 of
 // them at 3-6 us each).  `part` must stay allocated until the flush.
 int mlp_reduce_weight_partials(int count, int parts, const float *part, float *out, hipStream_t stream);
-// the pooled 128 -> 256 layer's forward as a persistent T-form kernel (mlp_pool_fwd256.hip); y may be NULL
-int mlp_pool_fwd256_supported(int b, int m, int k, int r, int ns, const float *w, const float *x);
-int mlp_pool_fwd256_launch(int b, int r, int ns, const float *w, const float *x, const float *scale,
-                           const float *shift, const float *gamma, float *y, float *pairs, float *ext,
-                           hipStream_t stream);
+// Across translation units an operand travels as the ABI's record, already through operand_from_abi
+// (OperandB belongs to the unnamed namespace its kernels are mangled with: it cannot leave the file).
+// The pooled 128 -> 256 layer's forward as a persistent T-form kernel (mlp_pool_fwd256.hip); x: the
+// mode-1 record; y may be NULL
+int mlp_pool_fwd256_supported(int b, int m, int k, int r, int ns, const float *w, const MlpOperand &x);
+int mlp_pool_fwd256_launch(int b, int r, int ns, const float *w, const MlpOperand &x, const float *gamma,
+                           float *y, float *pairs, float *ext, hipStream_t stream);
+// The (256, 128) half of mlp_pool_gram_* (mlp_pool_gram256.hip; the exported family and the (128, 64)
+// half: mlp_pool_gram.hip).  _supported: the forward's question (covered and worth it; _launch asks
+// for coverage alone); dy: the mode-3 record (its x is not read), x: the mode-1 record with mean / invstd
+bool mlp_pool_gram256_supported(int b, int r, int ns);
+int mlp_pool_gram256_parts(int b, int r);
+size_t mlp_pool_gram256_workspace_floats(int b, int r, int ns);
+int mlp_pool_gram256_launch(int b, int r, const float *w, const MlpOperand &dy, const MlpOperand &x,
+                            const float *ymax, float *dq, float *dw, float *stats_part, float *workspace,
+                            hipStream_t stream);

@@ -403,24 +403,23 @@ int pool_fwd256_cus() {
 
 // 1 when mlp_gemm_forward_stats_pool runs here: (m, k) = (256, 128), nsample 16 / 32, whole
 // 256-column blocks per cloud (MLP_POOL_FWD256=0: the tiled kernel)
-int mlp_pool_fwd256_supported(int b, int m, int k, int r, int ns, const float *w, const float *x) {
+int mlp_pool_fwd256_supported(int b, int m, int k, int r, int ns, const float *w, const MlpOperand &x) {
   const char *env = getenv("MLP_POOL_FWD256");  // (read on every call: the tests compare both kernels)
   const bool off = env && atoi(env) == 0;
   if (off || b <= 0 || m != kFM || k != kFK || r <= 0 || r % 256 != 0) return 0;
   if ((ns != 16 && ns != 32) || r % ns != 0) return 0;
-  return ((reinterpret_cast<size_t>(w) | reinterpret_cast<size_t>(x)) & 15) == 0 ? 1 : 0;
+  return ((reinterpret_cast<size_t>(w) | reinterpret_cast<size_t>(x.x)) & 15) == 0 ? 1 : 0;
 }
 
 // pairs: (b * r / 64, 256, 2); ext: 2 planes of (b, 256, r / ns) -- as the tiled kernel leaves them
-int mlp_pool_fwd256_launch(int b, int r, int ns, const float *w, const float *x, const float *scale,
-                           const float *shift, const float *gamma, float *y, float *pairs, float *ext,
-                           hipStream_t stream) {
-  if (!w || !x || !scale || !shift || !gamma || !pairs || !ext || (ns != 16 && ns != 32) || b <= 0 || r <= 0 ||
+int mlp_pool_fwd256_launch(int b, int r, int ns, const float *w, const MlpOperand &x, const float *gamma,
+                           float *y, float *pairs, float *ext, hipStream_t stream) {
+  if (!w || !x.x || !x.scale || !x.shift || !gamma || !pairs || !ext || (ns != 16 && ns != 32) || b <= 0 || r <= 0 ||
       r % 256 != 0)
     return (int)hipErrorInvalidValue;
   PoolFwdArgs a = {};
   a.r = r; a.chunks_per_cloud = r / kFTN; a.total_tiles = b * (r / 64); a.groups = r / ns;
-  a.w = w; a.x = x; a.sc = scale; a.sh = shift; a.gamma = gamma; a.pairs = pairs; a.ext = ext; a.y = y;
+  a.w = w; a.x = x.x; a.sc = x.scale; a.sh = x.shift; a.gamma = gamma; a.pairs = pairs; a.ext = ext; a.y = y;
   a.ext_plane = (size_t)b * kFM * (size_t)(r / ns);
   int grid = pool_fwd256_cus();
   if (grid > a.total_tiles / 2) grid = a.total_tiles / 2;

@@ -549,44 +549,62 @@ constexpr size_t kGramLds = 2 * (3 * (128 + 64) * 80 + 64 * 144) + 64 * 16 + 64 
 
 #define MLP_API extern "C" __attribute__((visibility("default")))
 
-// 1 when mlp_pool_gram_backward covers the layer: (m, k) = (128, 64), nsample 16 / 32 / 64, whole
-// 32-column chunks per cloud
+// what the (128, 64) pass covers: nsample 16 / 32 / 64, whole 32-column chunks per cloud, and enough
+// of them (64) to be worth it
+static bool gram_covers(int b, int r, int ns) {
+  if (b <= 0 || r <= 0 || r % 32 != 0) return false;
+  if ((ns != 16 && ns != 32 && ns != 64) || r % ns != 0) return false;
+  return (long long)b * (r / 32) >= 64;
+}
+static bool is128(int m, int k) { return m == kGM && k == kGK; }
+static bool is256(int m, int k) { return m == 256 && k == 128; }
+
+// The mlp_pool_gram_* family dispatches on (m, k): (128, 64) is this file, (256, 128)
+// mlp_pool_gram256.hip; any other layer is not covered.
+// 1 when the forward may leave the layer's backward to mlp_pool_gram_backward
 MLP_API int mlp_pool_gram_supported(int b, int m, int k, int r, int ns) {
-  if (b <= 0 || m != kGM || k != kGK || r <= 0 || r % 32 != 0) return 0;
-  if ((ns != 16 && ns != 32 && ns != 64) || r % ns != 0) return 0;
-  return (long long)b * (r / 32) >= 64 ? 1 : 0;
+  if (is128(m, k)) return gram_covers(b, r, ns) ? 1 : 0;
+  return is256(m, k) && mlp_pool_gram256_supported(b, r, ns) ? 1 : 0;
 }
 
 // number of per-workgroup partials (= parts of stats_part) and floats of workspace
-MLP_API int mlp_pool_gram_parts(int b, int r) { return gram_workgroups(b, r); }
-MLP_API size_t mlp_pool_gram_workspace_floats(int b, int r) {
+MLP_API int mlp_pool_gram_parts(int b, int m, int k, int r) {
+  if (is128(m, k)) return gram_workgroups(b, r);
+  return is256(m, k) ? mlp_pool_gram256_parts(b, r) : 0;
+}
+MLP_API size_t mlp_pool_gram_workspace_floats(int b, int m, int k, int r, int ns) {
+  if (is256(m, k)) return mlp_pool_gram256_workspace_floats(b, r, ns);
+  if (!is128(m, k)) return 0;
   const size_t g = (size_t)gram_workgroups(b, r);
   // qp (256) + M3 (4096) + v (64) + partials (4096 + 64 + 8192 per workgroup) + the sums as doubles
   return 256 + 4096 + 64 + g * (4096 + 64 + 8192) + 2 * (size_t)kGramSums + 16;
 }
 
-// Backward of the pooled last layer y3 = w3 . relu(bn2(y2)) from y2 and the pooled tensors alone:
-// dq (b,64,r) = gradient w.r.t. relu(bn2(y2)); dw3 (128,64); stats_part (64, parts, 2): the
-// BatchNorm-backward sums of layer 2 (for mlp_bn_backward_finalize).  coef3 (128,3) = (a, c1, c2) of
-// layer 3 as mlp_bn_relu_pool_backward leaves them.
-MLP_API int mlp_pool_gram_backward(int b, int r, int ns, const float *w3, const float *y2, const float *sc2,
-                                   const float *sh2, const float *mean2, const float *invstd2,
-                                   const float *coef3, const float *sc3, const float *sh3,
-                                   const float *mean3, const float *invstd3, const int *argmax,
-                                   const float *dpooled, const float *ymax, float *dq, float *dw3,
+// Backward of the pooled last layer y = w . relu(bn(x)) from x and the pooled tensors alone:
+// dq (b,k,r) = gradient w.r.t. relu(bn(x)); dw (m,k); stats_part (k, parts, 2): the BatchNorm-backward
+// sums of the layer below (for mlp_bn_backward_finalize).  dy: the layer's mode-3 record (its x, the
+// raw output, is not read and may be NULL); x: the mode-1 record of the layer below, mean / invstd
+// included.  The (256, 128) pass checks coverage only, not the forward's threshold.
+MLP_API int mlp_pool_gram_backward(int b, int m, int k, int r, const float *w, const MlpOperand *dy,
+                                   const MlpOperand *x, const float *ymax, float *dq, float *dw,
                                    float *stats_part, float *workspace, void *stream_) {
-  if (!mlp_pool_gram_supported(b, kGM, kGK, r, ns) || !w3 || !y2 || !sc2 || !sh2 || !mean2 || !invstd2 ||
-      !coef3 || !sc3 || !sh3 || !mean3 || !invstd3 || !argmax || !dpooled || !ymax || !dq || !dw3 ||
-      !stats_part || !workspace || (reinterpret_cast<size_t>(workspace) & 15) ||
-      (reinterpret_cast<size_t>(y2) & 15))
+  if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
+  OperandB P, Q;
+  int rc = operand_from_abi(dy, op_bit(OP_POOLDY) | OP_NO_Y, r, &P);
+  if (!rc) rc = operand_from_abi(x, op_bit(OP_BNRELU), r, &Q);
+  if (rc) return rc;
+  if (!Q.mean || !Q.invstd || !w || !ymax || !dq || !dw || !stats_part || !workspace ||
+      (reinterpret_cast<size_t>(workspace) & 15) || (reinterpret_cast<size_t>(Q.x) & 15))
     return (int)hipErrorInvalidValue;
   hipStream_t stream = (hipStream_t)stream_;
+  if (is256(m, k)) return mlp_pool_gram256_launch(b, r, w, *dy, *x, ymax, dq, dw, stats_part, workspace, stream);
+  if (!is128(m, k) || !gram_covers(b, r, P.ns)) return (int)hipErrorInvalidValue;
   const int g = gram_workgroups(b, r);
   float *qp = workspace, *m3 = qp + 256, *v = m3 + 4096;
   float *part_c2 = v + 64, *part_s2 = part_c2 + (size_t)g * 4096, *part_r = part_s2 + (size_t)g * 64;
   float *tail = part_r + (size_t)g * 8192;
   double *sums = reinterpret_cast<double *>(tail + ((reinterpret_cast<size_t>(tail) & 7) ? 1 : 0));
-  hipLaunchKernelGGL(pool_gram_prep_kernel, dim3(16), dim3(256), 0, stream, w3, coef3, mean3, invstd3, qp,
+  hipLaunchKernelGGL(pool_gram_prep_kernel, dim3(16), dim3(256), 0, stream, w, P.coef, P.mean, P.invstd, qp,
                      m3, v);
   static std::mutex mu;
   static bool attr_set = false;
@@ -599,15 +617,15 @@ MLP_API int mlp_pool_gram_backward(int b, int r, int ns, const float *w3, const 
     }
   }
   GramArgs a = {};
-  a.r = r; a.total_chunks = b * (r / 32); a.chunks_per_cloud = r / 32; a.ns = ns; a.groups = r / ns;
-  a.y2 = y2; a.sc2 = sc2; a.sh2 = sh2; a.mean2 = mean2; a.invstd2 = invstd2;
-  a.m3 = m3; a.v = v; a.w3 = w3; a.coef3 = coef3; a.sc3 = sc3; a.sh3 = sh3;
-  a.argmax = argmax; a.dpooled = dpooled; a.ymax = ymax;
+  a.r = r; a.total_chunks = b * (r / 32); a.chunks_per_cloud = r / 32; a.ns = P.ns; a.groups = P.groups;
+  a.y2 = Q.x; a.sc2 = Q.scale; a.sh2 = Q.shift; a.mean2 = Q.mean; a.invstd2 = Q.invstd;
+  a.m3 = m3; a.v = v; a.w3 = w; a.coef3 = P.coef; a.sc3 = P.scale; a.sh3 = P.shift;
+  a.argmax = P.argmax; a.dpooled = P.dz; a.ymax = ymax;
   a.dq = dq; a.part_c2 = part_c2; a.part_s2 = part_s2; a.part_r = part_r; a.stats_part = stats_part;
   hipLaunchKernelGGL(pool_gram_bwd_kernel, dim3(g), dim3(256), kGramLds, stream, a);
   static_assert(kGramSums % 32 == 0, "whole reduce workgroups");
   hipLaunchKernelGGL(pool_gram_reduce_kernel, dim3(kGramSums / 32), dim3(256), 0, stream, g, part_c2, part_s2,
                      part_r, sums);
-  hipLaunchKernelGGL(pool_gram_dw_kernel, dim3(kGM * kGK / 256), dim3(256), 0, stream, w3, qp, sums, dw3);
+  hipLaunchKernelGGL(pool_gram_dw_kernel, dim3(kGM * kGK / 256), dim3(256), 0, stream, w, qp, sums, dw);
   return pn2_launch_status();
 }

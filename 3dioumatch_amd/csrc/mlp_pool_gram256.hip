@@ -788,27 +788,25 @@ static_assert(kDgradLds <= 160 * 1024, "LDS of the data-gradient pass");
 
 }  // namespace
 
-#define MLP_API extern "C" __attribute__((visibility("default")))
-
-// what mlp_pool_gram256_backward covers: (m, k) = (256, 128), nsample 16 / 32, whole 32-column
-// chunks per cloud
-static bool gram256_covers(int b, int m, int k, int r, int ns) {
-  return b > 0 && m == kHM && k == kHK && r > 0 && r % 32 == 0 && (ns == 16 || ns == 32) && r % ns == 0;
+// The (256, 128) half of the mlp_pool_gram_* family (include/mlp_hip.h; exported from
+// mlp_pool_gram.hip, declared to it in mlp_operand.h).
+// what the backward covers: nsample 16 / 32, whole 32-column chunks per cloud
+static bool gram256_covers(int b, int r, int ns) {
+  return b > 0 && r > 0 && r % 32 == 0 && (ns == 16 || ns == 32) && r % ns == 0;
 }
 
-// 1 when the forward should leave the layer's backward to mlp_pool_gram256_backward: covered, and
-// worth it from SA2's size on (B = 8: 8192 chunks; measured: 308 us against 355 there, 154 against
-// 105 at SA3's 2048 chunks -- the two passes' fixed costs).  The threshold is read on every call
-// (tests lower it); the backward does not re-check it, so a forward decision made under one value
-// holds for its backward
-MLP_API int mlp_pool_gram256_supported(int b, int m, int k, int r, int ns) {
+// should the forward leave the layer's backward to this file: covered, and worth it from SA2's size
+// on (B = 8: 8192 chunks; measured: 308 us against 355 there, 154 against 105 at SA3's 2048 chunks --
+// the two passes' fixed costs).  The threshold is read on every call (tests lower it); the backward
+// does not re-check it, so a forward decision made under one value holds for its backward
+bool mlp_pool_gram256_supported(int b, int r, int ns) {
   const long long least = getenv("MLP_POOL_GRAM256_MIN_CHUNKS") ? atoll(getenv("MLP_POOL_GRAM256_MIN_CHUNKS")) : 4096;
-  return gram256_covers(b, m, k, r, ns) && (long long)b * (r / 32) >= least ? 1 : 0;
+  return gram256_covers(b, r, ns) && (long long)b * (r / 32) >= least;
 }
 
 // number of per-workgroup partials of stats_part (128, parts, 2) and floats of workspace
-MLP_API int mlp_pool_gram256_parts(int b, int r) { return gram256_workgroups(b, r, kDgradLeast); }
-MLP_API size_t mlp_pool_gram256_workspace_floats(int b, int r, int ns) {
+int mlp_pool_gram256_parts(int b, int r) { return gram256_workgroups(b, r, kDgradLeast); }
+size_t mlp_pool_gram256_workspace_floats(int b, int r, int ns) {
   const size_t g = (size_t)gram256_workgroups(b, r, kWgradLeast);
   const size_t groups = ns > 0 ? (size_t)(r / ns) : 0;
   // qp (512) + M3 (16384) + v (128) + the records (2 words per group and channel) + partials per
@@ -818,32 +816,25 @@ MLP_API size_t mlp_pool_gram256_workspace_floats(int b, int r, int ns) {
 
 // Backward of the pooled last layer y3 = w3 . relu(bn2(y2)), w3 (256,128), from y2 and the pooled
 // tensors alone: dq (b,128,r) = gradient w.r.t. relu(bn2(y2)); dw3 (256,128); stats_part
-// (128, parts, 2): the BatchNorm-backward sums of layer 2 (for mlp_bn_backward_finalize).  coef3
-// (256,3) = (a, c1, c2) of layer 3 as mlp_bn_relu_pool_backward leaves them.
-MLP_API int mlp_pool_gram256_backward(int b, int r, int ns, const float *w3, const float *y2, const float *sc2,
-                                      const float *sh2, const float *mean2, const float *invstd2,
-                                      const float *coef3, const float *sc3, const float *sh3,
-                                      const float *mean3, const float *invstd3, const int *argmax,
-                                      const float *dpooled, const float *ymax, float *dq, float *dw3,
-                                      float *stats_part, float *workspace, void *stream_) {
-  if (!gram256_covers(b, kHM, kHK, r, ns) || !w3 || !y2 || !sc2 || !sh2 || !mean2 || !invstd2 ||
-      !coef3 || !sc3 || !sh3 || !mean3 || !invstd3 || !argmax || !dpooled || !ymax || !dq || !dw3 ||
-      !stats_part || !workspace || (reinterpret_cast<size_t>(workspace) & 15) ||
-      (reinterpret_cast<size_t>(y2) & 15))
-    return (int)hipErrorInvalidValue;
-  hipStream_t stream = (hipStream_t)stream_;
+// (128, parts, 2): the BatchNorm-backward sums of layer 2 (for mlp_bn_backward_finalize).  dy: layer
+// 3's mode-3 record (no x: y3 does not exist), x: layer 2's mode-1 record with mean / invstd; both
+// through operand_from_abi and every other pointer checked by the caller (mlp_pool_gram_backward)
+int mlp_pool_gram256_launch(int b, int r, const float *w3, const MlpOperand &dy, const MlpOperand &x,
+                            const float *ymax, float *dq, float *dw3, float *stats_part,
+                            float *workspace, hipStream_t stream) {
+  const int ns = dy.ns, groups = dy.groups;
+  if (!gram256_covers(b, r, ns)) return (int)hipErrorInvalidValue;
   const int g1 = gram256_workgroups(b, r, kDgradLeast);
   const int g2 = gram256_workgroups(b, r, kWgradLeast);
   float *qp = workspace, *m3 = qp + 512, *v = m3 + 16384;
-  const int groups = r / ns;
   uint2 *recs = reinterpret_cast<uint2 *>(v + 128);  // (16-byte aligned: 17 024 floats in)
   float *part_c2 = v + 128 + (size_t)b * groups * kHM * 2, *part_s2 = part_c2 + (size_t)g2 * kHK * kHK, *part_r = part_s2 + (size_t)g2 * kHK;
   float *tail = part_r + (size_t)g2 * kHM * kHK;
   double *sums = reinterpret_cast<double *>(tail + ((reinterpret_cast<size_t>(tail) & 7) ? 1 : 0));
-  hipLaunchKernelGGL(pool_gram256_prep_kernel, dim3(kHK), dim3(256), 0, stream, w3, coef3, mean3,
-                     invstd3, qp, m3, v);
+  hipLaunchKernelGGL(pool_gram256_prep_kernel, dim3(kHK), dim3(256), 0, stream, w3, dy.coef, dy.mean,
+                     dy.invstd, qp, m3, v);
   hipLaunchKernelGGL(pool_gram256_pack_kernel, dim3((groups + 31) / 32, kHM / 32, b), dim3(256), 0, stream, groups,
-                     argmax, dpooled, ymax, coef3, sc3, sh3, recs);
+                     dy.argmax, dy.dz, ymax, dy.coef, dy.scale, dy.shift, recs);
   static std::mutex mu;
   static bool attr_set = false;
   {
@@ -862,8 +853,8 @@ MLP_API int mlp_pool_gram256_backward(int b, int r, int ns, const float *w3, con
   }
   Gram256Args a = {};
   a.r = r; a.total_chunks = b * (r / 32); a.chunks_per_cloud = r / 32; a.groups = groups;
-  a.y2 = y2; a.sc2 = sc2; a.sh2 = sh2; a.mean2 = mean2; a.invstd2 = invstd2;
-  a.m3 = m3; a.v = v; a.w3 = w3; a.coef3 = coef3; a.sc3 = sc3; a.sh3 = sh3;
+  a.y2 = x.x; a.sc2 = x.scale; a.sh2 = x.shift; a.mean2 = x.mean; a.invstd2 = x.invstd;
+  a.m3 = m3; a.v = v; a.w3 = w3; a.coef3 = dy.coef; a.sc3 = dy.scale; a.sh3 = dy.shift;
   a.recs = recs;
   a.dq = dq; a.stats_part = stats_part; a.part_c2 = part_c2; a.part_s2 = part_s2; a.part_r = part_r;
   if (ns == 16) {

@@ -192,16 +192,18 @@ def _operand(mode, ns=0, groups=0, **tensors):
     return op
 
 
-def _grad_operand(dy=None, fly=None, pooled=None):
+def _grad_operand(dy=None, fly=None, pooled=None, ns=None):
     """The gradient operand of a layer's backward GEMMs: dy (B,M,...) given (mode 0), or formed on the
     fly from fly = (y, dz, scale, shift, mean, invstd, coef) (mode 2) or from pooled = (y (B,M,m,ns),
-    dpooled, argmax, scale, shift, mean, invstd, coef) (mode 3)."""
+    dpooled, argmax, scale, shift, mean, invstd, coef) (mode 3; y None with ns given: a layer whose raw
+    output was never stored -- pool_gram_backward -- its groups are those of dpooled (B,M,m))."""
     if dy is not None:
         return _operand(0, x=dy)
     if pooled is not None:
         y, dpooled, argmax, scale, shift, mean, invstd, coef = pooled
+        ns, groups = (y.shape[3], y.shape[2]) if y is not None else (ns, dpooled.shape[2])
         return _operand(3, x=y, dz=dpooled, scale=scale, shift=shift, mean=mean, invstd=invstd,
-                        coef=coef, argmax=argmax, ns=y.shape[3], groups=y.shape[2])
+                        coef=coef, argmax=argmax, ns=ns, groups=groups)
     y, dz, scale, shift, mean, invstd, coef = fly
     return _operand(2, x=y, dz=dz, scale=scale, shift=shift, mean=mean, invstd=invstd, coef=coef)
 
@@ -307,6 +309,21 @@ def gemm_forward(w, x, coeff=None):
     return y
 
 
+def _finalize_pairs(c, parts, n_part, pairs, gamma, beta, running_mean, running_var, momentum, eps):
+    """(mean, invstd, scale, shift) of a training-mode BatchNorm over c channels from the (mean, M2)
+    pairs a forward kernel left behind (`parts` per channel, n_part columns each); folds the batch
+    statistics into running_* (either may be None).  The caller has made pairs' device current."""
+    out = torch.empty((4, c), dtype=torch.float32, device=pairs.device)
+    scratch = torch.empty(int(_lib.mlp_bn_finalize_pairs_scratch_bytes(c)), dtype=torch.uint8,
+                          device=pairs.device)
+    _L.check(_lib.mlp_bn_finalize_pairs(c, parts, n_part, pairs.data_ptr(), gamma.data_ptr(),
+                                        beta.data_ptr(), float(eps), float(momentum),
+                                        _ptr(running_mean), _ptr(running_var), out[0].data_ptr(),
+                                        out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
+                                        scratch.data_ptr(), _stream(pairs)), "mlp_bn_finalize_pairs")
+    return out[0], out[1], out[2], out[3]
+
+
 def gemm_forward_bn(w, x, coeff, gamma, beta, running_mean, running_var, momentum, eps, pool=False,
                     tickets=None, store=True):
     """Training-mode layer: y = gemm_forward(w, x, coeff) and the BatchNorm coefficients of y
@@ -335,33 +352,20 @@ def gemm_forward_bn(w, x, coeff, gamma, beta, running_mean, running_var, momentu
         raise RuntimeError("gemm_forward_bn(store=False): the pooled epilogue does not cover this layer")
     y = torch.empty((b, m) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device) if store else None
     pairs = torch.empty((parts, m, 2), dtype=torch.float32, device=x.device)
-    out = torch.empty((4, m), dtype=torch.float32, device=x.device)
-    scratch = torch.empty(int(_lib.mlp_bn_finalize_pairs_scratch_bytes(m)), dtype=torch.uint8,
-                          device=x.device)
-    scale, shift = coeff if coeff is not None else (None, None)
+    op = _input_operand(x, coeff)
     with torch.cuda.device(x.device):
         if pooled:
-            _L.check(_lib.mlp_gemm_forward_stats_pool(b, m, k, r, w.data_ptr(), x.data_ptr(),
-                                                      scale.data_ptr(), shift.data_ptr(),
-                                                      _ptr(y), pairs.data_ptr(), ns,
-                                                      gamma.data_ptr(), ext.data_ptr(), _stream(x)),
+            _L.check(_lib.mlp_gemm_forward_stats_pool(b, m, k, r, w.data_ptr(), ctypes.byref(op), _ptr(y),
+                                                      pairs.data_ptr(), ns, gamma.data_ptr(),
+                                                      ext.data_ptr(), _stream(x)),
                      "mlp_gemm_forward_stats_pool")
         else:
-            op = _input_operand(x, coeff)
             _L.check(_lib.mlp_gemm_forward(b, m, k, r, w.data_ptr(), None, ctypes.byref(op),
                                            y.data_ptr(), pairs.data_ptr(), _stream(x)),
                      "mlp_gemm_forward(pairs)")
-        rm = running_mean.data_ptr() if running_mean is not None else None
-        rv = running_var.data_ptr() if running_var is not None else None
-        _L.check(_lib.mlp_bn_finalize_pairs(m, parts, cols.value, pairs.data_ptr(),
-                                            gamma.data_ptr(), beta.data_ptr(), float(eps),
-                                            float(momentum), rm, rv, out[0].data_ptr(),
-                                            out[1].data_ptr(), out[2].data_ptr(),
-                                            out[3].data_ptr(), scratch.data_ptr(), _stream(x)),
-                 "mlp_bn_finalize_pairs")
-    if pool:
-        return y, out[0], out[1], out[2], out[3], ext
-    return y, out[0], out[1], out[2], out[3]
+        bn = _finalize_pairs(m, parts, cols.value, pairs, gamma, beta, running_mean, running_var,
+                             momentum, eps)
+    return (y,) + bn + ((ext,) if pool else ())
 
 
 def forward_pool_supported(w, x, coeff):
@@ -708,20 +712,13 @@ def gemm_forward_bn_lin4(w, x4, w1, coeff1, gamma, beta, running_mean, running_v
     parts = int(_lib.mlp_gemm_forward_stats_parts(b, m, 64, r, ctypes.byref(cols)))
     y = torch.empty((b, m) + tuple(x4.shape[2:]), dtype=torch.float32, device=x4.device)
     pairs = torch.empty((parts, m, 2), dtype=torch.float32, device=x4.device)
-    out = torch.empty((4, m), dtype=torch.float32, device=x4.device)
-    scratch = torch.empty(int(_lib.mlp_bn_finalize_pairs_scratch_bytes(m)), dtype=torch.uint8,
-                          device=x4.device)
+    op = _input_operand(x4, coeff1, lin_w=w1)
     with torch.cuda.device(x4.device):
-        _L.check(_lib.mlp_gemm_forward_stats_lin4(b, r, w.data_ptr(), x4.data_ptr(), w1.data_ptr(),
-                                                  coeff1[0].data_ptr(), coeff1[1].data_ptr(),
-                                                  y.data_ptr(), pairs.data_ptr(), _stream(x4)),
-                 "mlp_gemm_forward_stats_lin4")
-        _L.check(_lib.mlp_bn_finalize_pairs(m, parts, cols.value, pairs.data_ptr(), gamma.data_ptr(),
-                                            beta.data_ptr(), float(eps), float(momentum),
-                                            _ptr(running_mean), _ptr(running_var), out[0].data_ptr(),
-                                            out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
-                                            scratch.data_ptr(), _stream(x4)), "mlp_bn_finalize_pairs")
-    return y, out[0], out[1], out[2], out[3]
+        _L.check(_lib.mlp_gemm_forward(b, m, 64, r, w.data_ptr(), None, ctypes.byref(op), y.data_ptr(),
+                                       pairs.data_ptr(), _stream(x4)), "mlp_gemm_forward(lin4)")
+        bn = _finalize_pairs(m, parts, cols.value, pairs, gamma, beta, running_mean, running_var,
+                             momentum, eps)
+    return (y,) + bn
 
 
 def chain_lin4_supported(w0, w1, w2, x4, ns):
@@ -786,31 +783,15 @@ def chain_lin4_forward(x4, w0, coeff0, layer1, layer2, store=True, store_last=Tr
     return y1, (out1[0], out1[1], out1[2], out1[3]), y2, (out2[0], out2[1], out2[2], out2[3]), ext
 
 
-def _gram_entry(w):
-    """The C entry points for a pooled last layer of this shape: (128,64) csrc/mlp_pool_gram.hip,
-    (256,128) csrc/mlp_pool_gram256.hip."""
-    shape = tuple(w.shape)
-    if shape == (128, 64):
-        return (_lib.mlp_pool_gram_supported, _lib.mlp_pool_gram_parts, _lib.mlp_pool_gram_workspace_floats,
-                _lib.mlp_pool_gram_backward, "mlp_pool_gram_backward")
-    if shape == (256, 128):
-        return (_lib.mlp_pool_gram256_supported, _lib.mlp_pool_gram256_parts,
-                _lib.mlp_pool_gram256_workspace_floats, _lib.mlp_pool_gram256_backward,
-                "mlp_pool_gram256_backward")
-    return None
-
-
 def pool_gram_supported(w, y_in, ns):
     """Can the backward of the pooled last layer (w (128,64) on y_in (B,64,m,ns), or w (256,128) on
     y_in (B,128,m,ns)) run without that layer's raw output (csrc/mlp_pool_gram.hip,
     csrc/mlp_pool_gram256.hip)?  Only the (B, *, m, ns) extent of y_in is looked at: y_in may be that
     shape as a tuple (the forward decides before the layer's input exists)."""
-    entry = _gram_entry(w)
     shape = y_in if isinstance(y_in, tuple) else tuple(y_in.shape)
-    if entry is None or len(shape) != 4:
+    if w.dim() != 2 or len(shape) != 4:
         return False
-    b, r = shape[0], shape[2] * shape[3]
-    return bool(entry[0](b, w.shape[0], w.shape[1], r, int(ns)))
+    return bool(_lib.mlp_pool_gram_supported(shape[0], w.shape[0], w.shape[1], shape[2] * shape[3], int(ns)))
 
 
 def pool_gram_backward(w, y_in, in_coeff, in_gamma, coef, coeff, dpooled, argmax, ymax, ns, training):
@@ -820,31 +801,28 @@ def pool_gram_backward(w, y_in, in_coeff, in_gamma, coef, coeff, dpooled, argmax
     layer's BatchNorm; dpooled / argmax / ymax (B,M,m); (M,K) = (128,64) or (256,128).
     -> (d relu(bn(y_in)) (B,K,m,ns), dw (M,K), below = (dgamma, dbeta, coef) of the layer below)."""
     _f32c(w, "w"); _f32c(y_in, "y_in"); _f32c(dpooled, "dpooled"); _f32c(ymax, "ymax")
-    entry = _gram_entry(w)
-    if entry is None or y_in.shape[1] != w.shape[1]:
-        raise RuntimeError("pool_gram_backward: layer shape %s not covered" % (tuple(w.shape),))
-    _, parts_fn, ws_fn, backward_fn, name = entry
     mo, k = w.shape
     b = y_in.shape[0]
     r = y_in.numel() // (b * k)
+    parts = int(_lib.mlp_pool_gram_parts(b, mo, k, r))
+    if parts <= 0 or y_in.shape[1] != k:
+        raise RuntimeError("pool_gram_backward: layer shape %s not covered" % (tuple(w.shape),))
     dev = y_in.device
     mean_i, invstd_i, scale_i, shift_i = in_coeff
     mean, invstd, scale, shift = coeff
-    parts = int(parts_fn(b, r))
+    p = _grad_operand(pooled=(None, dpooled, argmax, scale, shift, mean, invstd, coef), ns=ns)
+    q = _input_operand(y_in, (scale_i, shift_i), (mean_i, invstd_i))
     dq = torch.empty_like(y_in)
     dw = torch.empty((mo, k), dtype=torch.float32, device=dev)
     sp = torch.empty((k, parts, 2), dtype=torch.float32, device=dev)
     small = torch.empty((5, k), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        ws_floats = ws_fn(b, r, int(ns)) if mo == 256 else ws_fn(b, r)
-        ws = torch.empty(int(ws_floats), dtype=torch.float32, device=dev)
+        ws = torch.empty(int(_lib.mlp_pool_gram_workspace_floats(b, mo, k, r, int(ns))), dtype=torch.float32,
+                         device=dev)
         st = _stream(y_in)
-        _L.check(backward_fn(b, r, int(ns), w.data_ptr(), y_in.data_ptr(), scale_i.data_ptr(),
-                             shift_i.data_ptr(), mean_i.data_ptr(), invstd_i.data_ptr(),
-                             coef.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                             mean.data_ptr(), invstd.data_ptr(), argmax.data_ptr(),
-                             dpooled.data_ptr(), ymax.data_ptr(), dq.data_ptr(),
-                             dw.data_ptr(), sp.data_ptr(), ws.data_ptr(), st), name)
+        _L.check(_lib.mlp_pool_gram_backward(b, mo, k, r, w.data_ptr(), ctypes.byref(p), ctypes.byref(q),
+                                             ymax.data_ptr(), dq.data_ptr(), dw.data_ptr(), sp.data_ptr(),
+                                             ws.data_ptr(), st), "mlp_pool_gram_backward")
         _L.check(_lib.mlp_bn_backward_finalize(k, parts, float(b) * float(r), 1 if training else 0,
                                                sp.data_ptr(), in_gamma.data_ptr(), invstd_i.data_ptr(),
                                                small[0].data_ptr(), small[1].data_ptr(), small[2:].data_ptr(),
@@ -899,17 +877,7 @@ def pregather_forward(z_ext, idx, n, stats=None):
                  "mlp_pregather_forward")
         if not stats:
             return y
-        gamma, beta, running_mean, running_var, momentum, eps = stats
-        out = torch.empty((4, c), dtype=torch.float32, device=z_ext.device)
-        scratch = torch.empty(int(_lib.mlp_bn_finalize_pairs_scratch_bytes(c)), dtype=torch.uint8,
-                              device=z_ext.device)
-        _L.check(_lib.mlp_bn_finalize_pairs(c, b, m * ns, pairs.data_ptr(), gamma.data_ptr(),
-                                            beta.data_ptr(), float(eps), float(momentum),
-                                            _ptr(running_mean), _ptr(running_var),
-                                            out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                                            out[3].data_ptr(), scratch.data_ptr(), _stream(z_ext)),
-                 "mlp_bn_finalize_pairs")
-    return y, out[0], out[1], out[2], out[3]
+        return (y,) + _finalize_pairs(c, b, m * ns, pairs, *stats)
 
 
 def pregather_backward(fly, inverse, n):

@@ -107,10 +107,13 @@ int mlp_bn_relu_backward_stats(int b, int c, int r, int training, const float *y
  *   mode 3  the same for the pooled last layer of a set-abstraction MLP (F.max_pool2d backward first,
  *           pointnet2_modules.py:256-262): x = y (b, rows, groups, ns), dz = dpooled and argmax
  *           (b, rows, groups), ns, groups, the vectors of mode 2 with coef as
- *           mlp_bn_relu_pool_backward(dy = NULL) leaves it -- neither dz nor dy is written to memory
+ *           mlp_bn_relu_pool_backward(dy = NULL) leaves it -- neither dz nor dy is written to memory.
+ *           mlp_pool_gram_backward alone does not read x (that y was never stored): NULL is valid there
  *   mode 4  the output of a VIRTUAL 4 -> rows first layer, never stored: x is that layer's input
  *           (b, 4, r), lin_w its weight (rows, 4), (scale, shift) its BatchNorm; the operand
- *           relu((lin_w . x)*scale + shift) is recomputed; mean / invstd as for mode 1 */
+ *           relu((lin_w . x)*scale + shift) is recomputed; mean / invstd as for mode 1
+ * Not operands, hence loose arguments: mlp_chain_lin4_* and mlp_eval_*_pool take weight IMAGES and
+ * folded per-channel (scale, shift) pairs -- no tensor transformed on its way into a GEMM. */
 typedef struct MlpOperand {
   int mode;
   const float *x;
@@ -129,7 +132,10 @@ typedef struct MlpOperand {
 /* forward: y = W * x (replaces nn.Conv2d of a shared-MLP layer, pytorch_utils.py:70-124); x: mode 0
  * or 1.  img (may be NULL): the weight ALSO as the bf16 image of mlp_weight_images_build below
  * (needs mlp_gemm_image_supported).  pairs (may be NULL): parts x m x 2 floats, the BatchNorm
- * statistics as a by-product (needs mlp_gemm_forward_stats_parts > 0).  Not both. */
+ * statistics as a by-product (needs mlp_gemm_forward_stats_parts > 0).  Not both.
+ * x in mode 4: the SECOND layer (64 -> 64) of a chain whose first layer is virtual (conv + BatchNorm
+ * + ReLU + conv of pytorch_utils.py:14-39 for SA1's first two layers); only with pairs, without img,
+ * (m, k) = (64, 64), w and lin_w 16-byte aligned. */
 int mlp_gemm_forward(int b, int m, int k, int r, const float *w, const void *img,
                      const MlpOperand *x, float *y, float *pairs, void *stream);
 
@@ -170,14 +176,14 @@ int mlp_gemm_wgrad(int b, int m, int k, int r, const MlpOperand *dy, const MlpOp
 /* 1 when mlp_gemm_forward_stats_pool covers the layer: m 128 or 256, ns 16 / 32 / 64, k % 4 == 0
  * and the epilogue statistics available (dispatch helper for pointnet2_modules.py:256-262) */
 int mlp_gemm_forward_stats_pool_supported(int b, int m, int k, int r, int ns);
-/* mlp_gemm_forward with pairs (x mode 1) that also writes ext: 2 planes of (b, m, r/ns) -- the raw output
+/* mlp_gemm_forward with pairs (x: mode 1 only) that also writes ext: 2 planes of (b, m, r/ns) -- the raw output
  * that wins the pool per channel and group of ns columns (the largest where gamma >= 0, the
  * smallest where gamma < 0: gamma = the weight of the BatchNorm that follows) and its first
  * index (replaces the read of y in the max-pool of pointnet2_modules.py:256-262).  y may be NULL:
- * the raw output is then not stored at all (its backward: mlp_pool_gram256_backward) */
-int mlp_gemm_forward_stats_pool(int b, int m, int k, int r, const float *w, const float *x,
-                                const float *scale, const float *shift, float *y, float *pairs,
-                                int ns, const float *gamma, float *ext, void *stream);
+ * the raw output is then not stored at all (its backward: mlp_pool_gram_backward) */
+int mlp_gemm_forward_stats_pool(int b, int m, int k, int r, const float *w, const MlpOperand *x,
+                                float *y, float *pairs, int ns, const float *gamma, float *ext,
+                                void *stream);
 /* ---- a set-abstraction module's shared MLP as a register chain (csrc/mlp_chain.hip) -----------
  * conv(1x1) -> BatchNorm -> ReLU -> conv(1x1) -> [statistics, max over nsample] for the SA1 shape
  * 4 -> 64 -> 64 -> 128 (pytorch_utils.py:14-39,70-124; the max-pool of pointnet2_modules.py:256-262):
@@ -211,44 +217,32 @@ int mlp_chain_finalize(int c, int parts, int n_part, const float *pairs, const f
                        const float *beta, float eps, float momentum, float *running_mean,
                        float *running_var, float *mean, float *invstd, float *scale, float *shift,
                        void *stream);
-/* ---- backward of a max-pooled last layer WITHOUT its raw output (csrc/mlp_pool_gram.hip) -------
- * For (m, k) = (128, 64) (SA1's last layer; pytorch_utils.py:14-39,70-124 with the max-pool of
- * pointnet2_modules.py:256-262): dy3 = q y3 + p + S with y3 = w3 a2 turns both backward products
- * into functions of the layer's input a2 = relu(bn2(y2)), the 64 x 64 matrices W3^T diag(q) W3 and
- * a2 a2^T, and one sparse column per (channel, group) -- y3 is neither read nor stored.
- * mlp_pool_gram_supported: 1 when the layer is covered (ns 16 / 32 / 64, r % 32 == 0). */
+/* ---- backward of a max-pooled last layer WITHOUT its raw output ------------------------------
+ * For (m, k) = (128, 64) (SA1's last layer, csrc/mlp_pool_gram.hip) and (256, 128) (SA2 / SA3 / SA4,
+ * csrc/mlp_pool_gram256.hip: two passes over the input); pytorch_utils.py:14-39,70-124 with the
+ * max-pool of pointnet2_modules.py:256-262.  dy = q y + p + S with y = w a (a = relu(bn(x)), the
+ * layer's input) turns both backward products into functions of a, the k x k matrices
+ * W^T diag(q) W and a a^T, and one sparse column per (channel, group) -- y is neither read nor stored.
+ * Any other (m, k): not covered (0, 0, 0, hipErrorInvalidValue below).
+ * mlp_pool_gram_supported: 1 when the forward may leave the layer to mlp_pool_gram_backward:
+ * r % 32 == 0 and (128, 64): ns 16 / 32 / 64, at least 64 chunks of 32 columns; (256, 128): ns 16 /
+ * 32, at least MLP_POOL_GRAM256_MIN_CHUNKS chunks (environment, read on every call; default 4096). */
 int mlp_pool_gram_supported(int b, int m, int k, int r, int ns);
-/* per-workgroup partials = parts of stats_part (64, parts, 2) (the autograd of nn.BatchNorm2d,
+/* per-workgroup partials = parts of stats_part (k, parts, 2) (the autograd of nn.BatchNorm2d,
  * pytorch_utils.py:42-67) */
-int mlp_pool_gram_parts(int b, int r);
+int mlp_pool_gram_parts(int b, int m, int k, int r);
 /* floats of 16-byte aligned workspace of mlp_pool_gram_backward (autograd of nn.Conv2d,
  * pytorch_utils.py:70-124) */
-size_t mlp_pool_gram_workspace_floats(int b, int r);
-/* dq (b,64,r) = gradient w.r.t. relu(bn2(y2)), dw3 (128,64), stats_part (64,parts,2) = layer 2's
- * BatchNorm-backward sums; y2 (b,64,r) raw, (sc2, sh2, mean2, invstd2) layer 2's BatchNorm,
- * coef3 (128,3) / (sc3, sh3, mean3, invstd3) layer 3's, argmax / dpooled / ymax (b,128,r/ns) the
- * pooled tensors (autograd of pytorch_utils.py:14-39 + pointnet2_modules.py:256-262) */
-int mlp_pool_gram_backward(int b, int r, int ns, const float *w3, const float *y2, const float *sc2,
-                           const float *sh2, const float *mean2, const float *invstd2,
-                           const float *coef3, const float *sc3, const float *sh3, const float *mean3,
-                           const float *invstd3, const int *argmax, const float *dpooled,
-                           const float *ymax, float *dq, float *dw3, float *stats_part,
-                           float *workspace, void *stream);
-/* The same for (m, k) = (256, 128) -- the last layer of SA2 / SA3 / SA4 (pointnet2_modules.py:256-262
- * after pytorch_utils.py:14-39,70-124), ns 16 / 32 (csrc/mlp_pool_gram256.hip: two passes over y2,
- * data gradient + BatchNorm-backward sums of the layer below, then weight-gradient sums).
- * mlp_pool_gram256_parts: parts of stats_part (128, parts, 2). */
-int mlp_pool_gram256_supported(int b, int m, int k, int r, int ns);
-int mlp_pool_gram256_parts(int b, int r);
-size_t mlp_pool_gram256_workspace_floats(int b, int r, int ns);
-/* dq (b,128,r), dw3 (256,128), stats_part (128,parts,2); y2 (b,128,r) raw; coef3 (256,3); argmax /
- * dpooled / ymax (b,256,r/ns) (autograd of pytorch_utils.py:14-39 + pointnet2_modules.py:256-262) */
-int mlp_pool_gram256_backward(int b, int r, int ns, const float *w3, const float *y2, const float *sc2,
-                              const float *sh2, const float *mean2, const float *invstd2,
-                              const float *coef3, const float *sc3, const float *sh3,
-                              const float *mean3, const float *invstd3, const int *argmax,
-                              const float *dpooled, const float *ymax, float *dq, float *dw3,
-                              float *stats_part, float *workspace, void *stream);
+size_t mlp_pool_gram_workspace_floats(int b, int m, int k, int r, int ns);
+/* dq (b,k,r) = gradient w.r.t. relu(bn(x)), dw (m,k), stats_part (k,parts,2) = the BatchNorm-backward
+ * sums of the layer below (autograd of pytorch_utils.py:14-39 + pointnet2_modules.py:256-262).
+ * dy: mode 3 only, x ignored (may be NULL); x: mode 1 only, with mean / invstd -- the pair
+ * mlp_gemm_backward_fused takes for this layer when its raw output was stored; x->x 16-byte aligned.
+ * ymax (b,m,r/ns): the pre-activation that won the pool (mlp_bn_pool_from_extrema).  (256, 128) asks
+ * for coverage only, not for the threshold of mlp_pool_gram_supported. */
+int mlp_pool_gram_backward(int b, int m, int k, int r, const float *w, const MlpOperand *dy,
+                           const MlpOperand *x, const float *ymax, float *dq, float *dw,
+                           float *stats_part, float *workspace, void *stream);
 /* pooled, argmax, ymax (b,c,groups) as mlp_bn_relu_pool returns them, from ext
  * (replaces F.max_pool2d of pointnet2_modules.py:256-262 after BatchNorm + ReLU) */
 int mlp_bn_pool_from_extrema(int b, int c, int groups, const float *ext, const float *scale,
@@ -373,17 +367,12 @@ int mlp_first4_moments_doubles(void);
 int mlp_first4_moments(int b, int r, const float *x, double *moments, void *stream);
 /* training-mode BatchNorm2d (pytorch_utils.py:42-50) of y = w x, w (64,4), from the moments of x
  * over count = b*r columns: mean, invstd, scale, shift (64) and the running-statistics update, as
- * mlp_bn_finalize_pairs -- without y */
+ * mlp_bn_finalize_pairs -- without y; the second layer then reads x through MlpOperand mode 4
+ * (mlp_gemm_forward) */
 int mlp_first4_bn(const double *moments, double count, const float *w, const float *gamma,
                   const float *beta, float eps, float momentum, float *running_mean,
                   float *running_var, float *mean, float *invstd, float *scale, float *shift,
                   void *stream);
-/* mlp_gemm_forward with pairs for the SECOND layer (64 -> 64) of such a chain: the operand
- * relu(bn(w1 x4)) is recomputed from x4 (b,4,r); the first layer's output is never stored
- * (replaces conv + BatchNorm + ReLU + conv of pytorch_utils.py:14-39 for SA1's first two layers) */
-int mlp_gemm_forward_stats_lin4(int b, int r, const float *w, const float *x4, const float *w1,
-                                const float *scale, const float *shift, float *y, float *pairs,
-                                void *stream);
 /* bytes of the workspace of mlp_wgrad_first4 (sizing helper for the backward-weight of
  * pytorch_utils.py:70-124) */
 size_t mlp_wgrad_first4_workspace_bytes(int b, int r);
