@@ -38,6 +38,10 @@ _SIGNATURES = {
     "pn2_three_interpolate": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "pn2_three_interpolate_affine_supported": [_c_int, _c_int, _c_int],
     "pn2_three_interpolate_affine": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_three_interpolate_affine_ld": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp,
+                                        _vp],
+    "pn2_three_interpolate_rows_into": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int,
+                                        _vp, _c_int, _c_int, _vp],
     "pn2_three_interpolate_grad": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "pn2_three_nn_weights": [ctypes.c_longlong, _vp, _vp, _vp],
     "pn2_multi_copy": [_c_int, _vp, ctypes.c_longlong, _vp],
@@ -82,6 +86,7 @@ _SIGNATURES = {
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     # the GEMM family: (b, m, k, r), then pointers; _op = a MlpOperand record
     "mlp_gemm_forward": [_c_int] * 4 + [_vp, _vp, _op, _vp, _vp, _vp],
+    "mlp_gemm_forward_small": [_c_int] * 4 + [_vp, _c_int, _vp, _op, _vp, _vp, _vp],
     "mlp_gemm_forward_stats_parts": [_c_int, _c_int, _c_int, _c_int, _vp],
     "mlp_bn_finalize_pairs": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_float, _c_float, _vp, _vp,
                               _vp, _vp, _vp, _vp, _vp, _vp],
@@ -155,6 +160,9 @@ _SIGNATURES = {
     "votenet_gridconv_points": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "votenet_iou_opt_box_step": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _c_float, _vp, _vp, _vp, _vp],
+    "votenet_vote_tail": [_c_int, _c_int, _c_int] + [_vp] * 7,
+    "votenet_vote_tail_grad": [_c_int, _c_int, _c_int] + [_vp] * 8,
+    "votenet_iou_score_slices_grad": [_c_int] * 5 + [_vp] * 4,
     "votenet_channel_normalize": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp],
     "votenet_channel_normalize_grad": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp],
     "votenet_adam_step": [ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,

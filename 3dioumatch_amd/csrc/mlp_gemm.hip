@@ -598,7 +598,8 @@ __device__ __forceinline__ void gemm_nn_small_body(int blk_x, int blk_y, int blk
                                                    int r, const float *__restrict__ a, int lda,
                                                    OperandB opb, float *__restrict__ c,
                                                    size_t b_stride_in, size_t b_stride_out,
-                                                   const AImage img = AImage{nullptr, 0, 0}) {
+                                                   const AImage img = AImage{nullptr, 0, 0},
+                                                   const float *__restrict__ bias = nullptr) {
   constexpr int TM = 64, TN = 64, LDA = TM + 1;
   constexpr int STAGE = KS * LDA + KS * TN, REDUCE = 4 * 16 * 64;
   __shared__ __attribute__((aligned(16))) float lds[STAGE > REDUCE ? STAGE : REDUCE];
@@ -716,6 +717,17 @@ __device__ __forceinline__ void gemm_nn_small_body(int blk_x, int blk_y, int blk
     }
     }
   }
+  // (bias: wave 0's 32 rows of it, requested here so that they arrive behind the cross-wave sum)
+  float bv[2][16];
+  if (bias != nullptr && wave == 0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int row = m0 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+        bv[i][q] = bias[row < m_total ? row : m_total - 1];
+      }
+  }
   for (int s = 1; s < 4; ++s) {  // waves 1..3 hand their accumulators to wave 0
     __syncthreads();
     if (wave == s) {
@@ -746,7 +758,11 @@ __device__ __forceinline__ void gemm_nn_small_body(int blk_x, int blk_y, int blk
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const int row = m0 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-        if (row < m_total && col < r) __builtin_nontemporal_store(acc[i][j][q], &cb[(size_t)row * r + col]);
+        if (row < m_total && col < r) {
+          // (bias: a convolution's, added to the finished sum as the separate pass over y did)
+          const float v = bias != nullptr ? acc[i][j][q] + bv[i][q] : acc[i][j][q];
+          __builtin_nontemporal_store(v, &cb[(size_t)row * r + col]);
+        }
       }
     }
 }
@@ -758,6 +774,18 @@ gemm_nn_small_kernel(int m_total, int k_total, int r, const float *__restrict__ 
                      size_t b_stride_out, AImage img) {
   gemm_nn_small_body<MODE, A_TRANS, X6, AIMG>((int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, m_total,
                                               k_total, r, a, lda, opb, c, b_stride_in, b_stride_out, img);
+}
+
+// The forward form with a per-row bias in its store (the last layer of a head: nn.Conv1d with bias).
+// A kernel of its own, so that the layers without one run the code they ran before.
+template <int MODE, bool AIMG>
+__global__ void __launch_bounds__(256, 1)
+gemm_nn_small_bias_kernel(int m_total, int k_total, int r, const float *__restrict__ a, int lda,
+                          OperandB opb, float *__restrict__ c, size_t b_stride_in,
+                          size_t b_stride_out, AImage img, const float *__restrict__ bias) {
+  gemm_nn_small_body<MODE, false, true, AIMG>((int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, m_total,
+                                              k_total, r, a, lda, opb, c, b_stride_in, b_stride_out, img,
+                                              bias);
 }
 
 // Partial wgrad: for one cloud b and one slice of R,
@@ -1439,6 +1467,42 @@ MLP_API int mlp_gemm_forward(int b, int m, int k, int r, const float *w, const v
                                 pairs, ai);
   return launch_nn<OP_BNRELU>(b, m, k, r, w, k, op, y, in_stride, out_stride, (hipStream_t)stream_,
                               pairs, ai);
+}
+
+// mlp_gemm_forward of a SMALL layer (mlp_gemm_image_supported(b, r)) whose weight is a view of a wider
+// row-major matrix -- row i starts at w + i * ldw, ldw >= k (a column slice, read in place) -- and / or
+// with a bias (m) added to every finished output element (may be NULL).  img: as mlp_gemm_forward,
+// of a weight with ldw == k only.
+MLP_API int mlp_gemm_forward_small(int b, int m, int k, int r, const float *w, int ldw, const void *img,
+                                   const MlpOperand *x, const float *bias, float *y, void *stream_) {
+  if (b <= 0 || m <= 0 || k <= 0 || r <= 0) return 0;
+  OperandB op;
+  const int rc = operand_from_abi(x, op_bit(OP_DIRECT) | op_bit(OP_BNRELU), r, &op);
+  if (rc) return rc;
+  if (!mlp_gemm_image_supported(b, r) || ldw < k || (img && ldw != k)) return (int)hipErrorInvalidValue;
+  const size_t in_stride = (size_t)k * r, out_stride = (size_t)m * r;
+  hipStream_t stream = (hipStream_t)stream_;
+  const AImage ai = {reinterpret_cast<const unsigned short *>(img), img ? pad64(k) : 0,
+                     img ? (size_t)pad64(m) * pad64(k) : 0};
+  if (!bias) {
+    if (x->mode == OP_DIRECT)
+      return launch_nn<OP_DIRECT>(b, m, k, r, w, ldw, op, y, in_stride, out_stride, stream, nullptr, ai);
+    return launch_nn<OP_BNRELU>(b, m, k, r, w, ldw, op, y, in_stride, out_stride, stream, nullptr, ai);
+  }
+  const dim3 grid(pn2_ceil_div(r, 64), pn2_ceil_div(m, 64), b);
+#define BIAS_FORM(MODE)                                                                                  \
+  do {                                                                                                   \
+    if (img)                                                                                             \
+      hipLaunchKernelGGL((gemm_nn_small_bias_kernel<MODE, true>), grid, dim3(256), 0, stream, m, k, r, w, \
+                         ldw, op, y, in_stride, out_stride, ai, bias);                                   \
+    else                                                                                                 \
+      hipLaunchKernelGGL((gemm_nn_small_bias_kernel<MODE, false>), grid, dim3(256), 0, stream, m, k, r,  \
+                         w, ldw, op, y, in_stride, out_stride, ai, bias);                                \
+  } while (0)
+  if (x->mode == OP_DIRECT) BIAS_FORM(OP_DIRECT);
+  else BIAS_FORM(OP_BNRELU);
+#undef BIAS_FORM
+  return pn2_launch_status();
 }
 
 // 1 when mlp_gemm_forward_stats_pool covers the pooled last layer: statistics from the epilogue

@@ -144,6 +144,30 @@ three_nn_split_kernel(int n, int m, const float *__restrict__ unknown,
   }
 }
 
+// Rows copied next to an interpolated channel block in the SAME launch (the concatenations of
+// pointnet2_modules.py:404-410 and grid_conv_module.py:87-110): src (b, rows, n) contiguous -> dst, the
+// first of `rows` channels inside the (b, c_total, n) output (bstride = c_total * n floats).  The
+// interpolation kernels' grids carry extra workgroups along y for them: group g of ng copies rows
+// g, g + ng, ... of the workgroup's column range, JP floats per lane (JP = 4: 16-byte copies).
+struct RowCopy {
+  const float *src;
+  float *dst;
+  int rows;
+  size_t bstride;
+};
+
+template <int JP>
+__device__ __forceinline__ void copy_rows(const RowCopy &rc, int n, int b, int g, int ng, int xblk) {
+  const int j0 = (xblk * 256 + (int)threadIdx.x) * JP;
+  if (j0 >= n) return;
+  for (int row = g; row < rc.rows; row += ng) {
+    const float *src = rc.src + ((size_t)b * rc.rows + row) * n + j0;
+    float *dst = rc.dst + (size_t)b * rc.bstride + (size_t)row * n + j0;
+    if (JP == 4) *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(src);
+    else dst[0] = src[0];
+  }
+}
+
 // out[b,l,j] = p[i1]*w1 + p[i2]*w2 + p[i3]*w3, left to right (interpolate_gpu.cu:77-106).
 // A lane owns JP consecutive query points (JP = 4 -> one 16-byte store per channel) and
 // walks a group of channels, so 12 independent gathers are in flight per channel step.
@@ -151,9 +175,13 @@ template <int JP>
 __global__ void __launch_bounds__(256)
 three_interpolate_kernel(int c, int m, int n, const float *__restrict__ points,
                          const int *__restrict__ idx, const float *__restrict__ weight,
-                         float *__restrict__ out, size_t out_bstride) {
+                         float *__restrict__ out, size_t out_bstride, int ygroups, RowCopy rc) {
   const BlockId blk = xcd_block_id();
   const int b = blk.z;
+  if (blk.y >= ygroups) {  // (only with rows to copy: gridDim.y == ygroups otherwise)
+    copy_rows<JP>(rc, n, b, blk.y - ygroups, (int)gridDim.y - ygroups, blk.x);
+    return;
+  }
   const int j0 = (blk.x * 256 + threadIdx.x) * JP;
   if (j0 >= n) return;
   int ii[JP][3];
@@ -166,7 +194,7 @@ three_interpolate_kernel(int c, int m, int n, const float *__restrict__ points,
 #pragma unroll
     for (int q = 0; q < 3; ++q) { ii[t][q] = ib[q]; ww[t][q] = wb[q]; }
   }
-  for (int l = blk.y; l < c; l += gridDim.y) {
+  for (int l = blk.y; l < c; l += ygroups) {
     const float *src = points + ((size_t)b * c + l) * m;
     float r[JP];
 #pragma unroll
@@ -191,9 +219,14 @@ template <int CPW>
 __global__ void __launch_bounds__(256)
 three_interpolate_lds_kernel(int c, int m, int n, const float *__restrict__ points,
                              const int *__restrict__ idx, const float *__restrict__ weight,
-                             float *__restrict__ out, size_t out_bstride) {
+                             float *__restrict__ out, size_t out_bstride, RowCopy rc) {
   extern __shared__ __attribute__((aligned(16))) float rows[];
   const BlockId blk = xcd_block_id();
+  const int ygroups = (c + CPW - 1) / CPW;
+  if (blk.y >= ygroups) {  // (only with rows to copy: gridDim.y == ygroups otherwise)
+    copy_rows<4>(rc, n, blk.z, blk.y - ygroups, (int)gridDim.y - ygroups, blk.x);
+    return;
+  }
   const int b = blk.z, l0 = blk.y * CPW;
   const int nc = c - l0 < CPW ? c - l0 : CPW;
   const float *src = points + ((size_t)b * c + l0) * m;
@@ -235,8 +268,8 @@ template <int CPW>
 __global__ void __launch_bounds__(256)
 three_interpolate_affine_lds_kernel(int c, int m, int n, const float *__restrict__ points,
                                     const int *__restrict__ idx, const float *__restrict__ weight,
-                                    const float *__restrict__ aw, const float *__restrict__ ax,
-                                    float *__restrict__ out) {
+                                    const float *__restrict__ aw, int aw_ld,
+                                    const float *__restrict__ ax, float *__restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float rows[];
   const BlockId blk = xcd_block_id();
   const int b = blk.z, l0 = blk.y * CPW;
@@ -260,7 +293,8 @@ three_interpolate_affine_lds_kernel(int c, int m, int n, const float *__restrict
   for (int cc = 0; cc < CPW; ++cc) {
     if (cc < nc) {
       const float *row = rows + cc * m;
-      const float a0 = aw[(l0 + cc) * 3], a1 = aw[(l0 + cc) * 3 + 1], a2 = aw[(l0 + cc) * 3 + 2];
+      const float *awr = aw + (size_t)(l0 + cc) * aw_ld;
+      const float a0 = awr[0], a1 = awr[1], a2 = awr[2];
       float r[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -371,27 +405,32 @@ PN2_API int pn2_three_nn(int b, int n, int m, const float *unknown, const float 
 }
 
 // out may be a channel slice of a wider (b, C_total, n) tensor: out_bstride = C_total * n floats
+// rc.rows > 0: those rows are copied by extra workgroups of the same launch (RowCopy)
 static int interpolate_run(int b, int c, int m, int n, const float *points, const int *idx,
                            const float *weight, float *out, size_t out_bstride,
-                           hipStream_t stream) {
+                           hipStream_t stream, const RowCopy rc = RowCopy{nullptr, nullptr, 0, 0}) {
   if (b <= 0 || c <= 0 || n <= 0) return 0;
-  const bool vec = n % 4 == 0 && out_bstride % 4 == 0 && (reinterpret_cast<size_t>(out) & 15) == 0;
+  bool vec = n % 4 == 0 && out_bstride % 4 == 0 && (reinterpret_cast<size_t>(out) & 15) == 0;
+  if (rc.rows > 0)
+    vec = vec && ((reinterpret_cast<size_t>(rc.src) | reinterpret_cast<size_t>(rc.dst)) & 15) == 0;
+  const int copy_groups = rc.rows > 0 ? interp_channel_groups(rc.rows) : 0;
   if (vec && n >= 2048 && m > 0 && m <= 2048) {  // 8 source rows fit 64 KB of LDS
     constexpr int CPW = 8;
-    dim3 grid(pn2_ceil_div(n, 1024), pn2_ceil_div(c, CPW), b);
+    dim3 grid(pn2_ceil_div(n, 1024), pn2_ceil_div(c, CPW) + copy_groups, b);
     hipLaunchKernelGGL(three_interpolate_lds_kernel<CPW>, grid, dim3(256),
                        sizeof(float) * (size_t)CPW * m, stream, c, m, n, points, idx, weight, out,
-                       out_bstride);
+                       out_bstride, rc);
     return pn2_launch_status();
   }
+  const int ygroups = interp_channel_groups(c);
   if (vec) {
-    dim3 grid(pn2_ceil_div(n, 1024), interp_channel_groups(c), b);
+    dim3 grid(pn2_ceil_div(n, 1024), ygroups + copy_groups, b);
     hipLaunchKernelGGL(three_interpolate_kernel<4>, grid, dim3(256), 0, stream, c, m, n, points,
-                       idx, weight, out, out_bstride);
+                       idx, weight, out, out_bstride, ygroups, rc);
   } else {
-    dim3 grid(pn2_ceil_div(n, 256), interp_channel_groups(c), b);
+    dim3 grid(pn2_ceil_div(n, 256), ygroups + copy_groups, b);
     hipLaunchKernelGGL(three_interpolate_kernel<1>, grid, dim3(256), 0, stream, c, m, n, points,
-                       idx, weight, out, out_bstride);
+                       idx, weight, out, out_bstride, ygroups, rc);
   }
   return pn2_launch_status();
 }
@@ -422,11 +461,12 @@ PN2_API int pn2_three_interpolate_affine_supported(int c, int m, int n) {
   return c > 0 && m > 0 && m <= 2048 && n >= 4 && n % 4 == 0;
 }
 
-PN2_API int pn2_three_interpolate_affine(int b, int c, int m, int n, const float *points, const int *idx,
-                                         const float *weight, const float *affine_w,
-                                         const float *affine_x, float *out, void *stream_) {
+// affine_w as a view of a wider row-major matrix: row l starts at affine_w + l * affine_w_ld
+PN2_API int pn2_three_interpolate_affine_ld(int b, int c, int m, int n, const float *points, const int *idx,
+                                            const float *weight, const float *affine_w, int affine_w_ld,
+                                            const float *affine_x, float *out, void *stream_) {
   if (b <= 0) return 0;
-  if (!pn2_three_interpolate_affine_supported(c, m, n) || !affine_w || !affine_x ||
+  if (!pn2_three_interpolate_affine_supported(c, m, n) || !affine_w || !affine_x || affine_w_ld < 3 ||
       (reinterpret_cast<size_t>(out) & 15) || (reinterpret_cast<size_t>(affine_x) & 15) ||
       (reinterpret_cast<size_t>(idx) & 15) || (reinterpret_cast<size_t>(weight) & 15))
     return (int)hipErrorInvalidValue;
@@ -434,8 +474,15 @@ PN2_API int pn2_three_interpolate_affine(int b, int c, int m, int n, const float
   dim3 grid(pn2_ceil_div(n, 1024), pn2_ceil_div(c, CPW), b);
   hipLaunchKernelGGL(three_interpolate_affine_lds_kernel<CPW>, grid, dim3(256),
                      sizeof(float) * (size_t)CPW * m, (hipStream_t)stream_, c, m, n, points, idx, weight,
-                     affine_w, affine_x, out);
+                     affine_w, affine_w_ld, affine_x, out);
   return pn2_launch_status();
+}
+
+PN2_API int pn2_three_interpolate_affine(int b, int c, int m, int n, const float *points, const int *idx,
+                                         const float *weight, const float *affine_w,
+                                         const float *affine_x, float *out, void *stream_) {
+  return pn2_three_interpolate_affine_ld(b, c, m, n, points, idx, weight, affine_w, 3, affine_x, out,
+                                         stream_);
 }
 
 PN2_API int pn2_three_interpolate(int b, int c, int m, int n, const float *points,
@@ -462,6 +509,24 @@ PN2_API int pn2_three_interpolate_into(int b, int c, int m, int n, const float *
   if (c_total < c) return (int)hipErrorInvalidValue;
   return interpolate_run(b, c, m, n, points, idx, weight, out, (size_t)c_total * n,
                          (hipStream_t)stream_);
+}
+
+// pn2_three_interpolate_into at channels [channel0, channel0 + c) of out (b, c_total, n) -- `out` is
+// the tensor's base here -- and, in the same launch, rows (b, rows_c, n) copied into channels
+// [rows_channel0, rows_channel0 + rows_c): the two halves of a concatenation along the channels.
+PN2_API int pn2_three_interpolate_rows_into(int b, int c, int m, int n, const float *points,
+                                            const int *idx, const float *weight, float *out,
+                                            int c_total, int channel0, const float *rows, int rows_c,
+                                            int rows_channel0, void *stream_) {
+  if (b <= 0 || n <= 0) return 0;
+  if (c <= 0 || rows_c <= 0 || !rows || channel0 < 0 || rows_channel0 < 0 ||
+      channel0 + c > c_total || rows_channel0 + rows_c > c_total ||
+      (channel0 < rows_channel0 + rows_c && rows_channel0 < channel0 + c))
+    return (int)hipErrorInvalidValue;
+  const size_t bstride = (size_t)c_total * n;
+  const RowCopy rc = {rows, out + (size_t)rows_channel0 * n, rows_c, bstride};
+  return interpolate_run(b, c, m, n, points, idx, weight, out + (size_t)channel0 * n, bstride,
+                         (hipStream_t)stream_, rc);
 }
 
 PN2_API int pn2_three_interpolate_grad_from(int b, int c, int n, int m, const float *grad_out,

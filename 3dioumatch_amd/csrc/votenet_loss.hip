@@ -311,3 +311,38 @@ int votenet_decode_scores_grad(int b, int k, int nh, int ns, int nc, const float
                      0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
+
+// The backward of the IoU head's score slice (models/grid_conv_module.py:113-116: the last iou_size
+// channels of the head output, and the split of its 2K boxes into predictions and jittered copies,
+// models/votenet_iou_branch.py:157-181): d_net (b, c_out, kt) WHOLE in one launch -- zero rows, and
+// the gradients g0 (b, k0, iou_size) / g1 (b, kt - k0, iou_size) transposed into the last iou_size
+// rows (either may be NULL = zeros).
+namespace {
+__global__ void __launch_bounds__(256)
+iou_score_slices_grad_kernel(int c_out, int kt, int iou_size, int k0, const float *__restrict__ g0,
+                             const float *__restrict__ g1, float *__restrict__ d_net, long long total) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int j = (int)(i % kt);
+  const long long row = i / kt;
+  const int ch = (int)(row % c_out), b = (int)(row / c_out);
+  const int s = ch - (c_out - iou_size);
+  float v = 0.f;
+  if (s >= 0) {
+    if (j < k0) v = g0 ? g0[((size_t)b * k0 + j) * iou_size + s] : 0.f;
+    else v = g1 ? g1[((size_t)b * (kt - k0) + (j - k0)) * iou_size + s] : 0.f;
+  }
+  d_net[i] = v;
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("default")))
+int votenet_iou_score_slices_grad(int b, int c_out, int kt, int iou_size, int k0, const float *g0,
+                                  const float *g1, float *d_net, void *stream_) {
+  if (b <= 0 || c_out <= 0 || kt <= 0) return 0;
+  if (iou_size < 0 || iou_size > c_out || k0 < 0 || k0 > kt || !d_net) return (int)hipErrorInvalidValue;
+  const long long total = (long long)b * c_out * kt;
+  hipLaunchKernelGGL(iou_score_slices_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream_, c_out, kt, iou_size, k0, g0, g1, d_net, total);
+  return (int)hipGetLastError();
+}

@@ -348,6 +348,31 @@ def three_interpolate_into(points, idx, weight, out, channel0):
     return out
 
 
+def three_interpolate_rows_into(points, idx, weight, out, channel0, rows, rows_channel0):
+    """three_interpolate_into(points, idx, weight, out, channel0) and, in the same launch,
+    out[:, rows_channel0:rows_channel0 + rows.shape[1]] = rows (B, C_rows, n): both halves of a
+    concatenation along the channels.  The two channel ranges must not overlap."""
+    _chk_f32(points, "points"); _chk_i32(idx, "idx"); _chk_f32(weight, "weight"); _chk_f32(out, "out")
+    _chk_f32(rows, "rows")
+    _chk_dev(points, (idx, "idx"), (weight, "weight"), (out, "out"), (rows, "rows"))
+    b, c, m = points.shape
+    n = idx.shape[1]
+    c_total, c_rows = out.shape[1], rows.shape[1]
+    if out.shape[0] != b or out.shape[2] != n or channel0 < 0 or channel0 + c > c_total:
+        raise RuntimeError("out must be (B, C_total >= channel0 + C, n)")
+    if rows.dim() != 3 or rows.shape[0] != b or rows.shape[2] != n or rows_channel0 < 0 or \
+            rows_channel0 + c_rows > c_total or \
+            (channel0 < rows_channel0 + c_rows and rows_channel0 < channel0 + c):
+        raise RuntimeError("rows must be (B, C_rows, n) and fit out's channels beside the interpolated block")
+    with torch.cuda.device(points.device):
+        _L.check(_lib.pn2_three_interpolate_rows_into(b, c, m, n, points.data_ptr(), idx.data_ptr(),
+                                                      weight.data_ptr(), out.data_ptr(), c_total,
+                                                      int(channel0), rows.data_ptr(), c_rows,
+                                                      int(rows_channel0), _stream(points)),
+                 "three_interpolate_rows_into")
+    return out
+
+
 def three_interpolate_affine_supported(c, m, n):
     return bool(_lib.pn2_three_interpolate_affine_supported(int(c), int(m), int(n)))
 
@@ -356,9 +381,13 @@ def three_interpolate_affine(points, idx, weight, affine_w, affine_x):
     """three_interpolate(points (B,C,m), idx, weight) + affine_w (C,3) . affine_x (B,3,n) -> (B,C,n):
     the output of a 1x1 convolution over cat([3 coordinate rows, interpolated features]) when
     `points` is that convolution's feature part applied to the SOURCE points
-    (include/pn2_hip.h pn2_three_interpolate_affine).  No gradient."""
-    for t, name in ((points, "points"), (weight, "weight"), (affine_w, "affine_w"), (affine_x, "affine_x")):
+    (include/pn2_hip.h pn2_three_interpolate_affine).  affine_w may be a column slice of a wider
+    matrix (unit column stride): it is read in place.  No gradient."""
+    for t, name in ((points, "points"), (weight, "weight"), (affine_x, "affine_x")):
         _chk_f32(t, name)
+    if affine_w.dtype != torch.float32 or affine_w.dim() != 2 or affine_w.stride(1) != 1 or \
+            affine_w.stride(0) < 3:
+        raise RuntimeError("affine_w must be a float (C,3) matrix with contiguous rows")
     _chk_i32(idx, "idx")
     _chk_dev(points, (idx, "idx"), (weight, "weight"), (affine_w, "affine_w"), (affine_x, "affine_x"))
     b, c, m = points.shape
@@ -368,9 +397,10 @@ def three_interpolate_affine(points, idx, weight, affine_w, affine_x):
         raise RuntimeError("three_interpolate_affine: affine_w (C,3), affine_x (B,3,n), m <= 2048, n % 4 == 0")
     out = torch.empty((b, c, n), dtype=torch.float32, device=points.device)
     with torch.cuda.device(points.device):
-        _L.check(_lib.pn2_three_interpolate_affine(b, c, m, n, points.data_ptr(), idx.data_ptr(),
-                                                   weight.data_ptr(), affine_w.data_ptr(),
-                                                   affine_x.data_ptr(), out.data_ptr(), _stream(points)),
+        _L.check(_lib.pn2_three_interpolate_affine_ld(b, c, m, n, points.data_ptr(), idx.data_ptr(),
+                                                      weight.data_ptr(), affine_w.data_ptr(),
+                                                      int(affine_w.stride(0)), affine_x.data_ptr(),
+                                                      out.data_ptr(), _stream(points)),
                  "three_interpolate_affine")
     return out
 

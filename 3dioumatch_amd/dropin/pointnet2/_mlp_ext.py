@@ -292,13 +292,40 @@ def _image_of(w, b, r):
     return None
 
 
-def gemm_forward(w, x, coeff=None):
+def gemm_forward(w, x, coeff=None, bias=None):
     """y (B,M,R) = w (M,K) @ x (B,K,R); with coeff=(scale, shift) the operand is
-    relu(x*scale[k] + shift[k]) formed on the fly (x is then the previous layer's conv output)."""
-    _f32c(x, "x"); _f32c(w, "w")
+    relu(x*scale[k] + shift[k]) formed on the fly (x is then the previous layer's conv output).
+    w may be a column slice of a wider matrix (unit column stride); bias (M): y + bias per row.  A
+    small layer (include/mlp_hip.h mlp_gemm_forward_small) reads the slice in place and adds the bias
+    in its store; any other copies the slice and adds the bias in a pass of its own."""
+    _f32c(x, "x")
     b, k = x.shape[0], x.shape[1]
     r = x.numel() // (b * k)
     m = w.shape[0]
+    sliced = w.dim() == 2 and not w.is_contiguous() and w.stride(1) == 1 and w.stride(0) >= k
+    if sliced or bias is not None:
+        if bias is not None:
+            _f32c(bias, "bias")
+        if _lib.mlp_gemm_image_supported(int(b), int(r)):
+            if not sliced:
+                _f32c(w, "w")
+            elif w.dtype != torch.float32 or not w.is_cuda:
+                raise RuntimeError("w must be a float32 GPU tensor")
+            y = torch.empty((b, m) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+            image = None if sliced else _image_of(w, b, r)
+            op = _input_operand(x, coeff)
+            with torch.cuda.device(x.device):
+                _L.check(_lib.mlp_gemm_forward_small(b, m, k, r, w.data_ptr(),
+                                                     int(w.stride(0)) if sliced else k,
+                                                     image[0] if image else None, ctypes.byref(op),
+                                                     _ptr(bias), y.data_ptr(), _stream(x)),
+                         "mlp_gemm_forward_small")
+            return y
+        y = gemm_forward(w.contiguous(), x, coeff)
+        if bias is not None:
+            y += bias.view((1, -1) + (1,) * (y.dim() - 2))
+        return y
+    _f32c(w, "w")
     y = torch.empty((b, m) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
     image = _image_of(w, b, r)
     op = _input_operand(x, coeff)

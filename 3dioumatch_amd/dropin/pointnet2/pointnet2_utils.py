@@ -114,8 +114,11 @@ class InterpolateConcat(Function):
         n = idx.shape[1]
         c1 = skip_feats.shape[1]
         out = torch.empty((b, c2 + c1, n), dtype=torch.float32, device=known_feats.device)
-        _ext.three_interpolate_into(known_feats.contiguous(), idx, weight, out, 0)
-        out[:, c2:].copy_(skip_feats)
+        if hasattr(_ext, "three_interpolate_rows_into") and skip_feats.is_contiguous():
+            _ext.three_interpolate_rows_into(known_feats.contiguous(), idx, weight, out, 0, skip_feats, c2)
+        else:
+            _ext.three_interpolate_into(known_feats.contiguous(), idx, weight, out, 0)
+            out[:, c2:].copy_(skip_feats)
         ctx.save_for_backward(idx, weight)
         ctx.dims = (c2, c1, m)
         return out

@@ -177,8 +177,9 @@ class Interpolated(object):
     def forward(self, w, x):
         from pointnet2 import _ext
         from pointnet2 import _mlp_ext as K
-        z = K.gemm_forward(w[:, 3:].contiguous(), x)
-        y = _ext.three_interpolate_affine(z, self.idx, self.weight, w[:, :3].contiguous(), self.rel)
+        # (both column slices of w are read in place)
+        z = K.gemm_forward(w[:, 3:], x)
+        y = _ext.three_interpolate_affine(z, self.idx, self.weight, w[:, :3], self.rel)
         return y.view(self.shape)
 
     def input(self, x):
@@ -187,8 +188,7 @@ class Interpolated(object):
         from pointnet2 import _ext
         b, c = x.shape[0], 3 + x.shape[1]
         feats = torch.empty((b, c, self.rel.shape[2]), dtype=torch.float32, device=x.device)
-        feats[:, :3].copy_(self.rel)
-        _ext.three_interpolate_into(x, self.idx, self.weight, feats, 3)
+        _ext.three_interpolate_rows_into(x, self.idx, self.weight, feats, 3, self.rel, 0)
         return feats.view(b, c, self.shape[2], self.shape[3])
 
 

@@ -96,7 +96,13 @@ class Pointnet2Backbone(nn.Module):
 
     def forward(self, pointcloud, end_points=None, geometry=None):
         end_points = end_points if end_points else {}
-        xyz, features = self._break_up_pc(pointcloud)
+        if geometry is not None and not pointcloud.requires_grad and \
+                all(geometry.get(key) is not None for key in ("sa1_grouped", "sa1_new_xyz", "sa1_inds")):
+            # SA1 runs from its precomputed grouped tensor and centroids: it reads neither the
+            # coordinates nor the features of the cloud, so neither strided copy is made
+            xyz, features = None, None
+        else:
+            xyz, features = self._break_up_pc(pointcloud)
         for i in range(1, 5):
             given = geometry["sa%d_inds" % i] if geometry is not None else None
             ball = geometry.get("sa%d_ball_idx" % i) if geometry is not None else None

@@ -57,6 +57,20 @@ def unit_length_features(features):
     return features.div(torch.norm(features, p=2, dim=1).unsqueeze(1))
 
 
+def iou_branch_split(grid_conv, center, size, heading, end_points, k):
+    """The IoU branch over K predicted boxes followed by their jittered copies: the scores of the
+    first K -> end_points['iou_scores'], the others' -> ['iou_scores_jitter'].  The branch is asked
+    to split them itself (GridConv.forward: one autograd node with the score slice); one that does
+    not is split here."""
+    end_points['iou_scores_split'] = k
+    end_points = grid_conv(center, size, heading, end_points)
+    end_points.pop('iou_scores_split', None)
+    if 'iou_scores_jitter' not in end_points:
+        end_points['iou_scores'], end_points['iou_scores_jitter'] = torch.split(
+            end_points['iou_scores'], [k, end_points['iou_scores'].shape[1] - k], dim=1)
+    return end_points
+
+
 class VoteNet(nn.Module):
     def __init__(self, num_class, num_heading_bin, num_size_cluster, mean_size_arr, dataset_config,
                  input_feature_dim=0, num_proposal=128, vote_factor=1, sampling='vote_fps',
@@ -87,8 +101,12 @@ class VoteNet(nn.Module):
         end_points['seed_inds'] = end_points['fp2_inds']
         end_points['seed_xyz'] = xyz
         end_points['seed_features'] = features
-        xyz, features = self.vgen(xyz, features)
-        features = unit_length_features(features)
+        votes = self.vgen.forward_unit_length(xyz, features)
+        if votes is not None:  # the head's tail and the normalisation as one kernel each way
+            xyz, features = votes
+        else:
+            xyz, features = self.vgen(xyz, features)
+            features = unit_length_features(features)
         end_points['vote_xyz'] = xyz
         end_points['vote_features'] = features
         geometry = inputs.get('geometry')
@@ -166,10 +184,8 @@ class VoteNet(nn.Module):
         all_center = torch.cat([center, center_jitter], dim=1)
         all_size = torch.cat([size, size_jitter], dim=1)
         all_heading = torch.cat([heading, heading_jitter], dim=1)
-        end_points = self.grid_conv(all_center.detach(), all_size.detach(), all_heading.detach(),
-                                    end_points)
-        end_points['iou_scores'], end_points['iou_scores_jitter'] = torch.split(
-            end_points['iou_scores'], [k, end_points['iou_scores'].shape[1] - k], dim=1)
+        end_points = iou_branch_split(self.grid_conv, all_center.detach(), all_size.detach(),
+                                      all_heading.detach(), end_points, k)
         end_points['jitter_center'] = center_jitter
         end_points['jitter_size'] = size_jitter * 2
         end_points['jitter_heading'] = heading_jitter
@@ -224,9 +240,7 @@ class VoteNet(nn.Module):
                 jitter_size2.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
                 "votenet_bbox_jitter")
         end_points['size'], end_points['heading'] = size, heading
-        end_points = self.grid_conv(all_center, all_size, all_heading, end_points)
-        end_points['iou_scores'], end_points['iou_scores_jitter'] = torch.split(
-            end_points['iou_scores'], [k, end_points['iou_scores'].shape[1] - k], dim=1)
+        end_points = iou_branch_split(self.grid_conv, all_center, all_size, all_heading, end_points, k)
         end_points['jitter_center'] = all_center[:, k:]
         end_points['jitter_size'] = jitter_size2
         end_points['jitter_heading'] = all_heading[:, k:]

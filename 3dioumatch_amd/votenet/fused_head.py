@@ -53,9 +53,8 @@ class _HeadChain(Function):
         c1 = bn(y1, b1, g1, be1, rm1, rv1, mom1, eps1)
         y2 = K.gemm_forward(w2m, y1, (c1[2], c1[3]))
         c2 = bn(y2, b2, g2, be2, rm2, rv2, mom2, eps2)
-        y3 = K.gemm_forward(w3m, y2, (c2[2], c2[3]))
-        if b3 is not None:
-            y3 += b3.detach().view(1, -1, 1)
+        # (the last layer's bias goes into its GEMM's store where the layer is a small one)
+        y3 = K.gemm_forward(w3m, y2, (c2[2], c2[3]), bias=None if b3 is None else b3.detach())
         ctx.save_for_backward(x, y1, y2, *c1, *c2, w1, w2, w3, g1, g2)
         ctx.training, ctx.tickets = training, tickets
         ctx.has_bias = (b1 is not None, b2 is not None, b3 is not None)

@@ -124,6 +124,8 @@ class _FusedLabeledLoss(torch.autograd.Function):
         stats, objectness_label, objectness_mask, object_assignment, pred_bbox, extra = out
         ctx.flat, ctx.shapes, ctx.sizes, ctx.has_jitter = extra
         ctx.mark_non_differentiable(objectness_label, objectness_mask, object_assignment, pred_bbox)
+        # (the other outputs' gradients are never read: no zeros are made for them)
+        ctx.set_materialize_grads(False)
         return stats, objectness_label, objectness_mask, object_assignment, pred_bbox
 
     @staticmethod
@@ -278,6 +280,8 @@ class _FusedConsistencyLoss(torch.autograd.Function):
             labels, config, agg_xyz, obj, center, h_scores, h_resn, s_scores, s_resn, sem)
         ctx.flat, ctx.shapes, ctx.sizes = extra
         ctx.mark_non_differentiable(objectness_label, objectness_mask, object_assignment)
+        # (the other outputs' gradients are never read: no zeros are made for them)
+        ctx.set_materialize_grads(False)
         return stats, objectness_label, objectness_mask, object_assignment
 
     @staticmethod
@@ -425,6 +429,8 @@ class _FusedSemiLoss(torch.autograd.Function):
         total = stats_l[ST_LOSS] + stats_u[ST_LOSS] * weight
         ctx.flat, ctx.shapes, ctx.sizes, ctx.has_jitter = flat, shapes, sizes, has_jitter
         ctx.mark_non_differentiable(stats_l, stats_u, lab_l, mask_l, assign_l, pred_bbox, lab_u, mask_u, assign_u)
+        # (the other outputs' gradients are never read: no zeros are made for them)
+        ctx.set_materialize_grads(False)
         return total, stats_l, stats_u, lab_l, mask_l, assign_l, pred_bbox, lab_u, mask_u, assign_u
 
     @staticmethod

@@ -22,6 +22,113 @@ from pointnet2.pointnet2_modules import PointnetSAModuleVotes
 from .fused_head import head_chain
 
 
+class _VoteTail(torch.autograd.Function):
+    """The voting module's tail and the unit-length normalisation of the vote features as one launch
+    each way (include/loss_hip.h votenet_vote_tail[_grad]): net (B,3+C,N), seed_xyz (B,N,3),
+    seed_features (B,C,N) -> vote_xyz (B,N,3), vote_features (B,C,N), norm (B,N)."""
+
+    @staticmethod
+    def forward(ctx, net, seed_xyz, seed_features):
+        _L = _fused_front_end()
+        net, xyz, feats = net.contiguous(), seed_xyz.contiguous(), seed_features.contiguous()
+        b, c, n = feats.shape
+        vote_xyz = torch.empty((b, n, 3), dtype=torch.float32, device=net.device)
+        vote_features = torch.empty_like(feats)
+        norm = torch.empty((b, n), dtype=torch.float32, device=net.device)
+        with torch.cuda.device(net.device):
+            _L.check(_L.lib.votenet_vote_tail(
+                b, c, n, net.data_ptr(), xyz.data_ptr(), feats.data_ptr(), vote_xyz.data_ptr(),
+                vote_features.data_ptr(), norm.data_ptr(),
+                torch.cuda.current_stream(net.device).cuda_stream), "votenet_vote_tail")
+        ctx.save_for_backward(vote_features, norm)
+        ctx.mark_non_differentiable(norm)
+        ctx.set_materialize_grads(False)  # (a missing gradient is None, not a zero fill)
+        return vote_xyz, vote_features, norm
+
+    @staticmethod
+    def backward(ctx, g_xyz, g_features, _g_norm):
+        _L = _fused_front_end()
+        y, norm = ctx.saved_tensors
+        b, c, n = y.shape
+        g_features = torch.zeros_like(y) if g_features is None else g_features.contiguous()
+        g_xyz = None if g_xyz is None else g_xyz.contiguous()
+        d_net = torch.empty((b, 3 + c, n), dtype=torch.float32, device=y.device)
+        d_xyz = torch.empty((b, n, 3), dtype=torch.float32, device=y.device) \
+            if ctx.needs_input_grad[1] else None
+        d_feats = torch.empty_like(y) if ctx.needs_input_grad[2] else None
+        with torch.cuda.device(y.device):
+            _L.check(_L.lib.votenet_vote_tail_grad(
+                b, c, n, y.data_ptr(), norm.data_ptr(), None if g_xyz is None else g_xyz.data_ptr(),
+                g_features.data_ptr(), d_net.data_ptr(), None if d_feats is None else d_feats.data_ptr(),
+                None if d_xyz is None else d_xyz.data_ptr(),
+                torch.cuda.current_stream(y.device).cuda_stream), "votenet_vote_tail_grad")
+        return d_net, d_xyz, d_feats
+
+
+def vote_tail_fused(seed_xyz, seed_features):
+    """Does vote_tail cover these seeds (float32 on one GPU, (B,N,3) and (B,C,N), the library there)?"""
+    _L = _fused_front_end()
+    return (_L is not None and hasattr(_L.lib, "votenet_vote_tail") and seed_features.is_cuda
+            and seed_features.dim() == 3 and seed_xyz.dim() == 3 and seed_xyz.shape[2] == 3
+            and seed_xyz.shape[:2] == (seed_features.shape[0], seed_features.shape[2])
+            and all(t.dtype == torch.float32 and t.device == seed_features.device
+                    for t in (seed_xyz, seed_features)))
+
+
+def vote_tail(net, seed_xyz, seed_features):
+    """(vote_xyz, unit-length vote_features, norm) from the vote head's output net (B, 3+C, N), one
+    vote per seed: one kernel each way (vote_tail_fused says where)."""
+    b, c, n = seed_features.shape
+    if tuple(net.shape) != (b, 3 + c, n) or net.dtype != torch.float32 or net.device != seed_features.device:
+        raise RuntimeError("vote_tail: net must be a float32 (B, 3+C, N) tensor beside the seeds")
+    return _VoteTail.apply(net, seed_xyz, seed_features)
+
+
+class _IouScoreSlices(torch.autograd.Function):
+    """The IoU head's score slice and the split of its boxes as ONE node: the forward hands out the
+    same views the tensor ops do (nothing is launched); the backward writes d_net (B, C_out, KT)
+    whole in one launch (include/loss_hip.h votenet_iou_score_slices_grad) instead of a
+    concatenation, a zero fill, a strided copy and a layout copy."""
+
+    @staticmethod
+    def forward(ctx, net, iou_size, k0):
+        kt = net.shape[2]
+        ctx.dims = (tuple(net.shape), int(iou_size), kt if k0 is None else int(k0))
+        ctx.set_materialize_grads(False)  # (an unused piece's gradient is None: the kernel's NULL)
+        scores = net.transpose(2, 1)[:, :, net.shape[1] - iou_size:]
+        if k0 is None:
+            return (scores,)
+        return scores[:, :k0], scores[:, k0:]
+
+    @staticmethod
+    def backward(ctx, *grads):
+        _L = _fused_front_end()
+        (b, c_out, kt), iou_size, k0 = ctx.dims
+        grads = [None if g is None else g.contiguous() for g in grads] + [None]
+        dev = next(g.device for g in grads if g is not None)
+        d_net = torch.empty((b, c_out, kt), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _L.check(_L.lib.votenet_iou_score_slices_grad(
+                b, c_out, kt, iou_size, k0, *[None if g is None else g.data_ptr() for g in grads[:2]],
+                d_net.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                "votenet_iou_score_slices_grad")
+        return d_net, None, None
+
+
+def iou_score_slices(net, iou_size, k0=None):
+    """The last iou_size channels of the IoU head's output net (B, C_out, KT) as (B, KT, iou_size)
+    scores -- with k0, split into the first k0 boxes and the rest: a tuple of one or two tensors.
+    On the GPU one autograd node whose backward is one launch; the tensor ops elsewhere."""
+    _L = _fused_front_end()
+    if _L is not None and hasattr(_L.lib, "votenet_iou_score_slices_grad") and net.is_cuda and \
+            net.dtype == torch.float32 and net.dim() == 3 and net.requires_grad and torch.is_grad_enabled():
+        return _IouScoreSlices.apply(net, iou_size, k0)
+    scores = net.transpose(2, 1)[:, :, net.shape[1] - iou_size:]
+    if k0 is None:
+        return (scores,)
+    return tuple(torch.split(scores, [k0, scores.shape[1] - k0], dim=1))
+
+
 class VotingModule(nn.Module):
     """seed (xyz, features) -> votes: xyz + offset, features + residual (vote_factor per seed)."""
 
@@ -46,6 +153,16 @@ class VotingModule(nn.Module):
         vote_features = vote_features.reshape(b, num_seed * self.vote_factor, self.out_dim)
         return vote_xyz, vote_features.transpose(2, 1).contiguous()
 
+    def forward_unit_length(self, seed_xyz, seed_features):
+        """forward followed by the division of the vote features by their length over the channels
+        (models/votenet_iou_branch.py:103-104): on the GPU the head's output goes through ONE kernel
+        each way (_VoteTail); None where that does not apply."""
+        if self.vote_factor != 1 or not vote_tail_fused(seed_xyz, seed_features):
+            return None
+        net = head_chain(seed_features, self.conv1, self.bn1, self.conv2, self.bn2, self.conv3)
+        vote_xyz, vote_features, _ = vote_tail(net, seed_xyz, seed_features)
+        return vote_xyz, vote_features
+
 
 class _DecodeScores(torch.autograd.Function):
     """decode_scores as one launch each way (include/loss_hip.h votenet_decode_scores): the nine
@@ -68,6 +185,8 @@ class _DecodeScores(torch.autograd.Function):
                 "votenet_decode_scores")
         ctx.save_for_backward(net, mean_size)
         ctx.dims = (nh, ns, nc)
+        # (the gradient of an output nothing differentiates is None -- the kernel's NULL -- not a zero fill)
+        ctx.set_materialize_grads(False)
         return tuple(outs)
 
     @staticmethod
@@ -258,7 +377,20 @@ class GridConv(nn.Module):
             return end_points['seed_xyz'], end_points['vote_features']
         raise NotImplementedError()
 
+    def _scores(self, net, end_points, split):
+        """end_points['iou_scores'] (and, with split = K, ['iou_scores_jitter']: the boxes after the
+        first K) from the head's output."""
+        pieces = iou_score_slices(net, self.iou_size, split)
+        end_points['iou_scores'] = pieces[0]
+        if split is not None:
+            end_points['iou_scores_jitter'] = pieces[1]
+        return end_points
+
     def forward(self, center, size, heading, end_points):
+        """end_points['iou_scores_split'] = K (optional; consumed here): the boxes are K predictions
+        followed by their jittered copies, and their scores go to end_points['iou_scores'] and
+        ['iou_scores_jitter'] -- slice and split as one autograd node."""
+        split = end_points.pop('iou_scores_split', None)
         origin_xyz, origin_features = self._origin(end_points)
         origin_xyz = origin_xyz.detach().contiguous()
         origin_features = origin_features.detach().contiguous()
@@ -296,13 +428,14 @@ class GridConv(nn.Module):
             else:
                 if commute:  # (the shared MLP declined: the full input after all)
                     rel, feats = feats, torch.empty((b, 3 + c, k * g3), dtype=torch.float32, device=size.device)
-                    feats[:, :3].copy_(rel)
-                pointnet2_utils._ext.three_interpolate_into(origin_features, idx, weight, feats, 3)
+                    pointnet2_utils._ext.three_interpolate_rows_into(origin_features, idx, weight, feats, 3,
+                                                                     rel, 0)
+                else:
+                    pointnet2_utils._ext.three_interpolate_into(origin_features, idx, weight, feats, 3)
                 iou_features = self.mlp_before_iou.forward_pooled(feats.view(b, -1, k, g3))
             net = head_chain(iou_features, self.conv1_iou, self.bn1_iou, self.conv2_iou, self.bn2_iou,
                              self.conv3_iou)
-            end_points['iou_scores'] = net.transpose(2, 1)[:, :, -self.iou_size:]
-            return end_points
+            return self._scores(net, end_points, split)
         unit = self._unit_grid(size.device)
         local = unit.view(1, 1, g3, 3) * size.unsqueeze(2)  # (B, K, 64, 3): half-sizes scale it
         # local @ rot_z(heading)^T, written out (a 3x3 rotation about z is two multiply-adds per
@@ -353,5 +486,4 @@ class GridConv(nn.Module):
         iou_features = self.mlp_before_iou.forward_pooled(feats)
         net = head_chain(iou_features, self.conv1_iou, self.bn1_iou, self.conv2_iou, self.bn2_iou,
                          self.conv3_iou)
-        end_points['iou_scores'] = net.transpose(2, 1)[:, :, -self.iou_size:]
-        return end_points
+        return self._scores(net, end_points, split)

@@ -110,6 +110,31 @@ int votenet_channel_normalize(int b, int c, int n, const float *x, float *y, flo
 int votenet_channel_normalize_grad(int b, int c, int n, const float *y, const float *norm,
                                    const float *dy, float *dx, void *stream);
 
+/* the voting module's tail and the unit-length normalisation behind it as one launch each way
+ * (models/voting_module.py:52-63 + models/votenet_iou_branch.py:103-104; vote_factor 1): net
+ * (b,3+c,n) the head's output, seed_xyz (b,n,3), seed_features (b,c,n) -> vote_xyz = seed_xyz +
+ * net[:, :3]^T (b,n,3), vote_features = f / ||f||_2 over c with f = seed_features + net[:, 3:]
+ * (b,c,n), norm (b,n).  Element for element what the tensor adds followed by
+ * votenet_channel_normalize compute. */
+int votenet_vote_tail(int b, int c, int n, const float *net, const float *seed_xyz,
+                      const float *seed_features, float *vote_xyz, float *vote_features, float *norm,
+                      void *stream);
+/* its backward (autograd of models/voting_module.py:52-63 + models/votenet_iou_branch.py:103-104):
+ * d_net (b,3+c,n) written whole, d_seed_features (b,c,n) and d_seed_xyz (b,n,3) (either may be
+ * NULL: not wanted) from g_vote_xyz (b,n,3; NULL = zeros), g_vote_features (b,c,n) and the forward's
+ * vote_features and norm; the feature rows as votenet_channel_normalize_grad computes them */
+int votenet_vote_tail_grad(int b, int c, int n, const float *vote_features, const float *norm,
+                           const float *g_vote_xyz, const float *g_vote_features, float *d_net,
+                           float *d_seed_features, float *d_seed_xyz, void *stream);
+
+/* the backward of the IoU head's score slice (models/grid_conv_module.py:113-116: the last
+ * iou_size channels of the head output net (b,c_out,kt)) and of the split of its kt boxes into
+ * the first k0 and the rest (models/votenet_iou_branch.py:157-181): d_net written whole -- zero
+ * rows, g0 (b,k0,iou_size) and g1 (b,kt-k0,iou_size) transposed into the last iou_size rows;
+ * either may be NULL = zeros */
+int votenet_iou_score_slices_grad(int b, int c_out, int kt, int iou_size, int k0, const float *g0,
+                                  const float *g1, float *d_net, void *stream);
+
 /* replaces decode_scores (models/proposal_module.py:24-54): the proposal head's output net
  * (b, c, k), c = 2 + 3 + 2 nh + 4 ns + nc, split into the named predictions, each a contiguous
  * (b,k,.) tensor: objectness (2), center = agg_xyz + offset (3), heading_scores (nh),

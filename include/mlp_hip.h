@@ -138,6 +138,14 @@ typedef struct MlpOperand {
  * (m, k) = (64, 64), w and lin_w 16-byte aligned. */
 int mlp_gemm_forward(int b, int m, int k, int r, const float *w, const void *img,
                      const MlpOperand *x, float *y, float *pairs, void *stream);
+/* mlp_gemm_forward of a SMALL layer (mlp_gemm_image_supported(b, r); x: mode 0 or 1) with
+ *  - w as a view of a wider row-major matrix, row i at w + i * ldw (ldw >= k): a column slice of a
+ *    convolution's weight read in place (the feature columns of models/grid_conv_module.py:87-110);
+ *  - bias (m floats, may be NULL) added to every finished output element: the bias of nn.Conv1d
+ *    (the heads' last layer, models/voting_module.py:34-60) without a second pass over y.
+ * img (may be NULL) only with ldw == k. */
+int mlp_gemm_forward_small(int b, int m, int k, int r, const float *w, int ldw, const void *img,
+                           const MlpOperand *x, const float *bias, float *y, void *stream);
 
 /* BatchNorm statistics as a by-product of the convolution (nn.Conv2d + nn.BatchNorm2d of a
  * shared-MLP layer, pytorch_utils.py:70-124, in training mode): the GEMM epilogue reduces every

@@ -97,6 +97,12 @@ int pn2_three_interpolate_affine_supported(int c, int m, int n);
 int pn2_three_interpolate_affine(int b, int c, int m, int n, const float *points, const int *idx,
                                  const float *weight, const float *affine_w, const float *affine_x,
                                  float *out, void *stream);
+/* the same with affine_w as a view of a wider row-major matrix, row l at affine_w + l * affine_w_ld
+ * (>= 3): the coordinate columns of the convolution's weight (models/grid_conv_module.py:87-110) read
+ * in place, without a copy of the slice */
+int pn2_three_interpolate_affine_ld(int b, int c, int m, int n, const float *points, const int *idx,
+                                    const float *weight, const float *affine_w, int affine_w_ld,
+                                    const float *affine_x, float *out, void *stream);
 
 /* replaces three_interpolate_grad_kernel_wrapper (interpolate.cpp:14-17,
  * interpolate_gpu.cu:121-159) -- the INTENDED scatter-add.  The reference's pybind layer
@@ -114,6 +120,14 @@ int pn2_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out
  * reading the gradient straight out of the concatenated gradient saves a copy of both. */
 int pn2_three_interpolate_into(int b, int c, int m, int n, const float *points, const int *idx,
                                const float *weight, float *out, int c_total, void *stream);
+/* pn2_three_interpolate_into (interpolate.cpp:47-75) at channels [channel0, channel0 + c) of out
+ * (b, c_total, n) -- out is the tensor's BASE here -- plus, in the same launch, rows (b, rows_c, n)
+ * copied into channels [rows_channel0, rows_channel0 + rows_c): both halves of the concatenations of
+ * pointnet2_modules.py:404-410 (skip features after the block) and models/grid_conv_module.py:87-110
+ * (coordinate rows before it).  The two channel ranges must not overlap. */
+int pn2_three_interpolate_rows_into(int b, int c, int m, int n, const float *points, const int *idx,
+                                    const float *weight, float *out, int c_total, int channel0,
+                                    const float *rows, int rows_c, int rows_channel0, void *stream);
 /* (interpolate.cpp:77-104, the intended scatter-add, on a slice of the gradient) */
 int pn2_three_interpolate_grad_from(int b, int c, int n, int m, const float *grad_out, int c_total,
                                     const int *idx, const float *weight, float *grad_points,
