@@ -142,6 +142,9 @@ _SIGNATURES = {
     "mlp_flush_weight_reductions": [],
     "lhs_nms3d_aabb": [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _c_int, _vp,
                        _vp],
+    "lhs_nms_aabb_masked": [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _c_int,
+                            _c_int, _vp, _vp, _vp],
+    "lhs_box_point_count": [_c_int] * 4 + [_vp] * 6,
     "votenet_decode_scores": [_c_int] * 5 + [_vp] * 13,
     "votenet_decode_scores_grad": [_c_int] * 5 + [_vp] * 13,
     "lhs_pseudo_select": [_vp, _vp],

@@ -12,6 +12,10 @@
 // the highest remaining lane, the suppressed set is a ballot, "the upper half of it" is a popcount
 // on the ballot above each lane.  Arithmetic as the reference: float32 corners from float64
 // decoding, float64 areas / overlaps.
+//
+// Two switches serve the evaluation path's other branches (models/ap_helper.py:139-203): `valid`
+// (a box with valid == 0 is never alive: the reference's NMS on boxes[nonempty_box_mask == 1]) and
+// `dims` (2: nms_2d_faster, utils/nms.py:52-83, on the camera x / z extents of the same bounds).
 #include "common.h"
 
 namespace {
@@ -42,11 +46,19 @@ __device__ __forceinline__ Aabb camera_aabb(const float *c, const double *sz, do
   return o;
 }
 
+// float64 volume of the bounds (dims == 3), or the area of their camera x / camera z footprint
+// (dims == 2: boxes_2d_with_prob of models/ap_helper.py:143-149)
+__device__ __forceinline__ double aabb_area(const Aabb &b, int dims) {
+  if (dims == 2) return ((double)b.x2 - b.x1) * ((double)b.z2 - b.z1);
+  return ((double)b.x2 - b.x1) * ((double)b.y2 - b.y1) * ((double)b.z2 - b.z1);
+}
+
 __global__ void __launch_bounds__(64)
 lhs_nms_kernel(int n, const float *__restrict__ center, const double *__restrict__ size,
                const double *__restrict__ heading, const float *__restrict__ score,
                const long long *__restrict__ cls, double thresh, int old_type, int same_class,
-               int readmit, double area_eps, int *__restrict__ picked) {
+               int readmit, double area_eps, int dims, const int *__restrict__ valid,
+               int *__restrict__ picked) {
   __shared__ float s_score[64];
   __shared__ Aabb s_box[64];
   __shared__ double s_area[64];
@@ -61,7 +73,7 @@ lhs_nms_kernel(int n, const float *__restrict__ center, const double *__restrict
   if (live) {
     mine = camera_aabb(center + (base + lane) * 3, size + (base + lane) * 3, heading[base + lane]);
     my_score = score[base + lane];
-    my_cls = cls[base + lane];
+    if (cls) my_cls = cls[base + lane];
   }
   s_score[lane] = my_score;
   __syncthreads();
@@ -73,8 +85,7 @@ lhs_nms_kernel(int n, const float *__restrict__ center, const double *__restrict
       rank += (sk < my_score || (sk == my_score && k < lane)) ? 1 : 0;
     }
     s_box[rank] = mine;
-    s_area[rank] = ((double)mine.x2 - mine.x1) * ((double)mine.y2 - mine.y1) *
-                       ((double)mine.z2 - mine.z1) + area_eps;
+    s_area[rank] = aabb_area(mine, dims) + area_eps;
     s_cls[rank] = my_cls;
     s_orig[rank] = lane;
   }
@@ -83,7 +94,9 @@ lhs_nms_kernel(int n, const float *__restrict__ center, const double *__restrict
   const Aabb b = live ? s_box[lane] : mine;
   const double area = live ? s_area[lane] : 1.0;
   const long long c = live ? s_cls[lane] : -1;
-  unsigned long long remaining = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
+  // a box with valid == 0 takes no part: never alive, so never a winner or a suppressor
+  unsigned long long remaining =
+      __ballot(live && (valid == nullptr || valid[base + s_orig[lane]] != 0));
   unsigned long long pick = 0ull;
   while (remaining) {
     const int i = 63 - __builtin_clzll(remaining);
@@ -99,13 +112,8 @@ lhs_nms_kernel(int n, const float *__restrict__ center, const double *__restrict
                    zz2 = bi.z2 < b.z2 ? bi.z2 : b.z2;
       const double l = xx2 - xx1 > 0 ? xx2 - xx1 : 0, w = yy2 - yy1 > 0 ? yy2 - yy1 : 0,
                    h = zz2 - zz1 > 0 ? zz2 - zz1 : 0;
-      double o;
-      if (old_type) {
-        o = (l * w * h) / area;
-      } else {
-        const double inter = l * w * h;
-        o = inter / (area_i + area - inter);
-      }
+      const double inter = dims == 2 ? l * h : l * w * h;
+      double o = old_type ? inter / area : inter / (area_i + area - inter);
       if (same_class) o = o * (ci == c ? 1.0 : 0.0);
       suppressed = o > thresh;
     }
@@ -128,7 +136,8 @@ __global__ void __launch_bounds__(T)
 nms_aabb_block_kernel(int n, const float *__restrict__ center, const double *__restrict__ size,
                       const double *__restrict__ heading, const float *__restrict__ score,
                       const long long *__restrict__ cls, double thresh, int old_type,
-                      int same_class, int readmit, double area_eps, int *__restrict__ picked) {
+                      int same_class, int readmit, double area_eps, int dims,
+                      const int *__restrict__ valid, int *__restrict__ picked) {
   __shared__ float s_score[T];
   __shared__ Aabb s_box[T];
   __shared__ double s_area[T];
@@ -144,7 +153,7 @@ nms_aabb_block_kernel(int n, const float *__restrict__ center, const double *__r
   if (live) {
     mine = camera_aabb(center + (base + tid) * 3, size + (base + tid) * 3, heading[base + tid]);
     my_score = score[base + tid];
-    my_cls = cls[base + tid];
+    if (cls) my_cls = cls[base + tid];
   }
   s_score[tid] = my_score;
   __syncthreads();
@@ -155,8 +164,7 @@ nms_aabb_block_kernel(int n, const float *__restrict__ center, const double *__r
       rank += (sk < my_score || (sk == my_score && k < tid)) ? 1 : 0;
     }
     s_box[rank] = mine;
-    s_area[rank] = ((double)mine.x2 - mine.x1) * ((double)mine.y2 - mine.y1) *
-                       ((double)mine.z2 - mine.z1) + area_eps;
+    s_area[rank] = aabb_area(mine, dims) + area_eps;
     s_cls[rank] = my_cls;
     s_orig[rank] = tid;
   }
@@ -164,7 +172,8 @@ nms_aabb_block_kernel(int n, const float *__restrict__ center, const double *__r
   const Aabb b = live ? s_box[tid] : mine;   // lane r is now the box of rank r
   const double area = live ? s_area[tid] : 1.0;
   const long long c = live ? s_cls[tid] : -1;
-  bool alive = live, pick = false;
+  // a box with valid == 0 takes no part: never alive, so never a winner or a suppressor
+  bool alive = live && (valid == nullptr || valid[base + s_orig[tid]] != 0), pick = false;
   for (;;) {
     const unsigned long long am = __ballot(alive);
     if (lane == 0) s_alive[w] = am;
@@ -185,13 +194,8 @@ nms_aabb_block_kernel(int n, const float *__restrict__ center, const double *__r
                    zz2 = bi.z2 < b.z2 ? bi.z2 : b.z2;
       const double l = xx2 - xx1 > 0 ? xx2 - xx1 : 0, wd = yy2 - yy1 > 0 ? yy2 - yy1 : 0,
                    h = zz2 - zz1 > 0 ? zz2 - zz1 : 0;
-      double o;
-      if (old_type) {
-        o = (l * wd * h) / area;
-      } else {
-        const double inter = l * wd * h;
-        o = inter / (area_i + area - inter);
-      }
+      const double inter = dims == 2 ? l * h : l * wd * h;
+      double o = old_type ? inter / area : inter / (area_i + area - inter);
       if (same_class) o = o * (ci == c ? 1.0 : 0.0);
       suppressed = o > thresh;
     }
@@ -221,20 +225,22 @@ nms_aabb_block_kernel(int n, const float *__restrict__ center, const double *__r
 static int nms_aabb_launch(int scenes, int n, const float *center, const double *size,
                            const double *heading, const float *score, const long long *cls,
                            double thresh, int old_type, int same_class, int readmit,
-                           double area_eps, int *picked, hipStream_t stream) {
+                           double area_eps, int dims, const int *valid, int *picked,
+                           hipStream_t stream) {
   if (scenes <= 0 || n <= 0) return 0;
   if (n > 1024) return (int)hipErrorInvalidValue;
   if (n <= 64)
     hipLaunchKernelGGL(lhs_nms_kernel, dim3(scenes), dim3(64), 0, stream, n, center, size, heading,
-                       score, cls, thresh, old_type, same_class, readmit, area_eps, picked);
+                       score, cls, thresh, old_type, same_class, readmit, area_eps, dims, valid,
+                       picked);
   else if (n <= 256)
     hipLaunchKernelGGL(nms_aabb_block_kernel<256>, dim3(scenes), dim3(256), 0, stream, n, center,
                        size, heading, score, cls, thresh, old_type, same_class, readmit, area_eps,
-                       picked);
+                       dims, valid, picked);
   else
     hipLaunchKernelGGL(nms_aabb_block_kernel<1024>, dim3(scenes), dim3(1024), 0, stream, n, center,
                        size, heading, score, cls, thresh, old_type, same_class, readmit, area_eps,
-                       picked);
+                       dims, valid, picked);
   return pn2_launch_status();
 }
 
@@ -246,7 +252,7 @@ int lhs_nms3d_aabb(int scenes, int n, const float *center, const double *size,
                    const double *heading, const float *score, const long long *cls, double thresh,
                    int old_type, int same_class, int *picked, void *stream) {
   return nms_aabb_launch(scenes, n, center, size, heading, score, cls, thresh, old_type,
-                         same_class, 0, 0.0, picked, (hipStream_t)stream);
+                         same_class, 0, 0.0, 3, nullptr, picked, (hipStream_t)stream);
 }
 
 // picked (scenes, n) int32 <- 1 for every box lhs_3d_faster_samecls returns (utils/nms.py:168-214)
@@ -256,5 +262,20 @@ int lhs_nms_samecls(int scenes, int n, const float *center, const double *size,
                     int old_type, int *picked, void *stream) {
   if (n > 64) return (int)hipErrorInvalidValue;  // MAX_NUM_OBJ = 64 (loss_helper_unlabeled.py:21)
   return nms_aabb_launch(scenes, n, center, size, heading, score, cls, thresh, old_type, 1, 1, 1e-8,
-                         picked, (hipStream_t)stream);
+                         3, nullptr, picked, (hipStream_t)stream);
+}
+
+// lhs_nms3d_aabb on the boxes with valid != 0 only (valid (scenes,n) int32, or NULL for all): the
+// reference runs every NMS of the evaluation path on boxes[nonempty_box_mask[i,:]==1]
+// (models/ap_helper.py:139-203); a box with valid == 0 gets picked = 0.  dims == 2: nms_2d_faster
+// (utils/nms.py:52-83) on the camera x / camera z bounds, `cls` unread (same_class must be 0).
+extern "C" __attribute__((visibility("default")))
+int lhs_nms_aabb_masked(int scenes, int n, const float *center, const double *size,
+                        const double *heading, const float *score, const long long *cls,
+                        double thresh, int old_type, int same_class, int dims, const int *valid,
+                        int *picked, void *stream) {
+  if ((dims != 2 && dims != 3) || (dims == 2 && same_class)) return (int)hipErrorInvalidValue;
+  if (dims == 3 && cls == nullptr) return (int)hipErrorInvalidValue;
+  return nms_aabb_launch(scenes, n, center, size, heading, score, dims == 2 ? nullptr : cls, thresh,
+                         old_type, same_class, 0, 0.0, dims, valid, picked, (hipStream_t)stream);
 }

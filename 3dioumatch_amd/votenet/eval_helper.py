@@ -1,8 +1,11 @@
 """Prediction parsing of the evaluation path with the NMS on the device.
 
 Host-side mirror of the reference models/ap_helper.py: predictions2corners3d :60-99 and
-parse_predictions :101-222 for the 3-D NMS branches the training scripts use
-(`use_3d_nms`, with or without `cls_nms`, optionally IoU-weighted scores; train.py:263-275).
+parse_predictions :101-222 with every combination of config keys the reference accepts: the 3-D NMS
+branches the training scripts use (`use_3d_nms`, with or without `cls_nms`, optionally IoU-weighted
+scores; train.py:263-275), the 2-D branch (`use_3d_nms` off: nms_2d_faster on the camera x / z
+bounds with objectness scores; `cls_nms` / `use_iou_for_nms` are not consulted there, as in the
+reference) and `remove_empty_box` in front of any of them.
 The reference decodes every box on the host (B x K calls of get_3d_box,
 utils/box_util.py:335-358) and runs utils/nms.py per scene in numpy; here the decoding is a few
 batched float64 tensor ops, the NMS one kernel launch (votenet/pseudo_nms.py:nms3d_aabb_gpu) and
@@ -12,8 +15,15 @@ parse_groundtruths (:224-307) and APCalculator (:382-435) complete the evaluatio
 train.py:evaluate_one_epoch; the average precision itself is votenet/eval_det.py (oriented-box IoU
 on the device).
 
-Not mirrored (raise NotImplementedError): `remove_empty_box` (off in the reference's configs) and
-the 2-D NMS branch.
+`remove_empty_box` (ap_helper.py:123-135) drops every proposal with fewer than five input points
+inside its oriented box before the NMS.  The reference asks scipy for a Delaunay triangulation of
+the eight corners per box; here one kernel (votenet/pseudo_nms.py:box_point_count_gpu) counts by
+the closed-form test in float32 on end_points['point_clouds'] in place, and the counts' `>= 5` goes
+to the NMS kernel as its validity mask, which is what running the NMS on the non-empty subset
+gives.  Two differences: a point within about 1e-5 m of a face may be classified differently from
+the triangulation (whose own answer there depends on qhull's tolerance), and a scene whose boxes
+are all empty gives an all-zero pred_mask row where the reference stops at assert(len(pick)>0) --
+imitating that would take a host round trip.
 """
 import numpy as np
 import torch
@@ -23,6 +33,20 @@ def _nms3d(center, size, heading, score, cls, thresh, old_type, same_class):
     """(S,n) bool keep mask; the GPU kernel (tests substitute the oracle)."""
     from .pseudo_nms import nms3d_aabb_gpu
     return nms3d_aabb_gpu(center, size, heading, score, cls, thresh, old_type, same_class)
+
+
+def _count_points(points, center, size, heading):
+    """(S,n) int32 points inside each box; the GPU kernel (tests substitute a host count)."""
+    from .pseudo_nms import box_point_count_gpu
+    return box_point_count_gpu(points, center, size, heading)
+
+
+def _nms_masked(center, size, heading, score, cls, thresh, old_type, same_class, dims, valid):
+    """(S,n) bool keep mask of the NMS on the boxes with valid != 0 (None: all), dims 2 or 3; the
+    GPU kernel (tests substitute a host loop)."""
+    from .pseudo_nms import nms_aabb_masked_gpu
+    return nms_aabb_masked_gpu(center, size, heading, score, cls, thresh, old_type, same_class,
+                               dims, valid)
 
 
 def corners_upright_camera(center, size64, heading64):
@@ -61,12 +85,9 @@ def decode_boxes(end_points, config):
 @torch.no_grad()
 def parse_predictions(end_points, config_dict):
     """-> batch_pred_map_cls: per scene a list of (class, corners (8,3) ndarray, confidence), as
-    ap_helper.parse_predictions returns it; also fills end_points['pred_mask'] (B,K) and
-    end_points['batch_pred_map_cls']."""
-    if config_dict.get('remove_empty_box', False):
-        raise NotImplementedError("remove_empty_box is not mirrored (off in the reference configs)")
-    if not config_dict.get('use_3d_nms', True):
-        raise NotImplementedError("only the 3-D NMS branches are mirrored")
+    ap_helper.parse_predictions returns it; also fills end_points['pred_mask'] (B,K),
+    end_points['batch_pred_map_cls'] and, with `remove_empty_box`, end_points['nonempty_box_mask']
+    (B,K)."""
     config = config_dict['dataset_config']
     center = end_points['center']
     sem_probs = torch.softmax(end_points['sem_cls_scores'], dim=-1)
@@ -75,16 +96,30 @@ def parse_predictions(end_points, config_dict):
     size64, heading64 = decode_boxes(end_points, config)
     corners = corners_upright_camera(center, size64, heading64)
 
+    nonempty = None
+    if config_dict.get('remove_empty_box', False):
+        count = _count_points(end_points['point_clouds'], center.contiguous(), size64, heading64)
+        nonempty = (count >= 5).to(torch.int32)
+
     scores = obj_prob
-    same_class = bool(config_dict.get('cls_nms', False))
+    use_3d = bool(config_dict.get('use_3d_nms', True))
+    same_class = use_3d and bool(config_dict.get('cls_nms', False))
     if same_class and config_dict.get('use_iou_for_nms', False):
         iou = torch.sigmoid(end_points['iou_scores'])
         if iou.shape[2] > 1:
             iou = torch.gather(iou, 2, pred_sem_cls.unsqueeze(-1))
         scores = scores * iou.squeeze(-1)
-    pred_mask = _nms3d(center.contiguous(), size64, heading64, scores.contiguous(), pred_sem_cls,
-                       config_dict['nms_iou'], config_dict['use_old_type_nms'], same_class)
+    if use_3d and nonempty is None:
+        pred_mask = _nms3d(center.contiguous(), size64, heading64, scores.contiguous(), pred_sem_cls,
+                           config_dict['nms_iou'], config_dict['use_old_type_nms'], same_class)
+    else:
+        pred_mask = _nms_masked(center.contiguous(), size64, heading64, scores.contiguous(),
+                                pred_sem_cls, config_dict['nms_iou'],
+                                config_dict['use_old_type_nms'], same_class, 3 if use_3d else 2,
+                                nonempty)
     # one device->host copy of the small results, then the reference's list layout
+    if nonempty is not None:
+        end_points['nonempty_box_mask'] = nonempty.cpu().numpy().astype(np.float64)
     keep = (pred_mask & (obj_prob > config_dict['conf_thresh'])).cpu().numpy()
     # (B,K) float64 numpy array of 0/1 like the reference's (ap_helper.py:141-155), so that
     # consumers such as dump_helper index / multiply it the same way

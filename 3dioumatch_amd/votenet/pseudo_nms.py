@@ -59,6 +59,81 @@ def nms3d_aabb_gpu(center, size, heading, score, cls, thresh, old_type=False, sa
     return picked.bool()
 
 
+def nms_aabb_masked_gpu(center, size, heading, score, cls, thresh, old_type=False, same_class=True,
+                        dims=3, valid=None):
+    """nms3d_aabb_gpu on the boxes with valid != 0 only (valid (S,n) i32 or None for all; the
+    reference's boxes[nonempty_box_mask[i,:]==1], models/ap_helper.py:139-203): a masked box is
+    neither winner nor suppressor and is not picked, a scene without a valid box gives an all-False
+    row.  dims=2: utils/nms.py nms_2d_faster on the camera x / z bounds; `cls` may be None and
+    same_class must be False."""
+    if dims not in (2, 3):
+        raise RuntimeError("nms_aabb_masked: dims must be 2 or 3")
+    if dims == 2 and same_class:
+        raise RuntimeError("nms_aabb_masked: the 2-D NMS has no same-class form")
+    if dims == 3 and cls is None:
+        raise RuntimeError("nms_aabb_masked: cls is required for dims = 3")
+    ins = [(center, torch.float32, "center"), (size, torch.float64, "size"),
+           (heading, torch.float64, "heading"), (score, torch.float32, "score")]
+    if cls is not None:
+        ins.append((cls, torch.int64, "cls"))
+    if valid is not None:
+        ins.append((valid, torch.int32, "valid"))
+    for t, dt, name in ins:
+        if not t.is_cuda or t.dtype != dt:
+            raise RuntimeError("%s must be a %s GPU tensor" % (name, dt))
+    s, n = score.shape
+    if n > 1024:
+        raise RuntimeError("nms_aabb_masked: at most 1024 boxes per scene")
+    if valid is not None and tuple(valid.shape) != (s, n):
+        raise RuntimeError("nms_aabb_masked: valid must be (%d, %d)" % (s, n))
+    picked = torch.zeros((s, n), dtype=torch.int32, device=score.device)
+    center, size, heading, score = (t.contiguous() for t in (center, size, heading, score))
+    cls = cls.contiguous() if cls is not None else None
+    valid = valid.contiguous() if valid is not None else None
+    with torch.cuda.device(score.device):
+        _L.check(_lib.lhs_nms_aabb_masked(s, n, center.data_ptr(), size.data_ptr(), heading.data_ptr(),
+                                          score.data_ptr(), cls.data_ptr() if cls is not None else None,
+                                          float(thresh), 1 if old_type else 0, 1 if same_class else 0,
+                                          dims, valid.data_ptr() if valid is not None else None,
+                                          picked.data_ptr(), _L.current_stream_ptr(score.device)),
+                 "lhs_nms_aabb_masked")
+    return picked.bool()
+
+
+BOX_POINT_CHUNK = 512  # points one workgroup of the count kernel stages (csrc/box_points.hip)
+
+
+def box_point_count_gpu(points, center, size, heading, out=None):
+    """points (S,N,3+C) f32 with xyz first, center (S,n,3) f32, size (S,n,3) f64 (l,w,h), heading
+    (S,n) f64, all in the depth frame -> count (S,n) int32: the points inside each oriented box,
+    len(extract_pc_in_box3d(...)[0]) of models/ap_helper.py:123-135 by the closed-form test of
+    include/lhs_hip.h.  `points` is read in place through its row stride (no xyz slice copy).
+    `out`: an (S,n) int32 tensor to overwrite (the entry point zero-fills it itself)."""
+    for t, dt, name in ((points, torch.float32, "points"), (center, torch.float32, "center"),
+                        (size, torch.float64, "size"), (heading, torch.float64, "heading")):
+        if not t.is_cuda or t.dtype != dt:
+            raise RuntimeError("%s must be a %s GPU tensor" % (name, dt))
+    s, n = heading.shape
+    if points.dim() != 3 or points.shape[0] != s or points.shape[2] < 3:
+        raise RuntimeError("box_point_count: points must be (%d, N, >= 3)" % s)
+    if tuple(center.shape) != (s, n, 3) or tuple(size.shape) != (s, n, 3):
+        raise RuntimeError("box_point_count: center and size must be (%d, %d, 3)" % (s, n))
+    npts, pstride = points.shape[1], points.shape[2]
+    if out is None:
+        out = torch.empty((s, n), dtype=torch.int32, device=heading.device)
+    elif not out.is_cuda or out.dtype != torch.int32 or tuple(out.shape) != (s, n) or not out.is_contiguous():
+        raise RuntimeError("box_point_count: out must be a contiguous (%d, %d) int32 GPU tensor" % (s, n))
+    count = out
+    if npts == 0 or s == 0 or n == 0:
+        return count.zero_()     # nothing to launch
+    points, center, size, heading = (t.contiguous() for t in (points, center, size, heading))
+    with torch.cuda.device(heading.device):
+        _L.check(_lib.lhs_box_point_count(s, n, npts, pstride, points.data_ptr(), center.data_ptr(),
+                                          size.data_ptr(), heading.data_ptr(), count.data_ptr(),
+                                          _L.current_stream_ptr(heading.device)), "lhs_box_point_count")
+    return count
+
+
 import ctypes  # noqa: E402
 
 _c_int, _c_float, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p

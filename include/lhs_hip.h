@@ -24,6 +24,33 @@ int lhs_nms3d_aabb(int scenes, int n, const float *center, const double *size,
                    const double *heading, const float *score, const long long *cls, double thresh,
                    int old_type, int same_class, int *picked, void *stream);
 
+/* the same NMS on a subset of the boxes, in three or two dimensions: what parse_predictions gets by
+ * calling utils/nms.py on boxes[nonempty_box_mask[i,:]==1] (models/ap_helper.py:139-203).
+ * valid (scenes,n) i32 or NULL (every box): a box with valid == 0 is neither a winner nor a
+ * suppressor and gets picked = 0; a scene with no valid box gives an all-zero row (the reference
+ * asserts there).  dims == 3: lhs_nms3d_aabb.  dims == 2: nms_2d_faster (utils/nms.py:52-83) on the
+ * camera x / camera z bounds of the same boxes (boxes_2d_with_prob, models/ap_helper.py:143-149);
+ * cls is not read and same_class must be 0.  n <= 1024; anything else: hipErrorInvalidValue. */
+int lhs_nms_aabb_masked(int scenes, int n, const float *center, const double *size,
+                        const double *heading, const float *score, const long long *cls,
+                        double thresh, int old_type, int same_class, int dims /* 2 or 3 */,
+                        const int *valid /* (scenes,n) i32 or NULL */, int *picked, void *stream);
+
+/* replaces the remove_empty_box loop of parse_predictions (models/ap_helper.py:123-135): B x K
+ * calls of extract_pc_in_box3d (sunrgbd/sunrgbd_utils.py:215-224), a Delaunay triangulation of the
+ * eight corners and a find_simplex over all points, per box.  count[s][j] = number of points p of
+ * scene s with, for d = p - center, c = cos(heading), s = sin(heading):
+ *   |c d.x - s d.y| <= l/2,  |s d.x + c d.y| <= w/2,  |d.z| <= h/2
+ * (the box frame in float64 rounded to float32, the per-pair arithmetic in float32).  Arguments as
+ * lhs_nms3d_aabb; any n.  Non-positive scenes, n or npts: returns 0 without a launch. */
+int lhs_box_point_count(int scenes, int n, int npts, int pstride,
+                        const float *points,      /* (scenes, npts, pstride) f32, xyz first, depth frame */
+                        const float *center,      /* (scenes, n, 3) f32, depth frame */
+                        const double *size,       /* (scenes, n, 3) f64  (l, w, h)   */
+                        const double *heading,    /* (scenes, n) f64                 */
+                        int *count,               /* (scenes, n) i32, written, not accumulated by the caller */
+                        void *stream);
+
 /* The rest of the pseudo-label filter around that NMS: get_pseudo_labels and the label transforms
  * of get_unlabeled_loss (models/loss_helper_unlabeled.py:364-445, :489-538, trans_center :24-36,
  * trans_size :39-51) as two launches (select, then -- after lhs_nms_samecls on the select's boxes --
