@@ -172,6 +172,8 @@ _SIGNATURES = {
                           ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp],
     "iou3d_corners_iou3d": [_c_int, _vp, _c_int, _vp, _vp, _vp],
     "iou3d_corners_best_match": [_c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "iou3d_eval_match": [_vp, _vp],
+    "iou3d_eval_mark": [_vp, _vp],
     "iou3d_nms_mask": [_vp, _vp, _c_int, _c_float, _vp],
     "iou3d_nms_normal_mask": [_vp, _vp, _c_int, _c_float, _vp],
     "iou3d_nms": [_vp, _c_int, _c_float, _c_int, _vp, _vp, _vp, _vp],

@@ -13,7 +13,12 @@ Differences, by construction: detections with exactly equal confidence keep thei
 reference's np.argsort(-confidence) leaves tie order to the sort implementation); a ground-truth
 class without any prediction gets AP = rec = prec = 0 (what eval_det_multiprocessing intends,
 :257-261; its list indexing misassigns results in that case).
+
+eval_match_gpu / eval_mark_gpu bind the two kernels of the device-resident form of all this
+(eval_helper.DeviceAPCalculator): the same matching on a batch's dense (scene, proposal, class) slots
+with every pair's IoU computed once, and the marking of all classes and thresholds in one launch.
 """
+import ctypes
 import importlib
 
 import numpy as np
@@ -53,6 +58,89 @@ def corners_best_match_gpu(det, gt_begin, gt_count, gt):
             nd, det.data_ptr(), gt_begin.data_ptr(), gt_count.data_ptr(), gt.data_ptr(), ovmax.data_ptr(),
             jmax.data_ptr(), _L.current_stream_ptr(det.device)), "iou3d_corners_best_match")
     return ovmax, jmax
+
+
+_vp, _ll = ctypes.c_void_p, ctypes.c_longlong
+EVAL_MAX_CLASS = 64  # include/iou3d_hip.h IOU3D_EVAL_MAX_CLASS
+
+
+class EvalMatchArgs(ctypes.Structure):  # field order == include/iou3d_hip.h
+    _fields_ = ([(n, ctypes.c_int) for n in ("B", "K", "G", "C")] +
+                [(n, _vp) for n in ("det", "keep", "det_cls", "gt", "gt_valid", "gt_cls", "ovmax", "jmax")])
+
+
+class EvalMarkArgs(ctypes.Structure):  # field order == include/iou3d_hip.h
+    _fields_ = ([("n", _ll), ("num_class", ctypes.c_int), ("num_thresh", ctypes.c_int), ("num_gt", _ll)] +
+                [(n, _vp) for n in ("seg", "ovmax", "gt_id", "npos", "thresh", "first", "cum_tp", "rec",
+                                    "prec", "ap", "last_rec")])
+
+
+def _device_inputs(what, tensors):
+    """dtype / device check, then contiguous tensors (bound by the caller until after the launch)."""
+    dev = tensors[0][0].device
+    out = []
+    for t, dt, name in tensors:
+        if not t.is_cuda or t.dtype != dt or t.device != dev:
+            raise RuntimeError("%s: %s must be a %s tensor on one GPU (there is no CPU path)" % (what, name, dt))
+        out.append(t.contiguous())
+    return out
+
+
+def eval_match_gpu(det, keep, det_cls, gt, gt_valid, gt_cls, num_class):
+    """det (B,K,8,3) f32, keep (B,K) bool, det_cls (B,K) i64, gt (B,G,8,3) f32, gt_valid (B,G) bool,
+    gt_cls (B,G) i64, all on the GPU; num_class = C >= 1: a slot per (proposal, class), 0: a slot per
+    proposal with class det_cls -> (ovmax (B,K,max(C,1)) f64, jmax i32), include/iou3d_hip.h
+    iou3d_eval_match: eval_det_cls' loop over the scene's ground truth of the slot's class."""
+    _L = importlib.import_module("3dioumatch_amd._lib")
+    det, keep, det_cls, gt, gt_valid, gt_cls = _device_inputs("eval_match", [
+        (det, torch.float32, "det"), (keep, torch.bool, "keep"), (det_cls, torch.int64, "det_cls"),
+        (gt, torch.float32, "gt"), (gt_valid, torch.bool, "gt_valid"), (gt_cls, torch.int64, "gt_cls")])
+    b, k = keep.shape
+    g = gt_valid.shape[1]
+    if tuple(det.shape) != (b, k, 8, 3) or tuple(det_cls.shape) != (b, k) or tuple(gt.shape) != (b, g, 8, 3) \
+            or tuple(gt_valid.shape) != (b, g) or tuple(gt_cls.shape) != (b, g):
+        raise RuntimeError("eval_match: det (B,K,8,3), keep / det_cls (B,K), gt (B,G,8,3), gt_valid / gt_cls (B,G)")
+    cm = max(int(num_class), 1)
+    ovmax = torch.empty((b, k, cm), dtype=torch.float64, device=det.device)
+    jmax = torch.empty((b, k, cm), dtype=torch.int32, device=det.device)
+    a = EvalMatchArgs()
+    a.B, a.K, a.G, a.C = b, k, g, int(num_class)
+    for name, t in (("det", det), ("keep", keep), ("det_cls", det_cls), ("gt", gt), ("gt_valid", gt_valid),
+                    ("gt_cls", gt_cls), ("ovmax", ovmax), ("jmax", jmax)):
+        setattr(a, name, t.data_ptr())
+    with torch.cuda.device(det.device):
+        _L.check(_L.lib.iou3d_eval_match(ctypes.byref(a), _L.current_stream_ptr(det.device)), "iou3d_eval_match")
+    return ovmax, jmax
+
+
+def eval_mark_gpu(seg, ovmax, gt_id, npos, thresholds, num_gt, curves=False):
+    """Detections in (class, score descending, insertion) order: seg (num_class+1) i64 rank ranges,
+    ovmax (n) f64, gt_id (n) i32, npos (num_class) i64, thresholds (T) f64, all on the GPU; num_gt:
+    ground-truth ids are below it -> (ap (T,num_class) f64, last_rec (T,num_class) f64, rec, prec
+    (T,n) f64 or None without `curves`), include/iou3d_hip.h iou3d_eval_mark."""
+    _L = importlib.import_module("3dioumatch_amd._lib")
+    seg, ovmax, gt_id, npos, thresholds = _device_inputs("eval_mark", [
+        (seg, torch.int64, "seg"), (ovmax, torch.float64, "ovmax"), (gt_id, torch.int32, "gt_id"),
+        (npos, torch.int64, "npos"), (thresholds, torch.float64, "thresholds")])
+    dev = ovmax.device
+    n, nc, nt = ovmax.numel(), npos.numel(), thresholds.numel()
+    if seg.numel() != nc + 1 or gt_id.numel() != n:
+        raise RuntimeError("eval_mark: seg (num_class+1), gt_id (n)")
+    first = torch.full((nt, int(num_gt)), torch.iinfo(torch.int32).max, dtype=torch.int32, device=dev)
+    cum_tp = torch.empty((nt, n), dtype=torch.int32, device=dev)
+    ap = torch.empty((nt, nc), dtype=torch.float64, device=dev)
+    last_rec = torch.empty((nt, nc), dtype=torch.float64, device=dev)
+    rec = torch.zeros((nt, n), dtype=torch.float64, device=dev) if curves else None
+    prec = torch.zeros((nt, n), dtype=torch.float64, device=dev) if curves else None
+    a = EvalMarkArgs()
+    a.n, a.num_class, a.num_thresh, a.num_gt = n, nc, nt, int(num_gt)
+    for name, t in (("seg", seg), ("ovmax", ovmax), ("gt_id", gt_id), ("npos", npos), ("thresh", thresholds),
+                    ("first", first), ("cum_tp", cum_tp), ("rec", rec), ("prec", prec), ("ap", ap),
+                    ("last_rec", last_rec)):
+        setattr(a, name, t.data_ptr() if t is not None else None)
+    with torch.cuda.device(dev):
+        _L.check(_L.lib.iou3d_eval_mark(ctypes.byref(a), _L.current_stream_ptr(dev)), "iou3d_eval_mark")
+    return ap, last_rec, rec, prec
 
 
 def _best_match(det, gt_begin, gt_count, gt, device):

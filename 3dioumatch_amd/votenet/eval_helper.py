@@ -15,6 +15,11 @@ parse_groundtruths (:224-307) and APCalculator (:382-435) complete the evaluatio
 train.py:evaluate_one_epoch; the average precision itself is votenet/eval_det.py (oriented-box IoU
 on the device).
 
+Both parsers are host listings of parse_predictions_device / parse_groundtruths_device, which return
+device tensors without a host copy; DeviceAPCalculator consumes those and keeps the whole evaluation
+on the device until one copy in compute_metrics (evaluate(..., device_ap=True) of votenet/inference.py
+and votenet/iou_opt.py).
+
 `remove_empty_box` (ap_helper.py:123-135) drops every proposal with fewer than five input points
 inside its oriented box before the NMS.  The reference asks scipy for a Delaunay triangulation of
 the eight corners per box; here one kernel (votenet/pseudo_nms.py:box_point_count_gpu) counts by
@@ -41,6 +46,20 @@ def _count_points(points, center, size, heading):
     return box_point_count_gpu(points, center, size, heading)
 
 
+def _eval_match(det, keep, det_cls, gt, gt_valid, gt_cls, num_class):
+    """(ovmax, jmax) (B,K,max(C,1)) of a batch's dense slots; the GPU kernel (tests substitute the
+    oracle)."""
+    from .eval_det import eval_match_gpu
+    return eval_match_gpu(det, keep, det_cls, gt, gt_valid, gt_cls, num_class)
+
+
+def _eval_mark(seg, ovmax, gt_id, npos, thresholds, num_gt, curves):
+    """(ap, last_rec, rec, prec) of ordered detections for all classes and thresholds; the GPU
+    kernel (tests substitute eval_det._mark)."""
+    from .eval_det import eval_mark_gpu
+    return eval_mark_gpu(seg, ovmax, gt_id, npos, thresholds, num_gt, curves)
+
+
 def _nms_masked(center, size, heading, score, cls, thresh, old_type, same_class, dims, valid):
     """(S,n) bool keep mask of the NMS on the boxes with valid != 0 (None: all), dims 2 or 3; the
     GPU kernel (tests substitute a host loop)."""
@@ -54,9 +73,12 @@ def corners_upright_camera(center, size64, heading64):
     (B,K,8,3) f32 corners in the upright camera frame, vertex order and float64 arithmetic of
     get_3d_box (utils/box_util.py:335-358) on flip_axis_to_camera centres (ap_helper.py:28-35)."""
     dev = center.device
-    sx = torch.tensor([1, 1, -1, -1, 1, 1, -1, -1], dtype=torch.float64, device=dev)
-    sy = torch.tensor([1, 1, 1, 1, -1, -1, -1, -1], dtype=torch.float64, device=dev)
-    sz = torch.tensor([1, -1, -1, 1, 1, -1, -1, 1], dtype=torch.float64, device=dev)
+    # the vertex signs (1,1,-1,-1,1,1,-1,-1), (1,1,1,1,-1,-1,-1,-1), (1,-1,-1,1,1,-1,-1,1) from the
+    # vertex number's bits: generated on the device, a tensor built from a list is a blocking copy
+    v = torch.arange(8, device=dev)
+    sx = (1 - 2 * ((v >> 1) & 1)).double()
+    sy = (1 - 2 * ((v >> 2) & 1)).double()
+    sz = (1 - 2 * ((v ^ (v >> 1)) & 1)).double()
     l, w, h = size64[..., 0:1], size64[..., 1:2], size64[..., 2:3]
     x, y, z = sx * l / 2, sy * h / 2, sz * w / 2                      # (B,K,8)
     c, s = torch.cos(heading64).unsqueeze(-1), torch.sin(heading64).unsqueeze(-1)
@@ -83,11 +105,17 @@ def decode_boxes(end_points, config):
 
 
 @torch.no_grad()
-def parse_predictions(end_points, config_dict):
-    """-> batch_pred_map_cls: per scene a list of (class, corners (8,3) ndarray, confidence), as
-    ap_helper.parse_predictions returns it; also fills end_points['pred_mask'] (B,K),
-    end_points['batch_pred_map_cls'] and, with `remove_empty_box`, end_points['nonempty_box_mask']
-    (B,K)."""
+def parse_predictions_device(end_points, config_dict):
+    """parse_predictions without its host listing: a dict of tensors on the end points' device,
+    computed without a host copy or a synchronising op.
+      corners   (B,K,8,3) f32  upright camera frame
+      pred_mask (B,K) bool     the NMS verdict
+      keep      (B,K) bool     pred_mask & (objectness probability > conf_thresh): the detections
+      cls       (B,K) i64      arg-max class
+      score     (B,K,C) f32 with `per_class_proposal`: sem_prob * obj_prob, the float32 product the
+                reference forms in numpy (ap_helper.py:213-214); otherwise (B,K) f32 obj_prob
+      nonempty  (B,K) i32      only with `remove_empty_box`
+    The config keys and branches are parse_predictions', which lists this dict on the host."""
     config = config_dict['dataset_config']
     center = end_points['center']
     sem_probs = torch.softmax(end_points['sem_cls_scores'], dim=-1)
@@ -117,44 +145,69 @@ def parse_predictions(end_points, config_dict):
                                 pred_sem_cls, config_dict['nms_iou'],
                                 config_dict['use_old_type_nms'], same_class, 3 if use_3d else 2,
                                 nonempty)
-    # one device->host copy of the small results, then the reference's list layout
+    out = {'corners': corners, 'pred_mask': pred_mask,
+           'keep': pred_mask & (obj_prob > config_dict['conf_thresh']), 'cls': pred_sem_cls,
+           'score': (sem_probs * obj_prob.unsqueeze(-1)) if config_dict['per_class_proposal'] else obj_prob}
     if nonempty is not None:
-        end_points['nonempty_box_mask'] = nonempty.cpu().numpy().astype(np.float64)
-    keep = (pred_mask & (obj_prob > config_dict['conf_thresh'])).cpu().numpy()
+        out['nonempty'] = nonempty
+    return out
+
+
+@torch.no_grad()
+def parse_predictions(end_points, config_dict):
+    """-> batch_pred_map_cls: per scene a list of (class, corners (8,3) ndarray, confidence), as
+    ap_helper.parse_predictions returns it; also fills end_points['pred_mask'] (B,K),
+    end_points['batch_pred_map_cls'] and, with `remove_empty_box`, end_points['nonempty_box_mask']
+    (B,K).  The host listing of parse_predictions_device."""
+    config = config_dict['dataset_config']
+    dev = parse_predictions_device(end_points, config_dict)
+    # one device->host copy of the small results, then the reference's list layout
+    if 'nonempty' in dev:
+        end_points['nonempty_box_mask'] = dev['nonempty'].cpu().numpy().astype(np.float64)
+    keep = dev['keep'].cpu().numpy()
     # (B,K) float64 numpy array of 0/1 like the reference's (ap_helper.py:141-155), so that
     # consumers such as dump_helper index / multiply it the same way
-    end_points['pred_mask'] = pred_mask.cpu().numpy().astype(np.float64)
-    corners_h = corners.cpu().numpy()
-    obj_h = obj_prob.cpu().numpy()
-    sem_h = sem_probs.cpu().numpy()
-    cls_h = pred_sem_cls.cpu().numpy()
+    end_points['pred_mask'] = dev['pred_mask'].cpu().numpy().astype(np.float64)
+    corners_h = dev['corners'].cpu().numpy()
+    score_h = dev['score'].cpu().numpy()
+    cls_h = dev['cls'].cpu().numpy()
     batch = []
     for i in range(keep.shape[0]):
         js = np.nonzero(keep[i])[0]
         if config_dict['per_class_proposal']:
-            cur = [(ii, corners_h[i, j], sem_h[i, j, ii] * obj_h[i, j])
+            cur = [(ii, corners_h[i, j], score_h[i, j, ii])
                    for ii in range(config.num_class) for j in js]
         else:
-            cur = [(int(cls_h[i, j]), corners_h[i, j], obj_h[i, j]) for j in js]
+            cur = [(int(cls_h[i, j]), corners_h[i, j], score_h[i, j]) for j in js]
         batch.append(cur)
     end_points['batch_pred_map_cls'] = batch
     return batch
 
 
 @torch.no_grad()
-def parse_groundtruths(end_points, config_dict):
-    """-> batch_gt_map_cls: per scene a list of (class, corners (8,3) float32 ndarray) of the boxes
-    with box_label_mask == 1 (ap_helper.py:224-307: groundtruths2corners3d + parse_groundtruths);
-    the corners of all B x MAX_NUM_OBJ labels are decoded in one batched float64 pass."""
+def parse_groundtruths_device(end_points, config_dict):
+    """parse_groundtruths without its host listing: corners (B,G,8,3) f32 of all B x MAX_NUM_OBJ
+    labels decoded in one batched float64 pass, valid (B,G) bool = box_label_mask == 1 and cls
+    (B,G) i64, on the labels' device and without a host copy."""
     config = config_dict['dataset_config']
     center = end_points['center_label'][:, :, 0:3].float()
     size64 = config.mean_size(center.device).double()[end_points['size_class_label'].long()] + \
         end_points['size_residual_label'].double()
     heading64 = config.class2angle_f64(end_points['heading_class_label'].long(),
                                        end_points['heading_residual_label'].float())
-    corners = corners_upright_camera(center, size64, heading64).cpu().numpy()
-    mask = (end_points['box_label_mask'] == 1).cpu().numpy()
-    sem = end_points['sem_cls_label'].cpu().numpy()
+    return {'corners': corners_upright_camera(center, size64, heading64),
+            'valid': end_points['box_label_mask'] == 1, 'cls': end_points['sem_cls_label'].long()}
+
+
+@torch.no_grad()
+def parse_groundtruths(end_points, config_dict):
+    """-> batch_gt_map_cls: per scene a list of (class, corners (8,3) float32 ndarray) of the boxes
+    with box_label_mask == 1 (ap_helper.py:224-307: groundtruths2corners3d + parse_groundtruths);
+    the host listing of parse_groundtruths_device."""
+    dev = parse_groundtruths_device(end_points, config_dict)
+    corners = dev['corners'].cpu().numpy()
+    mask = dev['valid'].cpu().numpy()
+    sem = dev['cls'].cpu().numpy()
     batch = [[(int(sem[i, j]), corners[i, j]) for j in np.nonzero(mask[i])[0]]
              for i in range(mask.shape[0])]
     end_points['batch_gt_map_cls'] = batch
@@ -200,3 +253,131 @@ class APCalculator(object):
         self.gt_map_cls = {}    # {scan_id: [(classname, bbox)]}
         self.pred_map_cls = {}  # {scan_id: [(classname, bbox, score)]}
         self.scan_cnt = 0
+
+
+class DeviceAPCalculator(object):
+    """APCalculator for the outputs of parse_predictions_device / parse_groundtruths_device, all
+    thresholds at once and without a host round trip per batch.
+
+    step() launches one match kernel (include/iou3d_hip.h iou3d_eval_match: every (proposal,
+    ground-truth box) IoU of the batch once, the best box per (proposal, class) slot) and appends the
+    batch's slots to a list of device tensors; nothing in it waits for the GPU.  compute_metrics()
+    concatenates, orders the slots by (class, score descending, (scan, proposal) order -- two stable
+    device sorts), marks true / false positives and integrates the precision envelope for every
+    class and threshold in one launch (iou3d_eval_mark) and makes ONE device->host copy.  The
+    results are eval_det's: the reported classes are those with a detection or a ground-truth box; a
+    class with ground truth and no detection reports 0 / 0 / 0; one with detections and no ground
+    truth NaN (0 / 0), as the host path does.
+
+    The store is dense: every (scene, proposal, class) slot of a batch is kept -- score f32, class
+    key i16, ovmax f64, ground-truth id i32 = 18 bytes -- whether the proposal survived the NMS or
+    not, because dropping the others needs either their count on the host or an unordered atomic
+    counter.  That is about 0.6 MB per ScanNet batch (8 x 256 x 18 slots) and about 0.3 GB for the
+    5050 scans of SUN RGB-D val (x 256 x 10).  Class ids are 0 .. 63.  There is no CPU path."""
+
+    def __init__(self, ap_iou_thresholds=(0.25, 0.5), class2type_map=None):
+        self.ap_iou_thresholds = tuple(float(t) for t in ap_iou_thresholds)
+        if not self.ap_iou_thresholds:
+            raise ValueError("DeviceAPCalculator: at least one IoU threshold")
+        self.class2type_map = class2type_map
+        self.reset()
+
+    def reset(self):
+        self._score, self._key, self._ovmax, self._gt_id = [], [], [], []
+        self._npos = None      # (MAX_CLASS + 1) i64 on the device: boxes per class, [-1]: ids out of range
+        self._gt_slots = 0     # ground-truth slots so far = the next batch's first ground-truth id
+        self.scan_cnt = 0
+
+    def step(self, pred, gt):
+        """pred: parse_predictions_device's dict, gt: parse_groundtruths_device's, of one batch."""
+        from .eval_det import EVAL_MAX_CLASS as nmax
+        keep, score, valid = pred['keep'], pred['score'], gt['valid']
+        b, k = keep.shape
+        g = valid.shape[1]
+        if valid.shape[0] != b:
+            raise ValueError("DeviceAPCalculator.step: %d scenes of predictions, %d of ground truth"
+                             % (b, valid.shape[0]))
+        c = score.shape[2] if score.dim() == 3 else 0
+        if self._gt_slots + b * g >= 2 ** 31:
+            raise ValueError("DeviceAPCalculator: more than 2^31 ground-truth slots")
+        dev = keep.device
+        ovmax, jmax = _eval_match(pred['corners'], keep, pred['cls'], gt['corners'], valid, gt['cls'], c)
+        if c > 0:
+            key = torch.arange(c, device=dev).expand(b, k, c)
+        else:
+            key = pred['cls'].unsqueeze(-1)
+            key = torch.where((key >= 0) & (key < nmax), key, nmax)
+        key = torch.where(keep.unsqueeze(-1), key, nmax + 1).to(torch.int16)   # nmax + 1: not a detection
+        first_id = self._gt_slots + torch.arange(b, device=dev).view(b, 1, 1) * g
+        self._score.append(score.reshape(-1).float())
+        self._key.append(key.reshape(-1))
+        self._ovmax.append(ovmax.reshape(-1))
+        self._gt_id.append((first_id + jmax.clamp(min=0)).to(torch.int32).reshape(-1))
+        if self._npos is None:
+            self._npos = torch.zeros(nmax + 1, dtype=torch.int64, device=dev)
+        gcls = gt['cls']
+        gkey = torch.where((gcls >= 0) & (gcls < nmax), gcls, nmax)
+        self._npos.scatter_add_(0, gkey.reshape(-1), valid.reshape(-1).to(torch.int64))
+        self._gt_slots += b * g
+        self.scan_cnt += b
+
+    def _evaluate(self, curves):
+        """-> per threshold (rec, prec, ap, last) dicts keyed by class; rec / prec hold the curves
+        only with `curves` (more host copies), `last` the recall at the class's last detection."""
+        from .eval_det import EVAL_MAX_CLASS as nmax
+        nt = len(self.ap_iou_thresholds)
+        if not self._score:
+            return [({}, {}, {}, {}) for _ in range(nt)]
+        score, key = torch.cat(self._score), torch.cat(self._key)
+        ovmax, gt_id = torch.cat(self._ovmax), torch.cat(self._gt_id)
+        dev = score.device
+        # (class, score descending, insertion): a stable sort by score, then a stable sort by class
+        by_score = torch.sort(-score, stable=True).indices
+        key_sorted, by_key = torch.sort(key[by_score], stable=True)
+        order = by_score[by_key]
+        seg = torch.searchsorted(key_sorted, torch.arange(nmax + 2, dtype=torch.int16, device=dev))
+        thr = torch.cat([torch.full((1,), t, dtype=torch.float64, device=dev) for t in self.ap_iou_thresholds])
+        ap, last, rec, prec = _eval_mark(seg[:nmax + 1].contiguous(), ovmax[order], gt_id[order],
+                                         self._npos[:nmax].contiguous(), thr, self._gt_slots, curves)
+        host = torch.cat([ap.reshape(-1), last.reshape(-1), seg.double(), self._npos.double()]).cpu().numpy()
+        ap_h, last_h = host[:nt * nmax].reshape(nt, nmax), host[nt * nmax:2 * nt * nmax].reshape(nt, nmax)
+        seg_h = host[2 * nt * nmax:2 * nt * nmax + nmax + 2].astype(np.int64)
+        npos_h = host[2 * nt * nmax + nmax + 2:].astype(np.int64)
+        if seg_h[nmax + 1] > seg_h[nmax] or npos_h[nmax] > 0:
+            raise ValueError("DeviceAPCalculator: class ids must be 0 .. %d" % (nmax - 1))
+        if curves:
+            rec, prec = rec.cpu().numpy(), prec.cpu().numpy()
+        out = []
+        for t in range(nt):
+            r, p, a, l = {}, {}, {}, {}
+            for c in range(nmax):
+                s0, s1 = int(seg_h[c]), int(seg_h[c + 1])
+                if s1 == s0 and npos_h[c] == 0:
+                    continue
+                if s1 == s0:
+                    r[c], p[c], a[c], l[c] = 0, 0, 0, 0
+                    continue
+                a[c], l[c] = ap_h[t, c], last_h[t, c]
+                if curves:
+                    r[c], p[c] = rec[t, s0:s1], prec[t, s0:s1]
+            out.append((r, p, a, l))
+        return out
+
+    def eval_det(self):
+        """-> per threshold (rec, prec, ap) dicts keyed by class, as eval_det.eval_det returns them."""
+        return [(r, p, a) for r, p, a, _ in self._evaluate(True)]
+
+    def compute_metrics(self):
+        """-> per threshold the dict APCalculator.compute_metrics returns."""
+        name = lambda key: self.class2type_map[key] if self.class2type_map else str(key)  # noqa: E731
+        ret = []
+        for _, _, ap, last in self._evaluate(False):
+            ret_dict = {}
+            for key in sorted(ap.keys()):
+                ret_dict['%s Average Precision' % name(key)] = ap[key]
+            ret_dict['mAP'] = np.mean(list(ap.values()))
+            for key in sorted(ap.keys()):
+                ret_dict['%s Recall' % name(key)] = last[key]
+            ret_dict['AR'] = np.mean([last[key] for key in sorted(ap.keys())])
+            ret.append(ret_dict)
+        return ret

@@ -239,19 +239,25 @@ def optimize_boxes(detector, end_points, opt_rate, opt_step=10, engine="auto"):
 
 
 def evaluate(detector, batches, config_dict, opt_step=0, opt_rate=5e-4, ap_iou_thresholds=(0.25, 0.5),
-             engine="auto"):
+             engine="auto", device_ap=False):
     """evaluate_one_epoch (opt_step = 0) / evaluate_with_opt (opt_step > 0) of the reference
     train.py:384-425 / :431-507, without the loss statistics: for every batch (a dict with
     'point_clouds' and the ground-truth labels parse_groundtruths reads) a no-grad forward, the
     IoU optimisation of the boxes, parse_predictions / parse_groundtruths and one APCalculator per
-    threshold.  Returns the list of compute_metrics() dicts, one per threshold."""
-    from .eval_helper import APCalculator, parse_groundtruths, parse_predictions
+    threshold.  Returns the list of compute_metrics() dicts, one per threshold.
+    device_ap: the device forms of the two parsers and one DeviceAPCalculator for all thresholds
+    instead (labels on the host are moved with non-blocking copies; no host round trip per batch)."""
+    from .eval_helper import (APCalculator, DeviceAPCalculator, parse_groundtruths, parse_groundtruths_device,
+                              parse_predictions, parse_predictions_device)
     if detector.training:
         raise ValueError("evaluate: the detector must be in eval mode")
     if opt_step > 0:
         _check_detector(detector)
     class2type = getattr(config_dict['dataset_config'], 'class2type', None)
-    calcs = [APCalculator(t, class2type) for t in ap_iou_thresholds]
+    if device_ap:
+        calc = DeviceAPCalculator(ap_iou_thresholds, class2type)
+    else:
+        calcs = [APCalculator(t, class2type) for t in ap_iou_thresholds]
     for batch in batches:
         with torch.no_grad():
             end_points = detector({'point_clouds': batch['point_clouds']})
@@ -259,9 +265,18 @@ def evaluate(detector, batches, config_dict, opt_step=0, opt_rate=5e-4, ap_iou_t
             end_points = optimize_boxes(detector, end_points, opt_rate, opt_step, engine)
         for key in batch:
             if key not in end_points:
-                end_points[key] = batch[key]
+                value = batch[key]
+                if device_ap and torch.is_tensor(value):
+                    value = value.to(end_points['center'].device, non_blocking=True)
+                end_points[key] = value
+        if device_ap:
+            calc.step(parse_predictions_device(end_points, config_dict),
+                      parse_groundtruths_device(end_points, config_dict))
+            continue
         pred = parse_predictions(end_points, config_dict)
         gt = parse_groundtruths(end_points, config_dict)
         for calc in calcs:
             calc.step(pred, gt)
+    if device_ap:
+        return calc.compute_metrics()
     return [calc.compute_metrics() for calc in calcs]

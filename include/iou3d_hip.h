@@ -83,6 +83,57 @@ int iou3d_corners_iou3d(int n, const float *a, int m, const float *b, double *io
 int iou3d_corners_best_match(int nd, const float *det, const int *gt_begin, const int *gt_count,
                              const float *gt, double *ovmax, int *jmax, void *stream);
 
+/* ---- device-resident AP: the per-batch match and the marking of all classes / thresholds ---- */
+
+#define IOU3D_EVAL_MAX_CLASS 64   /* class ids 0 .. 63 */
+
+/* Operands of iou3d_eval_match; `args` is a HOST struct of DEVICE pointers, all contiguous. */
+typedef struct EvalMatchArgs {
+  int B, K, G;                    /* scenes, proposals per scene (>= 1), ground-truth slots per scene (>= 0) */
+  int C;                          /* 0: single-class mode (one slot per proposal, class det_cls);
+                                     1 .. 64: one slot per (proposal, class), the proposal's box for each */
+  const float *det;               /* (B,K,8,3) f32 corners, upright camera frame */
+  const unsigned char *keep;      /* (B,K) bool: the proposal is a detection */
+  const long long *det_cls;       /* (B,K) i64, read only when C == 0 */
+  const float *gt;                /* (B,G,8,3) f32 corners */
+  const unsigned char *gt_valid;  /* (B,G) bool */
+  const long long *gt_cls;        /* (B,G) i64 */
+  double *ovmax;                  /* (B,K,max(C,1)) f64, every element written */
+  int *jmax;                      /* (B,K,max(C,1)) i32, every element written */
+} EvalMatchArgs;
+/* replaces the per-detection loop of eval_det_cls (utils/eval_det.py:128-141) for a whole batch in
+ * its dense layout: slot (b,k,c) <- the loop over g = 0 .. G-1 restricted to gt_valid[b,g] &&
+ * gt_cls[b,g] == c (c = det_cls[b,k] when C == 0), strict `>` from -inf, so the first maximum wins
+ * and a NaN IoU never does; jmax = that g, the index inside the scene.  (-inf, -1) for a proposal
+ * with keep == 0 and for a slot without such a box.  Every (b,k,g) IoU is computed once, whatever
+ * C is.  hipErrorInvalidValue unless 0 <= C <= 64, G >= 0, K >= 1, B >= 0. */
+int iou3d_eval_match(const EvalMatchArgs *args, void *stream);
+
+/* Operands of iou3d_eval_mark: n detections already ordered by (class ascending, score descending,
+ * insertion order); class c owns ranks seg[c] .. seg[c+1]-1. */
+typedef struct EvalMarkArgs {
+  long long n;                    /* detections in all, < 2^31 */
+  int num_class;                  /* 1 .. 64 */
+  int num_thresh;                 /* >= 1 */
+  long long num_gt;               /* ground-truth ids are 0 .. num_gt-1 */
+  const long long *seg;           /* (num_class+1) i64, ascending, seg[num_class] <= n */
+  const double *ovmax;            /* (n) f64 of iou3d_eval_match, in rank order */
+  const int *gt_id;               /* (n) i32 matched ground-truth id, read only where ovmax > threshold */
+  const long long *npos;          /* (num_class) i64 ground-truth boxes of the class */
+  const double *thresh;           /* (num_thresh) f64 */
+  int *first;                     /* (num_thresh, num_gt) i32 workspace, filled with INT_MAX by the caller */
+  int *cum_tp;                    /* (num_thresh, n) i32 workspace, no initialisation */
+  double *rec, *prec;             /* (num_thresh, n) f64 each, or both NULL: not wanted */
+  double *ap;                     /* (num_thresh, num_class) f64; 0 for a class without detections */
+  double *last_rec;               /* (num_thresh, num_class) f64: rec of the class's last rank; 0 likewise */
+} EvalMarkArgs;
+/* replaces the marking of eval_det_cls (utils/eval_det.py:119-157) and voc_ap (:29-61, the
+ * area-under-envelope form) for every class and threshold in one launch, one workgroup per (class,
+ * threshold): hit = ovmax > thr, the first hit of a ground-truth id in rank order is the true
+ * positive, prefix sums, rec = tp / npos, prec = tp / max(tp + fp, eps), the precision envelope and
+ * the sum over the ranks where rec changes -- float64 throughout. */
+int iou3d_eval_mark(const EvalMarkArgs *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
