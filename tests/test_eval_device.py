@@ -241,3 +241,95 @@ def test_eval_entry_points_gate_on_the_host():
         m = D.EvalMarkArgs()
         m.n, m.num_class, m.num_thresh, m.num_gt = n, nc, nt, 4
         assert lib.iou3d_eval_mark(ctypes.byref(m), None) != 0, (n, nc, nt)
+
+
+# ---------------------------------------------------------------------------------------------
+# the marking past one 256-detection chunk per class: eval_det._mark (the host path and
+# standin_mark above) against the plain loop of tests/eval_mark_cases.py
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("thr", [0.25, 0.5])
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_mark_matches_loop_reference(seed, thr):
+    import eval_mark_cases as M
+    _, D, _ = _mods()
+    case, want = M.mark_case(seed), M.reference(seed, thr)
+    checked = 0
+    for c, length in enumerate(M.LENGTHS):
+        if length == 0:
+            assert want[c] is None
+            continue
+        ov, gid, npos = M.segment(case, c)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rec, prec, ap = D._mark(-np.arange(length, dtype=np.float64), ov, gid.astype(np.int64), npos, thr, False)
+        wrec, wprec, wap = want[c]
+        np.testing.assert_array_equal(rec, wrec)        # NaN == NaN here
+        np.testing.assert_array_equal(prec, wprec)
+        assert (np.isnan(ap) and np.isnan(wap)) or abs(ap - wap) <= 1e-12, (c, ap, wap)
+        assert np.isnan(wap) == (npos == 0)
+        checked += 1
+    assert checked == 9
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_mark_case_builder_keeps_its_edges(seed):
+    """What tests/eval_mark_cases.py promises about mark_case, so that an edit cannot empty the case."""
+    import eval_mark_cases as M
+    case = M.mark_case(seed)
+    seg, npos = case["seg"], case["npos"]
+    assert tuple(np.diff(seg)) == M.LENGTHS and tuple(npos) == M.NPOS and len(case["ovmax"]) == 5631
+    assert case["ovmax"].dtype == np.float64 and case["gt_id"].dtype == np.int32 and seg.dtype == np.int64
+    assert case["num_gt"] == sum(M.NPOS) + 5
+    base = np.concatenate([[0], np.cumsum(npos)])
+    for c, length in enumerate(M.LENGTHS):
+        ov, gid, p = M.segment(case, c)
+        inf = np.isneginf(ov)
+        assert (gid[inf] == 0).all() and not np.isnan(ov).any()
+        assert ((gid[~inf] >= base[c]) & (gid[~inf] < base[c] + p)).all()
+        assert ((ov[~inf] >= 0) & (ov[~inf] <= 1)).all()
+        if length >= 255 and c not in (M.ALL_INF, M.REVERSED):
+            assert (ov == 0.25).any() and (ov == 0.5).any() and 0.05 * length < inf.sum() < 0.2 * length
+    ov, _, p = M.segment(case, M.ALL_INF)
+    assert p == 0 and len(ov) == 300 and np.isneginf(ov).all()
+    ov, _, _ = M.segment(case, M.REVERSED)
+    assert np.isneginf(ov[:M.REVERSED_FROM]).all() and M.REVERSED_FROM == 3 * M.CHUNK
+    for thr in (0.25, 0.5):
+        want = M.reference(seed, thr)
+        long = [c for c, length in enumerate(M.LENGTHS) if length > M.CHUNK and c != M.ALL_INF]
+        assert long == [4, 5, 6, 9, 10]
+        assert any(0 < want[c][2] < 1 for c in long)
+        assert any(want[c][0][-1] < 1 for c in long)
+        assert any(M.cross_chunk_claims(*M.segment(case, c)[:2], thr) >= 5 for c in long)
+        assert any(M.raised_chunks(want[c][1]) for c in long)
+        # the long score-ordered segments: 0 < AP < 1 in 513, 1000 and 2049, repeat claims across chunks in
+        # 1000 and 2049, a raised envelope in 513 and 1000, a final recall below 1 in 513
+        for c in (5, 6, 9):
+            assert 0 < want[c][2] < 1
+        for c in (6, 9):
+            assert M.cross_chunk_claims(*M.segment(case, c)[:2], thr) >= 5
+        for c in (5, 6):
+            assert M.raised_chunks(want[c][1])
+        assert want[5][0][-1] < 0.5
+        # the reversed segment: true positives only in its last chunk, every earlier chunk raised from it
+        rec, prec, ap = want[M.REVERSED]
+        assert rec[M.REVERSED_FROM - 1] == 0 and rec[-1] > 0 and ap > 0
+        assert M.raised_chunks(prec) == [0, 1, 2]
+        assert np.isnan(want[M.ALL_INF][2]) and np.isnan(want[M.ALL_INF][0]).all()
+    assert M.permuted_ids(case).dtype == np.int32 and not np.array_equal(M.permuted_ids(case), case["gt_id"])
+
+
+def test_mark_envelope_from_a_distant_chunk():
+    """eval_mark_cases.envelope_case: the case is what it says, and _mark agrees with the loop on it."""
+    import eval_mark_cases as M
+    _, D, _ = _mods()
+    case = M.envelope_case()
+    ov, gid, npos = M.segment(case, 0)
+    wrec, wprec, wap = M.loop_mark(ov, gid, npos, 0.5)
+    assert len(ov) == 3 * M.CHUNK + 5 and M.raised_chunks(wprec) == [0, 1, 2]
+    assert wprec.argmax() == len(ov) - 1 and wprec[-1] == 278 / 773 and wprec[:-1].max() < wprec[-1]
+    assert wrec[M.CHUNK - 1] == 16 / 300 and wrec[-1] == 278 / 300
+    # the AP with the envelope of the next chunk only, or of the chunks up to the third, is another number
+    assert abs(wap - (278 / 300) * (278 / 773)) < 0.05 * wap
+    rec, prec, ap = D._mark(-np.arange(len(ov), dtype=np.float64), ov, gid.astype(np.int64), npos, 0.5, False)
+    np.testing.assert_array_equal(rec, wrec)
+    np.testing.assert_array_equal(prec, wprec)
+    assert abs(ap - wap) <= 1e-12
