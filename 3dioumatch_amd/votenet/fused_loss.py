@@ -6,9 +6,18 @@ include/loss_hip.h; csrc/votenet_loss.hip, csrc/loss_core.h).
 of the loss with respect to every head output comes out of the same launch: the autograd node
 below just hands those buffers over, scaled by the incoming gradient of `loss`.  Only
 `end_points['loss']` (= 'detection_loss') is differentiable; the other entries are logging values.
+`get_pseudo_detection_loss_fused` is the same for the consistency loss on pseudo labels (the kernels'
+consistency mode), `get_semi_loss_fused` both losses of the semi-supervised step on one gradient buffer.
+
+Written once each: the differentiable inputs and their gradients (_HEADS, _grad_layout), the pass that
+fills VnLossArgs and launches (_loss_pass, both modes), the backward (_split_grads), the pseudo labels
+(_pseudo_labels), the end_points entries of each loss (_fill_supervised, _fill_unlabeled) and the
+switch of the consistency kernels (consistency_supported).
 """
+import collections
 import ctypes
 import importlib
+import math
 import os
 
 import torch
@@ -22,8 +31,25 @@ class VnLossTensor(ctypes.Structure):
 
 _PRED = ("agg_xyz", "obj", "center", "h_scores", "h_resn", "s_scores", "s_resn", "sem", "iou",
          "iou_jit", "seed_xyz", "vote_xyz", "jit_center", "jit_size", "jit_heading")
-_GRADS = ("g_obj", "g_center", "g_h_scores", "g_h_resn", "g_s_scores", "g_s_resn", "g_sem", "g_iou",
-          "g_iou_jit", "g_vote")
+
+# The differentiable inputs, in the order the gradients lie in a flat buffer: (VnLossArgs prediction
+# field, its gradient field, end_points key, shape of ONE scene's gradient as the kernels write it;
+# names are looked up in _dims).  The consistency mode has the first seven.
+_HEADS = (
+    ("obj", "g_obj", 'objectness_scores', ("K", 2)),
+    ("center", "g_center", 'center', ("K", 3)),
+    ("h_scores", "g_h_scores", 'heading_scores', ("K", "NH")),
+    ("h_resn", "g_h_resn", 'heading_residuals_normalized', ("K", "NH")),
+    ("s_scores", "g_s_scores", 'size_scores', ("K", "NS")),
+    ("s_resn", "g_s_resn", 'size_residuals_normalized', ("K", "NS", 3)),
+    ("sem", "g_sem", 'sem_cls_scores', ("K", "NC")),
+    ("iou", "g_iou", 'iou_scores', ("K", "NI")),
+    ("iou_jit", "g_iou_jit", 'iou_scores_jitter', ("K", "NI")),   # no jitter: no floats, gradient None
+    ("vote_xyz", "g_vote", 'vote_xyz', ("S*VF", 3)),
+)
+_FIELDS = tuple(row[0] for row in _HEADS)
+_GRADS = tuple(row[1] for row in _HEADS)
+_CONSISTENCY_GRADS = _GRADS[1:7]  # (g_obj is written too, as zeros: objectness is a statistic there)
 
 
 class VnLossArgs(ctypes.Structure):  # field order == include/loss_hip.h
@@ -106,167 +132,174 @@ def _view(t):
     return VnLossTensor(t.data_ptr(), s[0], s[1], s[2] if t.dim() > 2 else 0, s[3] if t.dim() > 3 else 0)
 
 
-def _label(end_points, key, dtype):
-    t = end_points[key]
-    if t.dtype != dtype:
-        raise RuntimeError("%s must be %s" % (key, dtype))
-    return t.contiguous()
+_Grad = collections.namedtuple("_Grad", "per size shape")  # floats per scene, floats, shape of n scenes
 
 
-class _FusedLabeledLoss(torch.autograd.Function):
-    """stats, labels <- launches; backward: the stored gradients times d(loss)."""
-
-    @staticmethod
-    def forward(ctx, end_points, config, nb, obj, center, h_scores, h_resn, s_scores, s_resn, sem,
-                iou, iou_jit, vote_xyz):
-        out = _labeled_pass(end_points, config, nb, obj, center, h_scores, h_resn, s_scores, s_resn,
-                            sem, iou, iou_jit, vote_xyz)
-        stats, objectness_label, objectness_mask, object_assignment, pred_bbox, extra = out
-        ctx.flat, ctx.shapes, ctx.sizes, ctx.has_jitter = extra
-        ctx.mark_non_differentiable(objectness_label, objectness_mask, object_assignment, pred_bbox)
-        # (the other outputs' gradients are never read: no zeros are made for them)
-        ctx.set_materialize_grads(False)
-        return stats, objectness_label, objectness_mask, object_assignment, pred_bbox
-
-    @staticmethod
-    def backward(ctx, g_stats, *unused):
-        scaled = ctx.flat * g_stats[ST_LOSS]
-        out, off = [], 0
-        for sh, n in zip(ctx.shapes, ctx.sizes):
-            out.append(scaled[off:off + n].view(sh) if n else None)
-            off += n
-        g_obj, g_center, g_hs, g_hr, g_ss, g_sr, g_sem, g_iou, g_jit, g_vote = out
-        return (None, None, None, g_obj, g_center, g_hs, g_hr, g_ss, g_sr, g_sem, g_iou,
-                g_jit if ctx.has_jitter else None, g_vote)
+def _dims(preds):
+    """What the gradient shapes are functions of, from the head outputs {prediction field: tensor}."""
+    vote = preds.get("vote_xyz")
+    return {"K": preds["center"].shape[1], "NH": preds["h_scores"].shape[2], "NS": preds["s_scores"].shape[2],
+            "NC": preds["sem"].shape[2], "NI": preds["iou"].shape[2] if "iou" in preds else 1,
+            "S*VF": 0 if vote is None else vote.shape[1], "jitter": preds.get("iou_jit") is not None}
 
 
-def _labeled_pass(end_points, config, nb, obj, center, h_scores, h_resn, s_scores, s_resn, sem, iou,
-                  iou_jit, vote_xyz, grad_dest=None, grad_scale=1.0):
-    """The supervised loss' launches on the first nb scenes.  grad_dest: {name of _GRADS: device
-    address} to write the gradient rows somewhere the caller owns (a buffer shared with the
-    consistency loss); None: a buffer of its own (returned in `extra`)."""
-    dev = center.device
-    k, g = center.shape[1], end_points['center_label'].shape[1]
-    s, vf = end_points['seed_xyz'].shape[1], vote_xyz.shape[1] // end_points['seed_xyz'].shape[1]
-    has_jitter = iou_jit is not None
-    rows = 2 * k if has_jitter else k
+def _grad_layout(dims, n):
+    """{gradient field: _Grad} of n scenes, in _GRADS order."""
+    layout = {}
+    for _, name, _, shape in _HEADS:
+        shape = tuple(dims.get(d, d) for d in shape)
+        per = 0 if name == "g_iou_jit" and not dims["jitter"] else math.prod(shape)
+        layout[name] = _Grad(per, n * per, (n,) + shape if per else (0,))
+    return layout
+
+
+def _carve(flat, layout, names):
+    """{gradient field: device address} of consecutive pieces of `flat`, in the order of `names`."""
+    dest, at = {}, flat.data_ptr()
+    for name in names:
+        dest[name] = at
+        at += 4 * layout[name].size
+    return dest
+
+
+def _split_grads(flat, g, layout, names=_GRADS):
+    """flat * g as one gradient per row of _HEADS (None: not among `names`, or no floats); `flat` holds
+    the pieces of `names` back to back."""
+    scaled = flat * g
+    out, at = [], 0
+    for name in _GRADS:
+        size = layout[name].size if name in names else 0
+        out.append(scaled[at:at + size].view(layout[name].shape) if size else None)
+        at += size
+    return tuple(out)
+
+
+_F32, _I64 = torch.float32, torch.int64
+# (VnLossArgs field = end_points key of the supervised loss, key among the pseudo labels, dtype)
+_LABELS = (('center_label', 'center', _F32), ('box_label_mask', 'mask', _F32),
+           ('heading_class_label', 'heading_class', _I64), ('heading_residual_label', 'heading_residual', _F32),
+           ('size_class_label', 'size_class', _I64), ('size_residual_label', 'size_residual', _F32),
+           ('sem_cls_label', 'sem_cls', _I64), ('vote_label', None, _F32), ('vote_label_mask', None, _I64))
+# (VnLossArgs tensor field, key) of the inputs without a gradient; the consistency mode has the first
+_INPUTS = (("agg_xyz", 'aggregated_vote_xyz'), ("seed_xyz", 'seed_xyz'))
+_JITTER_INPUTS = (("jit_center", 'jitter_center'), ("jit_size", 'jitter_size'), ("jit_heading", 'jitter_heading'))
+
+
+def _loss_pass(consistency, src, config, heads, grad_dest=None, grad_scale=1.0):
+    """The launches of one mode over the scenes of `heads`.
+
+    supervised: decode -> scene IoU -> forward_backward; `src` is end_points (_LABELS, seed_inds, _INPUTS,
+    _JITTER_INPUTS; their first scenes are read), `heads` the ten tensors of _HEADS cut to the labeled scenes
+    (iou_scores_jitter None: no jitter).  consistency: forward_backward alone with S = VF = N = 0, NI = 1;
+    `src` holds the pseudo labels and 'aggregated_vote_xyz', `heads` the first seven tensors.
+    grad_dest: {gradient field: device address} to write the gradient rows somewhere the caller owns (a buffer
+    both modes share); None: a buffer of its own.  Returns (stats, objectness_label, objectness_mask,
+    object_assignment, pred_bbox or None, that buffer or None, its _grad_layout)."""
+    preds = dict(zip(_FIELDS, heads))
+    center, has_jitter = preds["center"], preds.get("iou_jit") is not None
+    dev, (nb, k) = center.device, center.shape[:2]
+    dims = _dims(preds)
     a = VnLossArgs()
-    a.B, a.K, a.G, a.S, a.VF, a.N = nb, k, g, s, vf, end_points['vote_label'].shape[1]
-    a.NH, a.NS, a.NC, a.NI = h_scores.shape[2], s_scores.shape[2], sem.shape[2], iou.shape[2]
-    a.has_jitter = 1 if has_jitter else 0
-    a.grad_scale = float(grad_scale)
+    a.B, a.K, a.G = nb, k, src['center' if consistency else 'center_label'].shape[1]
+    a.NH, a.NS, a.NC, a.NI = dims["NH"], dims["NS"], dims["NC"], dims["NI"]
+    if not consistency:
+        a.S, a.N = src['seed_xyz'].shape[1], src['vote_label'].shape[1]
+        a.VF = dims["S*VF"] // a.S
+    a.has_jitter, a.consistency, a.grad_scale = int(has_jitter), int(consistency), float(grad_scale)
     keep = []  # tensors whose storage the struct points into
 
     def ptr(t):
         keep.append(t)
         return t.data_ptr()
-    for key, dt in (('center_label', torch.float32), ('box_label_mask', torch.float32),
-                    ('heading_class_label', torch.int64), ('heading_residual_label', torch.float32),
-                    ('size_class_label', torch.int64), ('size_residual_label', torch.float32),
-                    ('sem_cls_label', torch.int64), ('vote_label', torch.float32),
-                    ('vote_label_mask', torch.int64)):
-        setattr(a, key, ptr(_label(end_points, key, dt)))
-    seed_inds = end_points['seed_inds']
-    if seed_inds.dtype != torch.int32 or seed_inds.stride(1) != 1:
-        seed_inds = seed_inds.int().contiguous()
-    a.seed_inds, a.seed_inds_stride = ptr(seed_inds), seed_inds.stride(0)
+    for field, key, dt in _LABELS:
+        if consistency and key is None:
+            continue  # (no votes in this mode)
+        t = src[key if consistency else field]
+        if consistency and (t.dtype != dt or t.shape[0] != nb):
+            raise RuntimeError("pseudo label %s must be %s with %d scenes" % (key, dt, nb))
+        if t.dtype != dt:
+            raise RuntimeError("%s must be %s" % (field, dt))
+        setattr(a, field, ptr(t.contiguous()))
+    if not consistency:
+        seed_inds = src['seed_inds']
+        if seed_inds.dtype != torch.int32 or seed_inds.stride(1) != 1:
+            seed_inds = seed_inds.int().contiguous()
+        a.seed_inds, a.seed_inds_stride = ptr(seed_inds), seed_inds.stride(0)
     a.mean_size = ptr(config.mean_size(dev).contiguous())
-    preds = {"agg_xyz": end_points['aggregated_vote_xyz'], "obj": obj, "center": center,
-             "h_scores": h_scores, "h_resn": h_resn, "s_scores": s_scores, "s_resn": s_resn,
-             "sem": sem, "iou": iou, "iou_jit": iou_jit if has_jitter else iou,
-             "seed_xyz": end_points['seed_xyz'], "vote_xyz": vote_xyz}
-    if has_jitter:
-        preds.update(jit_center=end_points['jitter_center'], jit_size=end_points['jitter_size'],
-                     jit_heading=end_points['jitter_heading'])
-    else:
-        preds.update(jit_center=center, jit_size=center, jit_heading=center)
-    for name, t in preds.items():
+    for name, key in _INPUTS[:1] if consistency else _INPUTS + (_JITTER_INPUTS if has_jitter else ()):
+        preds[name] = src[key]
+    for name in _PRED:
+        t = preds.get(name)
+        if t is None:
+            t = center  # not read in this mode (or without jitter)
         if t.dtype != torch.float32 or t.device != dev:
             raise RuntimeError("%s must be a float32 tensor on %s" % (name, dev))
         keep.append(t)
         setattr(a, name, _view(t))
 
     f32 = dict(dtype=torch.float32, device=dev)
-    boxes = torch.empty((nb, rows, 7), **f32)
-    gt_boxes = torch.empty((nb, g, 7), **f32)
-    a.boxes, a.gt_boxes = ptr(boxes), ptr(gt_boxes)
-    _launch("votenet_loss_decode", a, dev)
-    iou_lab, iou_assign = _scene_iou(boxes, gt_boxes)
-    a.iou_lab, a.iou_assign = ptr(iou_lab), ptr(iou_assign)
-
-    stats = torch.empty(ST_COUNT, **f32)
-    objectness_label = torch.empty((nb, k), dtype=torch.int64, device=dev)
-    objectness_mask = torch.empty((nb, k), **f32)
-    object_assignment = torch.empty((nb, k), dtype=torch.int64, device=dev)
-    gt_nearest = torch.empty((nb, g), dtype=torch.int32, device=dev)
-    a.stats, a.objectness_label = ptr(stats), ptr(objectness_label)
-    a.objectness_mask, a.object_assignment = ptr(objectness_mask), ptr(object_assignment)
-    a.gt_nearest = ptr(gt_nearest)
+    pred_bbox = None
+    if not consistency:
+        boxes = torch.empty((nb, 2 * k if has_jitter else k, 7), **f32)
+        gt_boxes = torch.empty((nb, a.G, 7), **f32)
+        a.boxes, a.gt_boxes = ptr(boxes), ptr(gt_boxes)
+        _launch("votenet_loss_decode", a, dev)
+        iou_lab, iou_assign = _scene_iou(boxes, gt_boxes)
+        a.iou_lab, a.iou_assign = ptr(iou_lab), ptr(iou_assign)
+        pred_bbox = boxes[:, :k]
+    out = {"stats": torch.empty(ST_COUNT, **f32),
+           "objectness_label": torch.empty((nb, k), dtype=torch.int64, device=dev),
+           "objectness_mask": torch.empty((nb, k), **f32),
+           "object_assignment": torch.empty((nb, k), dtype=torch.int64, device=dev),
+           "gt_nearest": torch.empty((nb, a.G), dtype=torch.int32, device=dev)}
+    for name, t in out.items():
+        setattr(a, name, ptr(t))
     a.partials = ptr(torch.empty(max(1, _scratch_floats(a, dev)), **f32))
-    shapes = [(nb, k, 2), (nb, k, 3), (nb, k, a.NH), (nb, k, a.NH), (nb, k, a.NS),
-              (nb, k, a.NS, 3), (nb, k, a.NC), (nb, k, a.NI),
-              (nb, k, a.NI) if has_jitter else (0,), (nb, s * vf, 3)]
-    sizes = [int(torch.Size(sh).numel()) for sh in shapes]
+    layout = _grad_layout(dims, nb)
+    names = _GRADS[:7] if consistency else _GRADS
     flat = None
     if grad_dest is None:
-        flat = torch.empty(sum(sizes), **f32)  # every element is written by the kernel
-        off = 0
-        for name, n in zip(_GRADS, sizes):
-            setattr(a, name, flat.data_ptr() + 4 * off)
-            off += n
+        flat = torch.empty(sum(layout[name].size for name in names), **f32)  # every element is written by the kernel
+        grad_dest = _carve(flat, layout, names)
         keep.append(flat)
-    else:
-        for name in _GRADS:
-            setattr(a, name, grad_dest[name])
+    for name in names:
+        setattr(a, name, grad_dest[name])
     _launch("votenet_loss_forward_backward", a, dev)
-    pred_bbox = boxes[:, :k]
-    return (stats, objectness_label, objectness_mask, object_assignment, pred_bbox,
-            (flat, shapes, sizes, has_jitter))
+    return (out["stats"], out["objectness_label"], out["objectness_mask"], out["object_assignment"], pred_bbox,
+            flat, layout)
 
 
-def supported(end_points, supervised_inds):
-    return (supervised_inds is None or isinstance(supervised_inds, slice)) and \
-        'iou_scores' in end_points and end_points['center'].dim() == 3
+def _labeled_pass(end_points, config, nb, *heads, **grads):
+    """_loss_pass in its supervised mode; `heads` are cut to the nb labeled scenes"""
+    out = _loss_pass(False, end_points, config, heads, **grads)
+    return out[:5] + (out[5:],)
 
 
-def get_labeled_loss_fused(end_points, dataset_config, supervised_inds=None):
-    """Same contract as losses.get_labeled_loss for `supervised_inds` None (every scene) or
-    slice(0, n) (labeled scenes first)."""
-    nb = end_points['center'].shape[0] if supervised_inds is None else int(supervised_inds.stop)
-
-    def sel(key):
-        t = end_points[key]
-        return t if t.shape[0] == nb else t[:nb]
-    has_jitter = 'jitter_center' in end_points
-    stats, objectness_label, objectness_mask, object_assignment, pred_bbox = _FusedLabeledLoss.apply(
-        end_points, dataset_config, nb, sel('objectness_scores'), sel('center'), sel('heading_scores'),
-        sel('heading_residuals_normalized'), sel('size_scores'), sel('size_residuals_normalized'),
-        sel('sem_cls_scores'), sel('iou_scores'), sel('iou_scores_jitter') if has_jitter else None,
-        sel('vote_xyz'))
-    log = stats.detach()
-    for key, i in _STAT_KEYS.items():
-        end_points[key] = log[i]
-    if has_jitter:
-        for key, i in _JITTER_KEYS.items():
-            end_points[key] = log[i]
-    end_points['objectness_label'] = objectness_label
-    end_points['objectness_mask'] = objectness_mask
-    end_points['object_assignment'] = object_assignment
-    end_points['pred_bbox'] = pred_bbox
-    loss = stats[ST_LOSS]
-    end_points['detection_loss'] = loss
-    end_points['loss'] = loss
-    return loss, end_points
+def _consistency_pass(labels, config, agg_xyz, *heads, **grads):
+    """_loss_pass in its consistency mode on the scenes of `heads` (no pred_bbox)"""
+    out = _loss_pass(True, dict(labels, aggregated_vote_xyz=agg_xyz), config, heads, **grads)
+    return out[:4] + (out[5:],)
 
 
-_CONSISTENCY_GRADS = ("g_center", "g_h_scores", "g_h_resn", "g_s_scores", "g_s_resn", "g_sem")
-_CONSISTENCY_KEYS = {
-    'unlabeled_objectness_loss': ST_OBJ, 'unlabeled_pos_ratio': ST_POS_RATIO,
-    'unlabeled_neg_ratio': ST_NEG_RATIO, 'unlabeled_center_loss': ST_CENTER,
-    'unlabeled_heading_cls_loss': ST_HCLS, 'unlabeled_heading_reg_loss': ST_HREG,
-    'unlabeled_size_cls_loss': ST_SCLS, 'unlabeled_size_reg_loss': ST_SREG,
-    'unlabeled_sem_cls_loss': ST_SEM, 'unlabeled_box_loss': ST_BOX,
-}
+def _only_loss_differentiable(ctx, *others):
+    ctx.mark_non_differentiable(*others)
+    # (the other outputs' gradients are never read: no zeros are made for them)
+    ctx.set_materialize_grads(False)
+
+
+class _FusedLabeledLoss(torch.autograd.Function):
+    """stats, labels <- launches; backward: the stored gradients times d(loss)."""
+
+    @staticmethod
+    def forward(ctx, end_points, config, *heads):
+        stats, label, mask, assignment, pred_bbox, (ctx.flat, ctx.layout) = _labeled_pass(
+            end_points, config, heads[1].shape[0], *heads)
+        _only_loss_differentiable(ctx, label, mask, assignment, pred_bbox)
+        return stats, label, mask, assignment, pred_bbox
+
+    @staticmethod
+    def backward(ctx, g_stats, *unused):
+        return (None, None) + _split_grads(ctx.flat, g_stats[ST_LOSS], ctx.layout)
 
 
 class _FusedConsistencyLoss(torch.autograd.Function):
@@ -275,119 +308,15 @@ class _FusedConsistencyLoss(torch.autograd.Function):
     tensor version is ~90 small kernels forward and as many backward."""
 
     @staticmethod
-    def forward(ctx, labels, config, agg_xyz, obj, center, h_scores, h_resn, s_scores, s_resn, sem):
-        stats, objectness_label, objectness_mask, object_assignment, extra = _consistency_pass(
-            labels, config, agg_xyz, obj, center, h_scores, h_resn, s_scores, s_resn, sem)
-        ctx.flat, ctx.shapes, ctx.sizes = extra
-        ctx.mark_non_differentiable(objectness_label, objectness_mask, object_assignment)
-        # (the other outputs' gradients are never read: no zeros are made for them)
-        ctx.set_materialize_grads(False)
-        return stats, objectness_label, objectness_mask, object_assignment
+    def forward(ctx, labels, config, agg_xyz, *heads):
+        stats, label, mask, assignment, (ctx.flat, ctx.layout) = _consistency_pass(labels, config, agg_xyz, *heads)
+        _only_loss_differentiable(ctx, label, mask, assignment)
+        return stats, label, mask, assignment
 
     @staticmethod
     def backward(ctx, g_stats, *unused):
-        first = ctx.sizes[0]  # (the objectness rows are zeros: no gradient)
-        scaled = ctx.flat[first:] * g_stats[ST_LOSS]
-        out, off = [], 0
-        for sh, n in zip(ctx.shapes[1:], ctx.sizes[1:]):
-            out.append(scaled[off:off + n].view(sh))
-            off += n
-        return (None, None, None, None) + tuple(out)
-
-
-def _consistency_pass(labels, config, agg_xyz, obj, center, h_scores, h_resn, s_scores, s_resn, sem,
-                      grad_dest=None, grad_scale=1.0):
-    """The consistency mode's launches; grad_dest / grad_scale as in _labeled_pass (names: g_obj and
-    _CONSISTENCY_GRADS)."""
-    dev = center.device
-    nb, k = center.shape[:2]
-    g = labels['center'].shape[1]
-    a = VnLossArgs()
-    a.B, a.K, a.G, a.S, a.VF, a.N = nb, k, g, 0, 0, 0
-    a.NH, a.NS, a.NC, a.NI = h_scores.shape[2], s_scores.shape[2], sem.shape[2], 1
-    a.has_jitter, a.consistency = 0, 1
-    a.grad_scale = float(grad_scale)
-    keep = []
-
-    def ptr(t):
-        keep.append(t)
-        return t.data_ptr()
-    for field, key, dt in (('center_label', 'center', torch.float32), ('box_label_mask', 'mask', torch.float32),
-                           ('heading_class_label', 'heading_class', torch.int64),
-                           ('heading_residual_label', 'heading_residual', torch.float32),
-                           ('size_class_label', 'size_class', torch.int64),
-                           ('size_residual_label', 'size_residual', torch.float32),
-                           ('sem_cls_label', 'sem_cls', torch.int64)):
-        t = labels[key]
-        if t.dtype != dt or t.shape[0] != nb:
-            raise RuntimeError("pseudo label %s must be %s with %d scenes" % (key, dt, nb))
-        setattr(a, field, ptr(t.contiguous()))
-    a.mean_size = ptr(config.mean_size(dev).contiguous())
-    preds = {"agg_xyz": agg_xyz, "obj": obj, "center": center, "h_scores": h_scores, "h_resn": h_resn,
-             "s_scores": s_scores, "s_resn": s_resn, "sem": sem}
-    for name, t in preds.items():
-        if t.dtype != torch.float32 or t.device != dev:
-            raise RuntimeError("%s must be a float32 tensor on %s" % (name, dev))
-        keep.append(t)
-        setattr(a, name, _view(t))
-    for name in ("iou", "iou_jit", "seed_xyz", "vote_xyz", "jit_center", "jit_size", "jit_heading"):
-        setattr(a, name, _view(center))  # unused in this mode
-    f32 = dict(dtype=torch.float32, device=dev)
-    stats = torch.empty(ST_COUNT, **f32)
-    objectness_label = torch.empty((nb, k), dtype=torch.int64, device=dev)
-    objectness_mask = torch.empty((nb, k), **f32)
-    object_assignment = torch.empty((nb, k), dtype=torch.int64, device=dev)
-    gt_nearest = torch.empty((nb, g), dtype=torch.int32, device=dev)
-    a.stats, a.objectness_label = ptr(stats), ptr(objectness_label)
-    a.objectness_mask, a.object_assignment = ptr(objectness_mask), ptr(object_assignment)
-    a.gt_nearest = ptr(gt_nearest)
-    a.partials = ptr(torch.empty(max(1, _scratch_floats(a, dev)), **f32))
-    shapes = [(nb, k, 2), (nb, k, 3), (nb, k, a.NH), (nb, k, a.NH), (nb, k, a.NS), (nb, k, a.NS, 3),
-              (nb, k, a.NC)]
-    sizes = [int(torch.Size(sh).numel()) for sh in shapes]
-    flat = None
-    if grad_dest is None:
-        flat = torch.empty(sum(sizes), **f32)  # every element is written by the kernel
-        off = 0
-        for name, n in zip(("g_obj",) + _CONSISTENCY_GRADS, sizes):
-            setattr(a, name, flat.data_ptr() + 4 * off)
-            off += n
-        keep.append(flat)
-    else:
-        for name in ("g_obj",) + _CONSISTENCY_GRADS:
-            setattr(a, name, grad_dest[name])
-    _launch("votenet_loss_forward_backward", a, dev)
-    return stats, objectness_label, objectness_mask, object_assignment, (flat, shapes, sizes)
-
-
-def get_pseudo_detection_loss_fused(end_points, labeled_num, config):
-    """Same contract as losses_unlabeled.get_pseudo_detection_loss (same end_points keys)."""
-    tail = slice(labeled_num, None)
-    mask = end_points['unlabeled_box_label_mask']
-    center = end_points['unlabeled_center_label'][:, :, 0:3]
-    # (the reference masks the centres of empty slots in place, loss_helper_unlabeled.py:150-152)
-    center = torch.where((1 - mask).unsqueeze(-1).bool(), torch.full_like(center, -1000), center)
-    end_points['unlabeled_center_label'] = center
-    labels = {'center': center, 'mask': mask.float(),
-              'heading_class': end_points['unlabeled_heading_class_label'],
-              'heading_residual': end_points['unlabeled_heading_residual_label'],
-              'size_class': end_points['unlabeled_size_class_label'],
-              'size_residual': end_points['unlabeled_size_residual_label'],
-              'sem_cls': end_points['unlabeled_sem_cls_label']}
-    stats, obj_label, obj_mask, assignment = _FusedConsistencyLoss.apply(
-        labels, config, end_points['aggregated_vote_xyz'][tail], end_points['objectness_scores'][tail],
-        end_points['center'][tail], end_points['heading_scores'][tail],
-        end_points['heading_residuals_normalized'][tail], end_points['size_scores'][tail],
-        end_points['size_residuals_normalized'][tail], end_points['sem_cls_scores'][tail])
-    log = stats.detach()
-    for key, i in _CONSISTENCY_KEYS.items():
-        end_points[key] = log[i]
-    end_points['unlabeled_objectness_label'] = obj_label
-    end_points['unlabeled_objectness_mask'] = obj_mask
-    end_points['unlabeled_object_assignment'] = assignment
-    loss = stats[ST_LOSS]
-    end_points['unlabeled_detection_loss'] = loss
-    return loss, end_points
+        behind = ctx.flat[ctx.layout["g_obj"].size:]  # (the objectness rows are zeros: no gradient)
+        return (None, None, None) + _split_grads(behind, g_stats[ST_LOSS], ctx.layout, _CONSISTENCY_GRADS)[:7]
 
 
 class _FusedSemiLoss(torch.autograd.Function):
@@ -399,95 +328,122 @@ class _FusedSemiLoss(torch.autograd.Function):
     and a copy per slice (slice_backward) and an addition per output."""
 
     @staticmethod
-    def forward(ctx, end_points, config, ln, weight, labels, obj, center, h_scores, h_resn, s_scores,
-                s_resn, sem, iou, iou_jit, vote_xyz):
-        dev = center.device
-        bt, k = center.shape[:2]
-        has_jitter = iou_jit is not None
-        nh, ns, nc, ni = h_scores.shape[2], s_scores.shape[2], sem.shape[2], iou.shape[2]
-        rows = [k * 2, k * 3, k * nh, k * nh, k * ns, k * ns * 3, k * nc, k * ni,
-                k * ni if has_jitter else 0, vote_xyz.shape[1] * 3]      # floats per scene, _GRADS order
-        shapes = [(bt, k, 2), (bt, k, 3), (bt, k, nh), (bt, k, nh), (bt, k, ns), (bt, k, ns, 3),
-                  (bt, k, nc), (bt, k, ni), (bt, k, ni) if has_jitter else (0,), (bt, vote_xyz.shape[1], 3)]
-        sizes = [bt * r for r in rows]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)  # (IoU / vote rows of the unlabeled scenes stay zero)
-        base, off = {}, 0
-        for name, n in zip(_GRADS, sizes):
-            base[name] = flat.data_ptr() + 4 * off
-            off += n
-        head = lambda t: t[:ln]  # noqa: E731
-        tail = lambda t: t[ln:]  # noqa: E731
-        out_l = _labeled_pass(end_points, config, ln, head(obj), head(center), head(h_scores), head(h_resn),
-                              head(s_scores), head(s_resn), head(sem), head(iou),
-                              head(iou_jit) if has_jitter else None, head(vote_xyz), grad_dest=base)
-        stats_l, lab_l, mask_l, assign_l, pred_bbox, _ = out_l
-        row_of = dict(zip(_GRADS, rows))
-        dest_u = {name: base[name] + 4 * ln * row_of[name] for name in ("g_obj",) + _CONSISTENCY_GRADS}
+    def forward(ctx, end_points, config, ln, weight, labels, *heads):
+        preds = dict(zip(_FIELDS, heads))
+        layout = _grad_layout(_dims(preds), preds["center"].shape[0])
+        # (the IoU / vote rows of the unlabeled scenes stay zero)
+        flat = torch.zeros(sum(g.size for g in layout.values()), dtype=torch.float32, device=preds["center"].device)
+        base = _carve(flat, layout, _GRADS)
+        stats_l, lab_l, mask_l, assign_l, pred_bbox, _ = _labeled_pass(
+            end_points, config, ln, *[t if t is None else t[:ln] for t in heads], grad_dest=base)
+        dest_u = {name: base[name] + 4 * ln * layout[name].per for name in _GRADS[:7]}
         stats_u, lab_u, mask_u, assign_u, _ = _consistency_pass(
-            labels, config, tail(end_points['aggregated_vote_xyz']), tail(obj), tail(center), tail(h_scores),
-            tail(h_resn), tail(s_scores), tail(s_resn), tail(sem), grad_dest=dest_u, grad_scale=weight)
+            labels, config, end_points['aggregated_vote_xyz'][ln:], *[t[ln:] for t in heads[:7]],
+            grad_dest=dest_u, grad_scale=weight)
         total = stats_l[ST_LOSS] + stats_u[ST_LOSS] * weight
-        ctx.flat, ctx.shapes, ctx.sizes, ctx.has_jitter = flat, shapes, sizes, has_jitter
-        ctx.mark_non_differentiable(stats_l, stats_u, lab_l, mask_l, assign_l, pred_bbox, lab_u, mask_u, assign_u)
-        # (the other outputs' gradients are never read: no zeros are made for them)
-        ctx.set_materialize_grads(False)
+        ctx.flat, ctx.layout = flat, layout
+        _only_loss_differentiable(ctx, stats_l, stats_u, lab_l, mask_l, assign_l, pred_bbox, lab_u, mask_u, assign_u)
         return total, stats_l, stats_u, lab_l, mask_l, assign_l, pred_bbox, lab_u, mask_u, assign_u
 
     @staticmethod
     def backward(ctx, g_total, *unused):
-        scaled = ctx.flat * g_total
-        out, off = [], 0
-        for sh, n in zip(ctx.shapes, ctx.sizes):
-            out.append(scaled[off:off + n].view(sh) if n else None)
-            off += n
-        g_obj, g_center, g_hs, g_hr, g_ss, g_sr, g_sem, g_iou, g_jit, g_vote = out
-        return (None, None, None, None, None, g_obj, g_center, g_hs, g_hr, g_ss, g_sr, g_sem, g_iou,
-                g_jit if ctx.has_jitter else None, g_vote)
+        return (None, None, None, None, None) + _split_grads(ctx.flat, g_total, ctx.layout)
+
+
+_CONSISTENCY_KEYS = {
+    'unlabeled_objectness_loss': ST_OBJ, 'unlabeled_pos_ratio': ST_POS_RATIO,
+    'unlabeled_neg_ratio': ST_NEG_RATIO, 'unlabeled_center_loss': ST_CENTER,
+    'unlabeled_heading_cls_loss': ST_HCLS, 'unlabeled_heading_reg_loss': ST_HREG,
+    'unlabeled_size_cls_loss': ST_SCLS, 'unlabeled_size_reg_loss': ST_SREG,
+    'unlabeled_sem_cls_loss': ST_SEM, 'unlabeled_box_loss': ST_BOX,
+}
+
+
+def supported(end_points, supervised_inds):
+    return (supervised_inds is None or isinstance(supervised_inds, slice)) and \
+        'iou_scores' in end_points and end_points['center'].dim() == 3
+
+
+def consistency_supported(end_points):
+    """the consistency kernels may run (VOTENET_FUSED_LOSS=0 or VOTENET_FUSED_CONSISTENCY=0: tensor operations)"""
+    return (enabled() and os.environ.get("VOTENET_FUSED_CONSISTENCY", "1") != "0"
+            and available(end_points['center'].device) and end_points['center'].dim() == 3)
 
 
 def semi_loss_supported(end_points, labeled_num):
-    dev = end_points['center'].device
-    return (enabled() and os.environ.get("VOTENET_FUSED_SEMI_LOSS", "1") != "0" and available(dev)
-            and os.environ.get("VOTENET_FUSED_CONSISTENCY", "1") != "0"
-            and 'iou_scores' in end_points and end_points['center'].dim() == 3
-            and 0 < labeled_num < end_points['center'].shape[0])
+    return (consistency_supported(end_points) and os.environ.get("VOTENET_FUSED_SEMI_LOSS", "1") != "0"
+            and 'iou_scores' in end_points and 0 < labeled_num < end_points['center'].shape[0])
+
+
+def _head_outputs(end_points, cut, count=len(_HEADS)):
+    """cut(head output) of the first `count` rows of _HEADS (iou_scores_jitter None: no jitter)"""
+    return [cut(end_points[key]) if key != 'iou_scores_jitter' or 'jitter_center' in end_points else None
+            for _, _, key, _ in _HEADS[:count]]
+
+
+def _pseudo_labels(end_points):
+    """{pseudo-label key of _LABELS: end_points['unlabeled_' + field]}; the centres of empty slots are masked as the
+    reference does in place (loss_helper_unlabeled.py:150-152), and stored back"""
+    mask = end_points['unlabeled_box_label_mask']
+    center = end_points['unlabeled_center_label'][:, :, 0:3]
+    center = torch.where((1 - mask).unsqueeze(-1).bool(), torch.full_like(center, -1000), center)
+    end_points['unlabeled_center_label'] = center
+    labels = {key: end_points['unlabeled_' + field] for field, key, _ in _LABELS if key}
+    labels['mask'] = mask.float()
+    return labels
+
+
+def _fill_supervised(end_points, stats, objectness_label, objectness_mask, object_assignment, pred_bbox):
+    log = stats.detach()
+    for key, i in _STAT_KEYS.items():
+        end_points[key] = log[i]
+    if 'jitter_center' in end_points:
+        for key, i in _JITTER_KEYS.items():
+            end_points[key] = log[i]
+    end_points['objectness_label'] = objectness_label
+    end_points['objectness_mask'] = objectness_mask
+    end_points['object_assignment'] = object_assignment
+    end_points['pred_bbox'] = pred_bbox
+    end_points['detection_loss'] = stats[ST_LOSS]
+
+
+def _fill_unlabeled(end_points, stats, objectness_label, objectness_mask, object_assignment):
+    log = stats.detach()
+    for key, i in _CONSISTENCY_KEYS.items():
+        end_points[key] = log[i]
+    end_points['unlabeled_objectness_label'] = objectness_label
+    end_points['unlabeled_objectness_mask'] = objectness_mask
+    end_points['unlabeled_object_assignment'] = object_assignment
+    end_points['unlabeled_detection_loss'] = stats[ST_LOSS]
+
+
+def get_labeled_loss_fused(end_points, dataset_config, supervised_inds=None):
+    """Same contract as losses.get_labeled_loss for `supervised_inds` None (every scene) or
+    slice(0, n) (labeled scenes first)."""
+    nb = end_points['center'].shape[0] if supervised_inds is None else int(supervised_inds.stop)
+    heads = _head_outputs(end_points, lambda t: t if t.shape[0] == nb else t[:nb])
+    _fill_supervised(end_points, *_FusedLabeledLoss.apply(end_points, dataset_config, *heads))
+    loss = end_points['loss'] = end_points['detection_loss']
+    return loss, end_points
+
+
+def get_pseudo_detection_loss_fused(end_points, labeled_num, config):
+    """Same contract as losses_unlabeled.get_pseudo_detection_loss (same end_points keys)."""
+    tail = slice(labeled_num, None)
+    labels = _pseudo_labels(end_points)
+    _fill_unlabeled(end_points, *_FusedConsistencyLoss.apply(
+        labels, config, end_points['aggregated_vote_xyz'][tail], *_head_outputs(end_points, lambda t: t[tail], 7)))
+    return end_points['unlabeled_detection_loss'], end_points
 
 
 def get_semi_loss_fused(end_points, config, labeled_num, weight):
     """(loss, end_points) with loss = detection_loss + weight * unlabeled_detection_loss and every key
     get_labeled_loss_fused and get_pseudo_detection_loss_fused fill; the pseudo labels
     (`unlabeled_*_label`, `unlabeled_box_label_mask`) are already in end_points."""
-    mask = end_points['unlabeled_box_label_mask']
-    center = end_points['unlabeled_center_label'][:, :, 0:3]
-    center = torch.where((1 - mask).unsqueeze(-1).bool(), torch.full_like(center, -1000), center)
-    end_points['unlabeled_center_label'] = center
-    labels = {'center': center, 'mask': mask.float(),
-              'heading_class': end_points['unlabeled_heading_class_label'],
-              'heading_residual': end_points['unlabeled_heading_residual_label'],
-              'size_class': end_points['unlabeled_size_class_label'],
-              'size_residual': end_points['unlabeled_size_residual_label'],
-              'sem_cls': end_points['unlabeled_sem_cls_label']}
-    has_jitter = 'jitter_center' in end_points
-    (total, stats_l, stats_u, lab_l, mask_l, assign_l, pred_bbox, lab_u, mask_u, assign_u) = _FusedSemiLoss.apply(
-        end_points, config, int(labeled_num), float(weight), labels, end_points['objectness_scores'],
-        end_points['center'], end_points['heading_scores'], end_points['heading_residuals_normalized'],
-        end_points['size_scores'], end_points['size_residuals_normalized'], end_points['sem_cls_scores'],
-        end_points['iou_scores'], end_points['iou_scores_jitter'] if has_jitter else None,
-        end_points['vote_xyz'])
-    log = stats_l.detach()
-    for key, i in _STAT_KEYS.items():
-        end_points[key] = log[i]
-    if has_jitter:
-        for key, i in _JITTER_KEYS.items():
-            end_points[key] = log[i]
-    end_points['objectness_label'], end_points['objectness_mask'] = lab_l, mask_l
-    end_points['object_assignment'], end_points['pred_bbox'] = assign_l, pred_bbox
-    end_points['detection_loss'] = log[ST_LOSS]
-    logu = stats_u.detach()
-    for key, i in _CONSISTENCY_KEYS.items():
-        end_points[key] = logu[i]
-    end_points['unlabeled_objectness_label'], end_points['unlabeled_objectness_mask'] = lab_u, mask_u
-    end_points['unlabeled_object_assignment'] = assign_u
-    end_points['unlabeled_detection_loss'] = logu[ST_LOSS]
+    labels = _pseudo_labels(end_points)
+    total, stats_l, stats_u, lab_l, mask_l, assign_l, pred_bbox, lab_u, mask_u, assign_u = _FusedSemiLoss.apply(
+        end_points, config, int(labeled_num), float(weight), labels, *_head_outputs(end_points, lambda t: t))
+    _fill_supervised(end_points, stats_l, lab_l, mask_l, assign_l, pred_bbox)
+    _fill_unlabeled(end_points, stats_u, lab_u, mask_u, assign_u)
     end_points['loss'] = total
     return total, end_points

@@ -287,8 +287,7 @@ def get_pseudo_detection_loss(end_points, labeled_num, config):
     the supervised loss in their consistency mode (fused_loss.get_pseudo_detection_loss_fused;
     VOTENET_FUSED_LOSS=0 or VOTENET_FUSED_CONSISTENCY=0 keep the tensor operations below)."""
     from . import fused_loss
-    if fused_loss.enabled() and os.environ.get("VOTENET_FUSED_CONSISTENCY", "1") != "0" and \
-            fused_loss.available(end_points['center'].device) and end_points['center'].dim() == 3:
+    if fused_loss.consistency_supported(end_points):
         return fused_loss.get_pseudo_detection_loss_fused(end_points, labeled_num, config)
     obj_loss, obj_label, obj_mask, assignment = compute_objectness_loss(end_points, labeled_num)
     end_points['unlabeled_objectness_loss'] = obj_loss

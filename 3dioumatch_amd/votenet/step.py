@@ -820,7 +820,8 @@ class SemiSupervisedStep(SupervisedStep):
         from . import fused_loss
         if fused_loss.semi_loss_supported(end_points, labeled):
             # both losses as ONE autograd node over one gradient buffer per head output
-            # (fused_loss._FusedSemiLoss); the pseudo labels first, without their loss
+            # (fused_loss._FusedSemiLoss: fused_loss._loss_pass in its supervised mode on the labeled
+            # scenes, in its consistency mode on the others); the pseudo labels first, without their loss
             _, end_points = unlabeled_loss(labels_only=True)
             loss, end_points = fused_loss.get_semi_loss_fused(end_points, self.cfg, labeled,
                                                               self.unlabeled_loss_weight)

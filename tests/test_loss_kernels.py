@@ -3,9 +3,9 @@ loss_finalize_kernel; csrc/loss_core.h; votenet/fused_loss.py) against their for
 multi-workgroup shapes.
 
 tests/test_fused_loss.py and the train-step tests reach these kernels through a whole detector at B = 2,
-K = 64 and compare parameter gradients fp32 against fp32.  Here the real binding (_labeled_pass,
-_consistency_pass) is driven without a network on seeded inputs (tests/loss_kernel_cases.py) and every
-output is compared with a float64 evaluation of the formulas:
+K = 64 and compare parameter gradients fp32 against fp32.  Here the real binding (_loss_pass, the one pass
+builder, in both of its modes) is driven without a network on seeded inputs (tests/loss_kernel_cases.py) and
+every output is compared with a float64 evaluation of the formulas:
 
   * objectness_label / objectness_mask / object_assignment / gt_nearest: equal;
   * the decoded boxes handed to the IoU kernel: within one fp32 rounding per operation;
@@ -25,6 +25,11 @@ of 1e-5 is 20x the former and 100x under the latter.
 
 CPU leg: the same cases through the host build of loss_core.h (tests/loss_host.cpp): proves the builder,
 its margins and the reference without a GPU.  GPU leg: the kernels.
+
+The gradient sizes and shapes of the arenas come from the binding's one table (_grad_layout); the float64
+reference's own shapes are asserted against them.  The semi-supervised node (both modes of the pass builder on
+one zero-filled gradient buffer) is compared with the two separate nodes on two of the shapes, on both legs:
+every output the same bits, every gradient element the same number.
 
 Largest errors seen on the MI355X against float64 (statistic: |err| / max(1, |ref|); gradient: |err| /
 max|ref|), over the supervised and consistency runs of each case:
@@ -102,21 +107,20 @@ class _Config:
         return self._mean_size.to(dev)
 
 
-def _grad_sizes(c):
-    B, K = c["B"], c["K"]
-    sizes = {"g_obj": B * K * 2, "g_center": B * K * 3, "g_h_scores": B * K * c["NH"], "g_h_resn": B * K * c["NH"],
-             "g_s_scores": B * K * c["NS"], "g_s_resn": B * K * c["NS"] * 3, "g_sem": B * K * c["NC"]}
-    if not c["consistency"]:
-        sizes.update(g_iou=B * K * c["NI"], g_iou_jit=B * K * c["NI"] if c["jitter"] else 0,
-                     g_vote=B * c["S"] * c["VF"] * 3)
-    return sizes
+def _layout(fused, c):
+    """the gradients of the case's mode from the binding's one table: name -> (floats per scene, floats, shape)"""
+    dims = {"K": c["K"], "NH": c["NH"], "NS": c["NS"], "NC": c["NC"], "NI": c["NI"], "S*VF": c["S"] * c["VF"],
+            "jitter": c["jitter"]}
+    layout = fused._grad_layout(dims, c["B"])
+    return {name: layout[name] for name in (("g_obj",) + fused._CONSISTENCY_GRADS if c["consistency"] else fused._GRADS)}
 
 
-def _grad_shapes(c):
-    B, K = c["B"], c["K"]
-    return {"g_obj": (B, K, 2), "g_center": (B, K, 3), "g_h_scores": (B, K, c["NH"]), "g_h_resn": (B, K, c["NH"]),
-            "g_s_scores": (B, K, c["NS"]), "g_s_resn": (B, K, c["NS"], 3), "g_sem": (B, K, c["NC"]),
-            "g_iou": (B, K, c["NI"]), "g_iou_jit": (B, K, c["NI"]), "g_vote": (B, c["S"] * c["VF"], 3)}
+def _grad_sizes(fused, c):
+    return {name: g.size for name, g in _layout(fused, c).items()}
+
+
+def _grad_shapes(fused, c):
+    return {name: g.shape for name, g in _layout(fused, c).items()}
 
 
 class Run:
@@ -133,7 +137,7 @@ def run_case(fused, dev, c, grad_scale, monkeypatch):
     f32, i32, i64 = torch.float32, torch.int32, torch.int64
     B, K, G = c["B"], c["K"], c["G"]
     rows = 2 * K if c["jitter"] else K
-    run.grads = Arena(dev, f32, _grad_sizes(c))
+    run.grads = Arena(dev, f32, _grad_sizes(fused, c))
     run.own = {}
     seen = {}
     real_launch = fused._launch
@@ -143,7 +147,7 @@ def run_case(fused, dev, c, grad_scale, monkeypatch):
         b = type(a).from_buffer_copy(a)
         if "f" not in run.own:
             sizes = dict(stats=fused.ST_COUNT, objectness_mask=B * K, partials=fused._scratch_floats(a, dev))
-            sizes.update(_grad_sizes(c))
+            sizes.update(_grad_sizes(fused, c))
             run.own.update(f=Arena(dev, f32, sizes), l=Arena(dev, i64, dict(objectness_label=B * K,
                                                                              object_assignment=B * K)),
                            i=Arena(dev, i32, dict(gt_nearest=B * G)),
@@ -169,23 +173,23 @@ def run_case(fused, dev, c, grad_scale, monkeypatch):
     dest = {name: run.grads.ptr(name) for name in run.grads.slots}
     heads = [t[k] for k in ("obj", "center", "h_scores", "h_resn", "s_scores", "s_resn", "sem")]
     if c["consistency"]:
-        labels = {"center": t["center_label"], "mask": t["box_label_mask"],
-                  "heading_class": t["heading_class_label"], "heading_residual": t["heading_residual_label"],
-                  "size_class": t["size_class_label"], "size_residual": t["size_residual_label"],
-                  "sem_cls": t["sem_cls_label"]}
-        stats, lab, mask, assign, _ = fused._consistency_pass(labels, cfg, t["agg_xyz"], *heads, grad_dest=dest,
-                                                               grad_scale=grad_scale)
-        assert seen["calls"] == ["votenet_loss_forward_backward"]
+        src = {"center": t["center_label"], "mask": t["box_label_mask"],
+               "heading_class": t["heading_class_label"], "heading_residual": t["heading_residual_label"],
+               "size_class": t["size_class_label"], "size_residual": t["size_residual_label"],
+               "sem_cls": t["sem_cls_label"], "aggregated_vote_xyz": t["agg_xyz"]}
+        calls = ["votenet_loss_forward_backward"]
     else:
-        ep = {k: t[k] for k in ("center_label", "box_label_mask", "heading_class_label", "heading_residual_label",
-                                "size_class_label", "size_residual_label", "sem_cls_label", "vote_label",
-                                "vote_label_mask", "seed_inds", "seed_xyz", "jitter_center", "jitter_size",
-                                "jitter_heading")}
-        ep["aggregated_vote_xyz"] = t["agg_xyz"]
-        stats, lab, mask, assign, pred_bbox, _ = fused._labeled_pass(
-            ep, cfg, B, *heads, t["iou"], t["iou_jit"] if c["jitter"] else None, t["vote_xyz"], grad_dest=dest,
-            grad_scale=grad_scale)
-        assert seen["calls"] == ["votenet_loss_decode", "votenet_loss_forward_backward"]
+        src = {k: t[k] for k in ("center_label", "box_label_mask", "heading_class_label", "heading_residual_label",
+                                 "size_class_label", "size_residual_label", "sem_cls_label", "vote_label",
+                                 "vote_label_mask", "seed_inds", "seed_xyz", "jitter_center", "jitter_size",
+                                 "jitter_heading")}
+        src["aggregated_vote_xyz"] = t["agg_xyz"]
+        heads += [t["iou"], t["iou_jit"] if c["jitter"] else None, t["vote_xyz"]]
+        calls = ["votenet_loss_decode", "votenet_loss_forward_backward"]
+    stats, lab, mask, assign, pred_bbox, _, _ = fused._loss_pass(c["consistency"], src, cfg, heads, grad_dest=dest,
+                                                                 grad_scale=grad_scale)
+    assert seen["calls"] == calls
+    if not c["consistency"]:
         assert torch.equal(pred_bbox, seen["boxes"][:, :K])
     if dev.type == "cuda":
         torch.cuda.synchronize()
@@ -195,7 +199,7 @@ def run_case(fused, dev, c, grad_scale, monkeypatch):
     for key in ("boxes", "gt_boxes"):
         if key in seen:
             run.out[key] = seen[key].cpu().numpy()
-    shapes = _grad_shapes(c)
+    shapes = _grad_shapes(fused, c)
     for name in run.grads.slots:
         run.out[name] = run.grads.get(name, shapes[name] if run.grads.slots[name][1] else None)
     return run
@@ -213,7 +217,7 @@ def _stat_names(fused, c):
 
 
 def check_case(fused, c, run, ref, what):
-    out, shapes = run.out, _grad_shapes(c)
+    out, shapes = run.out, _grad_shapes(fused, c)
     # ---- the guard words, and the binding's outputs against the test's own launch of the same arguments
     run.grads.check(what + " grad_dest")
     for key, arena in run.own.items():
@@ -351,6 +355,102 @@ def test_builder_layouts():
     assert tensors(build("second_block"), torch.device("cpu"))["sem"].is_contiguous()
 
 
+# ------------------------------------------------------------------ the semi-supervised node
+SEMI = [pytest.param("second_block", 2, id="second_block-2-labeled"),
+        pytest.param("one_lane_over", 1, id="one_lane_over-1-labeled")]
+SEMI_WEIGHT = 2.0  # train.py:333; a power of two: the in-kernel grad_scale and autograd's product round alike
+HEAD_KEYS = {"objectness_scores": "obj", "center": "center", "heading_scores": "h_scores",
+             "heading_residuals_normalized": "h_resn", "size_scores": "s_scores",
+             "size_residuals_normalized": "s_resn", "sem_cls_scores": "sem", "iou_scores": "iou",
+             "iou_scores_jitter": "iou_jit", "vote_xyz": "vote_xyz"}
+SUPERVISED_ONLY = ("iou_scores", "iou_scores_jitter", "vote_xyz", "objectness_scores")
+
+
+def _semi_end_points(c, t, ln):
+    """end_points of a semi-supervised step out of a supervised case: every scene's head outputs as leaf
+    tensors, the case's labels (the first ln scenes are the labeled ones), and as pseudo labels the case's own
+    labels of the remaining scenes"""
+    ep = {key: t[name].detach().requires_grad_(True) for key, name in HEAD_KEYS.items()}
+    ep.update({k: t[k] for k in ("center_label", "box_label_mask", "heading_class_label", "heading_residual_label",
+                                 "size_class_label", "size_residual_label", "sem_cls_label", "vote_label",
+                                 "vote_label_mask", "seed_inds", "seed_xyz", "jitter_center", "jitter_size",
+                                 "jitter_heading")})
+    ep["aggregated_vote_xyz"] = t["agg_xyz"]
+    for k in ("center_label", "box_label_mask", "heading_class_label", "heading_residual_label", "size_class_label",
+              "size_residual_label", "sem_cls_label"):
+        ep["unlabeled_" + k] = t[k][ln:].clone()
+    return ep
+
+
+def _bits(x):
+    x = x.detach().cpu().contiguous()
+    return x.view(torch.int32) if x.dtype == torch.float32 else x
+
+
+def semi_case(fused, dev, name, ln, monkeypatch):
+    """One gradient buffer for both losses (get_semi_loss_fused) against the two separate nodes
+    (get_labeled_loss_fused on the labeled scenes + SEMI_WEIGHT * get_pseudo_detection_loss_fused) on the same
+    inputs: (end_points, loss) of each, after backward, and the launches of the first."""
+    c = build(name)
+    assert c["jitter"] and 0 < ln < c["B"]
+    t = tensors(c, dev)
+    cfg = _Config(t["mean_size"])
+    calls = []
+    real_launch = fused._launch
+    monkeypatch.setattr(fused, "_launch", lambda n, a, d: (calls.append(n), real_launch(n, a, d)))
+    monkeypatch.setattr(fused, "_scene_iou", lambda boxes, gt_boxes: (t["iou_lab"][:ln], t["iou_assign"][:ln]))
+    one = _semi_end_points(c, t, ln)
+    loss_one, one = fused.get_semi_loss_fused(one, cfg, ln, SEMI_WEIGHT)
+    launched = list(calls)
+    loss_one.backward()
+    two = _semi_end_points(c, t, ln)
+    labeled, two = fused.get_labeled_loss_fused(two, cfg, slice(0, ln))
+    unlabeled, two = fused.get_pseudo_detection_loss_fused(two, ln, cfg)
+    loss_two = labeled + unlabeled * SEMI_WEIGHT
+    loss_two.backward()
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    return (one, loss_one), (two, loss_two), launched
+
+
+def check_semi(fused, name, ln, result):
+    (one, loss_one), (two, loss_two), launched = result
+    assert launched == ["votenet_loss_decode", "votenet_loss_forward_backward", "votenet_loss_forward_backward"]
+    assert torch.equal(_bits(loss_one), _bits(loss_two)) and torch.equal(_bits(one["loss"]), _bits(loss_one))
+    logged = list(fused._STAT_KEYS) + list(fused._JITTER_KEYS) + list(fused._CONSISTENCY_KEYS)
+    for key in logged + ["detection_loss", "unlabeled_detection_loss"]:
+        assert not one[key].requires_grad
+        assert torch.equal(_bits(one[key]), _bits(two[key])), (name, key, float(one[key]), float(two[key]))
+    for key in ("objectness_label", "objectness_mask", "object_assignment", "pred_bbox", "unlabeled_objectness_label",
+                "unlabeled_objectness_mask", "unlabeled_object_assignment", "unlabeled_center_label"):
+        assert one[key].shape == two[key].shape and torch.equal(_bits(one[key]), _bits(two[key])), (name, key)
+    assert one["objectness_label"].shape[0] == ln and one["pred_bbox"].shape[1] == one["center"].shape[1]
+    assert int(one["objectness_label"].sum()) + int(one["unlabeled_objectness_label"].sum()) > 0
+    for key in HEAD_KEYS:
+        got, want = one[key].grad.cpu(), two[key].grad.cpu()
+        assert got.shape == one[key].shape and bool(torch.isfinite(got).all()), (name, key)
+        one_class = key == "heading_scores" and got.shape[2] == 1  # (cross entropy over one class: no gradient)
+        # (equal as numbers: the kernels write -0.0 where a factor is negative, and autograd's sum of the two
+        # nodes' zero-padded slices turns that into +0.0; every other element has the same bits)
+        assert torch.equal(got, want), (name, key, float((got - want).abs().max()))
+        assert torch.equal(_bits(got)[got != 0], _bits(want)[want != 0]), (name, key)
+        if key in SUPERVISED_ONLY:
+            assert not got[ln:].any(), (name, key, "a gradient on the rows of an unlabeled scene")
+        elif not one_class:
+            assert got[ln:].any(), (name, key)  # (the consistency rows are there)
+
+
+@pytest.mark.parametrize("name,ln", SEMI)
+def test_host_build_semi_node_equals_two_nodes(name, ln, host_build, monkeypatch):  # noqa: F811
+    """the semi-supervised node (both modes of the pass builder writing the rows of ONE zero-filled gradient
+    buffer per head output, the consistency rows scaled in the kernel) is bit-equal to the two separate nodes:
+    loss, every logged key, labels, pred_bbox, the gradient of every head output; the unlabeled rows of
+    iou_scores, iou_scores_jitter, vote_xyz and objectness_scores get exactly zero.  Shapes: a partial second
+    proposal block with contiguous head outputs, and two votes per seed with strided ones."""
+    fused = _fused(monkeypatch, host_build)
+    check_semi(fused, name, ln, semi_case(fused, torch.device("cpu"), name, ln, monkeypatch))
+
+
 # ------------------------------------------------------------------ GPU leg: the kernels
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,consistency", _cases())
@@ -391,3 +491,11 @@ def test_entry_points_reject_bad_arguments(monkeypatch):
     torch.cuda.synchronize()
     for key, arena in run.own.items():
         arena.check("rejected " + key, written=False)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,ln", SEMI)
+def test_kernels_semi_node_equals_two_nodes(name, ln, monkeypatch):
+    """as test_host_build_semi_node_equals_two_nodes, on the kernels (no atomics in them: the same bits)"""
+    fused = _fused(monkeypatch)
+    check_semi(fused, name, ln, semi_case(fused, torch.device("cuda:0"), name, ln, monkeypatch))

@@ -122,11 +122,12 @@ def test_semi_graph_replay_matches_eager(oracle_omp, monkeypatch):
 
 @pytest.mark.gpu
 def test_one_loss_node_for_both_losses(oracle_omp, monkeypatch):
-    """fused_loss._FusedSemiLoss (the supervised loss on the labeled scenes and the consistency loss
-    on the unlabeled ones writing ONE gradient buffer per head output, the consistency rows
-    pre-scaled by the loss weight) == the two separate autograd nodes on slices of the head outputs:
-    same loss, same logged terms and labels, same parameter gradients (to the order of the fp32
-    atomics), from the same initial state and noise."""
+    """fused_loss.get_semi_loss_fused (_FusedSemiLoss: fused_loss._loss_pass in its supervised mode on the
+    labeled scenes and in its consistency mode on the unlabeled ones, writing ONE gradient buffer per head
+    output, the consistency rows pre-scaled by the loss weight) == the two separate autograd nodes on slices
+    of the head outputs: same loss, same logged terms and labels, same parameter gradients (to the order of
+    the fp32 atomics), from the same initial state and noise.  (The node alone, without a detector and
+    element for element: tests/test_loss_kernels.py::test_kernels_semi_node_equals_two_nodes.)"""
     V, dev = _setup(True, oracle_omp, monkeypatch)
     cfg = V.scannet_config()
     step_mod = importlib.import_module("3dioumatch_amd.votenet.step")
