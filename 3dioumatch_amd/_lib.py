@@ -159,6 +159,8 @@ _SIGNATURES = {
     "votenet_loss_decode": [_vp, _vp],
     "votenet_loss_forward_backward": [_vp, _vp],
     "votenet_loss_scratch_floats": [_vp],
+    "votenet_eval_loss_decode": [_vp, _vp],
+    "votenet_eval_loss": [_vp, _vp, _vp, _vp],
     "votenet_bbox_jitter": [_c_int, _c_int, _c_int, _c_int] + [_vp] * 15,
     "votenet_gridconv_points": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "votenet_iou_opt_box_step": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _vp,

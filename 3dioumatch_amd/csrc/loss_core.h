@@ -425,3 +425,178 @@ LOSS_HD void vote_grad(const LossArgs &a, int b, int s, int arg, float mask, con
       a.g_vote[((long long)b * a.S * a.VF + s * a.VF + j) * 3 + c] = v;
     }
 }
+
+// ---- the test-time criterion: models/loss_helper.py get_loss :222-291 ------------------------------
+// What evaluate_one_epoch / evaluate_with_opt (train.py:378-530) run per batch next to the AP: the
+// same terms as above, forward only, with five differences (loss_helper.py against
+// loss_helper_labeled.py): the objectness labels come from the RAW centre labels (:86-92, empty slots
+// stay where the loaders put them and tie exactly: first index), cls_acc is over all B*K proposals
+// (:188-189) with cls_acc_obj next to it (:190-192), the IoU channel is the PREDICTED class (:208-210),
+// iou_loss is averaged over the positives (:216-218), and there is no jitter term.  No gradient is
+// stored and no g_* pointer of LossArgs is read.
+//
+// The partial sums use the rows of ACC_* above; two slots change meaning: ACC_CLSACC is the unmasked
+// match count, ACC_IOUHUB the huber sum over positives, and the match count over positives takes the
+// slot of the absent jitter term.
+enum { EV_ACC_CLSACC_OBJ = ACC_JITACC };
+
+enum {
+  EV_LOSS = VN_EV_LOSS, EV_VOTE = VN_EV_VOTE, EV_OBJ = VN_EV_OBJ, EV_CENTER = VN_EV_CENTER,
+  EV_HCLS = VN_EV_HCLS, EV_HREG = VN_EV_HREG, EV_SCLS = VN_EV_SCLS, EV_SREG = VN_EV_SREG,
+  EV_SEM = VN_EV_SEM, EV_BOX = VN_EV_BOX, EV_IOU = VN_EV_IOU, EV_POS_RATIO = VN_EV_POS_RATIO,
+  EV_NEG_RATIO = VN_EV_NEG_RATIO, EV_OBJ_ACC = VN_EV_OBJ_ACC, EV_CLS_ACC = VN_EV_CLS_ACC,
+  EV_CLS_ACC_OBJ = VN_EV_CLS_ACC_OBJ, EV_PRED_IOU = VN_EV_PRED_IOU,
+  EV_PRED_IOU_OBJ = VN_EV_PRED_IOU_OBJ, EV_IOU_ACC = VN_EV_IOU_ACC,
+  EV_IOU_ACC_OBJ = VN_EV_IOU_ACC_OBJ, EV_OBJ_COUNT = VN_EV_OBJ_COUNT, EV_COUNT = VN_EV_COUNT
+};
+
+// cross entropy of row (b,k) against `label` and the first arg-max class through *top: the forward
+// half of ce_and_grad
+LOSS_HD float ce_forward(const LossTensor &t, int b, int k, int n, int label, int *top) {
+  if (n <= kRowMax) {
+    ScoreRow r;
+    load_row(t, b, k, n, r);
+    const float lse = row_log_sum_exp(r);
+    float at_label = 0.0f, m = r.v[0];
+    int best = 0;
+#pragma unroll
+    for (int j = 0; j < kRowMax; ++j) {
+      if (j < n) {
+        if (j == label) at_label = r.v[j];
+        if (r.v[j] > m) { m = r.v[j]; best = j; }
+      }
+    }
+    *top = best;
+    return lse - at_label;
+  }
+  *top = arg_max(t, b, k, n);
+  return log_sum_exp(t, b, k, n) - lt_at(t, b, k, label);
+}
+
+// decoded prediction k of scene b as compute_iou_labels reads it at test time
+// (loss_helper_iou.py:64-88 on end_points['size_residuals'] / ['heading_residuals'], which
+// evaluate_with_opt rewrites, train.py:480-487): the size is mean + the UNNORMALISED residual, handed
+// over in LossArgs.jit_size as a (B,K,NS,3) view; heading as decode_prediction
+LOSS_HD void eval_decode_prediction(const LossArgs &a, int b, int k) {
+  float *o = a.boxes + ((long long)b * a.K + k) * 7;
+  const int hc = row_arg_max(a.h_scores, b, k, a.NH);
+  const int sc = row_arg_max(a.s_scores, b, k, a.NS);
+  const float h_res = lt_at(a.h_resn, b, k, hc) * (float)(M_PI / (double)a.NH);
+  for (int d = 0; d < 3; ++d) {
+    o[d] = lt_at(a.center, b, k, d);
+    float s = a.mean_size[sc * 3 + d] + lt_at(a.jit_size, b, k, sc, d);
+    if (s <= 0.0f) s = 1e-6f;
+    o[3 + d] = s;
+  }
+  o[6] = -class2angle(hc, h_res, a.NH);
+}
+
+// proposal k of scene b: labels and every per-proposal term into acc
+LOSS_HD void eval_proposal(const LossArgs &a, const SceneView &sv, int b, int k, float *acc) {
+  const long long bk = (long long)b * a.K + k;
+  const float vx = lt_at(a.agg_xyz, b, k, 0), vy = lt_at(a.agg_xyz, b, k, 1), vz = lt_at(a.agg_xyz, b, k, 2);
+  const float cx = lt_at(a.center, b, k, 0), cy = lt_at(a.center, b, k, 1), cz = lt_at(a.center, b, k, 2);
+  float best = 0.0f, best_c = 0.0f;
+  int assign = 0;
+  for (int g = 0; g < a.G; ++g) {  // both nearest-centre searches on the raw labels
+    const float gx = sv.gt_center[g * 3], gy = sv.gt_center[g * 3 + 1], gz = sv.gt_center[g * 3 + 2];
+    const float d = ((vx - gx) * (vx - gx) + (vy - gy) * (vy - gy)) + (vz - gz) * (vz - gz);
+    if (g == 0 || d < best) { best = d; assign = g; }
+    const float dc = ((cx - gx) * (cx - gx) + (cy - gy) * (cy - gy)) + (cz - gz) * (cz - gz);
+    if (g == 0 || dc < best_c) best_c = dc;
+  }
+  const float dist = sqrtf(best + 1e-6f);
+  const int label = dist < kNear ? 1 : 0;
+  const float mask = (dist < kNear || dist > kFar) ? 1.0f : 0.0f;
+  const float obj = (float)label;
+  a.objectness_label[bk] = label;
+  a.objectness_mask[bk] = mask;
+  a.object_assignment[bk] = assign;
+  acc[ACC_MASK] += mask;
+  acc[ACC_POS] += obj;
+  {
+    const float w = label ? 0.8f : 0.2f;
+    const float s0 = lt_at(a.obj, b, k, 0), s1 = lt_at(a.obj, b, k, 1);
+    const float m = s0 > s1 ? s0 : s1;
+    const float lse = m + logf(expf(s0 - m) + expf(s1 - m));
+    acc[ACC_CE_MASK] += w * (lse - (label ? s1 : s0)) * mask;
+    acc[ACC_OBJACC] += ((s1 > s0 ? 1 : 0) == label ? 1.0f : 0.0f) * mask;
+  }
+  acc[ACC_CENTER1] += best_c * obj;
+  const long long gi = (long long)b * a.G + assign;
+  int top;
+  {
+    const int hl = (int)a.heading_class_label[gi];
+    acc[ACC_HCLS] += obj * ce_forward(a.h_scores, b, k, a.NH, hl, &top);
+    const float target = a.heading_residual_label[gi] / (float)(M_PI / (double)a.NH);
+    acc[ACC_HREG] += obj * huber1(lt_at(a.h_resn, b, k, hl) - target);
+  }
+  {
+    const int sl = (int)a.size_class_label[gi];
+    acc[ACC_SCLS] += obj * ce_forward(a.s_scores, b, k, a.NS, sl, &top);
+    float reg = 0.0f;
+    for (int d = 0; d < 3; ++d)
+      reg += huber1(lt_at(a.s_resn, b, k, sl, d) - a.size_residual_label[gi * 3 + d] / a.mean_size[sl * 3 + d]);
+    acc[ACC_SREG] += obj * (reg / 3.0f);
+  }
+  {
+    const int cl = (int)a.sem_cls_label[gi];
+    acc[ACC_SEM] += obj * ce_forward(a.sem, b, k, a.NC, cl, &top);
+    const float match = top == cl ? 1.0f : 0.0f;
+    acc[ACC_CLSACC] += match;
+    acc[EV_ACC_CLSACC_OBJ] += match * obj;
+  }
+  {  // IoU estimation at the predicted class
+    const float lab = a.iou_lab[bk];
+    const float p = 1.0f / (1.0f + expf(-lt_at(a.iou, b, k, a.NI > 1 ? top : 0)));
+    const float x = p - lab;
+    acc[ACC_IOULAB] += lab;
+    acc[ACC_IOULAB_OBJ] += lab * obj;
+    acc[ACC_IOUACC] += fabsf(x);
+    acc[ACC_IOUACC_OBJ] += fabsf(x) * obj;
+    acc[ACC_IOUHUB] += huber1(x) * obj;
+  }
+}
+
+// GT slot g of scene b: loss_ground_truth without the arg-min the gradient needs
+LOSS_HD void eval_ground_truth(const LossArgs &a, const SceneView &sv, int g, float *acc) {
+  const float gx = sv.gt_center[g * 3], gy = sv.gt_center[g * 3 + 1], gz = sv.gt_center[g * 3 + 2];
+  float best = 0.0f;
+  for (int k = 0; k < a.K; ++k) {
+    const float cx = sv.center[k * 3], cy = sv.center[k * 3 + 1], cz = sv.center[k * 3 + 2];
+    const float d = ((cx - gx) * (cx - gx) + (cy - gy) * (cy - gy)) + (cz - gz) * (cz - gz);
+    if (k == 0 || d < best) best = d;
+  }
+  acc[ACC_BLM] += sv.gt_mask[g];
+  acc[ACC_DIST2] += best * sv.gt_mask[g];
+}
+
+// the 20 logged keys and the positive count from the global sums; accum (unless NULL) += them
+LOSS_HD void eval_stats(const LossArgs &a, const float *acc, float *st, float *accum) {
+  const float total = (float)(a.B * a.K);
+  const float cnt = acc[ACC_POS];
+  const float inv = 1.0f / (cnt + 1e-6f);
+  st[EV_VOTE] = acc[ACC_VDIST] / (acc[ACC_VMASK] + 1e-6f);
+  st[EV_OBJ] = acc[ACC_CE_MASK] / (acc[ACC_MASK] + 1e-6f);
+  st[EV_CENTER] = acc[ACC_CENTER1] * inv + acc[ACC_DIST2] / (acc[ACC_BLM] + 1e-6f);
+  st[EV_HCLS] = acc[ACC_HCLS] * inv;
+  st[EV_HREG] = acc[ACC_HREG] * inv;
+  st[EV_SCLS] = acc[ACC_SCLS] * inv;
+  st[EV_SREG] = acc[ACC_SREG] * inv;
+  st[EV_SEM] = acc[ACC_SEM] * inv;
+  st[EV_BOX] = 0.1f * st[EV_HCLS] + st[EV_HREG] + 0.1f * st[EV_SCLS] + st[EV_SREG] + st[EV_CENTER];
+  st[EV_IOU] = acc[ACC_IOUHUB] * inv;
+  st[EV_LOSS] = kLossWeight * (st[EV_VOTE] + 0.5f * st[EV_OBJ] + st[EV_BOX] + 0.1f * st[EV_SEM] + st[EV_IOU]);
+  st[EV_POS_RATIO] = cnt / total;
+  st[EV_NEG_RATIO] = acc[ACC_MASK] / total - st[EV_POS_RATIO];
+  st[EV_OBJ_ACC] = acc[ACC_OBJACC] / (acc[ACC_MASK] + 1e-6f);
+  st[EV_CLS_ACC] = acc[ACC_CLSACC] / total;
+  st[EV_CLS_ACC_OBJ] = acc[EV_ACC_CLSACC_OBJ] * inv;
+  st[EV_PRED_IOU] = acc[ACC_IOULAB] / total;
+  st[EV_PRED_IOU_OBJ] = acc[ACC_IOULAB_OBJ] * inv;
+  st[EV_IOU_ACC] = acc[ACC_IOUACC] / total;
+  st[EV_IOU_ACC_OBJ] = acc[ACC_IOUACC_OBJ] * inv;
+  st[EV_OBJ_COUNT] = cnt;
+  if (accum)
+    for (int i = 0; i < EV_COUNT; ++i) accum[i] += st[i];
+}

@@ -1,4 +1,5 @@
-// 3dioumatch_amd/csrc/votenet_loss.hip -- the supervised VoteNet-IoU loss as three launches (gfx950).
+// 3dioumatch_amd/csrc/votenet_loss.hip -- the supervised VoteNet-IoU loss as three launches, and the
+// test-time criterion as three more (gfx950).
 //
 // The arithmetic lives in loss_core.h (shared with the host test harness); this file is the
 // parallel schedule around it:
@@ -16,6 +17,12 @@
 //                                  partial rows (a few dozen), then normalises its gradient rows,
 //                                  folds in the GT -> nearest-centre term and writes the vote
 //                                  gradients; one lane writes the statistics.
+//
+//   votenet_eval_loss_decode       the same for the test-time criterion (sizes from the unnormalised
+//   votenet_eval_loss              residuals); eval_terms_kernel on the grid and roles of
+//                                  loss_terms_kernel, forward only: labels and partial rows, no gradient
+//                                  store; eval_stats_kernel, one workgroup: the rows in a fixed order,
+//                                  the statistics of models/loss_helper.py:222-291 and `accum += stats`.
 //
 // (A first version ran everything in ONE 1024-lane workgroup to get the global sums from a single
 // LDS reduction: 482 us, every runtime-bound loop paying a global-load latency per iteration on a
@@ -59,6 +66,43 @@ __device__ __forceinline__ void stage_ground_truth(const LossArgs &a, int b, flo
   for (int t = threadIdx.x; t < a.G; t += kLossBlock) gtm[t] = a.box_label_mask[(long long)b * a.G + t];
 }
 
+// one row of partial sums per workgroup: wave shuffle, then the four wave results through LDS
+__device__ __forceinline__ void write_partial_row(const float (&acc)[ACC_COUNT],
+                                                  float (&partial)[kLossBlock / kWave][ACC_COUNT], float *row) {
+  const int tid = threadIdx.x, lane = lane_id(), wave = tid / kWave;
+#pragma unroll
+  for (int i = 0; i < ACC_COUNT; ++i) {
+    float v = acc[i];
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+    if (lane == 0) partial[wave][i] = v;
+  }
+  __syncthreads();
+  if (tid < ACC_COUNT) {
+    float v = 0.0f;
+    for (int w = 0; w < kLossBlock / kWave; ++w) v += partial[w][tid];
+    row[tid] = v;
+  }
+}
+
+// the sum of every workgroup's partial row into total[ACC_COUNT], in an order that depends on the
+// shape only: lane (group, column) adds every 8th row, then the 8 shares (ends with the data
+// visible after the caller's next __syncthreads)
+__device__ __forceinline__ void sum_partial_rows(const LossArgs &a, int rows, float (&share)[kLossBlock / 32][32],
+                                                 float *total) {
+  const int tid = threadIdx.x, col = tid & 31, group = tid >> 5;
+  float v = 0.0f;
+  if (col < ACC_COUNT)
+    for (int row = group; row < rows; row += kLossBlock / 32)
+      v += a.partials[(long long)row * ACC_COUNT + col];
+  share[group][col] = v;
+  __syncthreads();
+  if (tid < ACC_COUNT) {
+    float t = 0.0f;
+    for (int g = 0; g < kLossBlock / 32; ++g) t += share[g][tid];
+    total[tid] = t;
+  }
+}
+
 __global__ void __launch_bounds__(kLossBlock) loss_terms_kernel(LossArgs a) {
   __shared__ float gtc[kMaxG * 3], gtm[kMaxG], ctr[kMaxK * 3];
   __shared__ float partial[kLossBlock / kWave][ACC_COUNT];
@@ -83,20 +127,7 @@ __global__ void __launch_bounds__(kLossBlock) loss_terms_kernel(LossArgs a) {
     float m;
     if (s < a.S) loss_seed(a, b, s, acc, &m);
   }
-  // one row of partial sums per workgroup: wave shuffle, then the four wave results through LDS
-  const int lane = lane_id(), wave = tid / kWave;
-#pragma unroll
-  for (int i = 0; i < ACC_COUNT; ++i) {
-    float v = acc[i];
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    if (lane == 0) partial[wave][i] = v;
-  }
-  __syncthreads();
-  if (tid < ACC_COUNT) {
-    float v = 0.0f;
-    for (int w = 0; w < kLossBlock / kWave; ++w) v += partial[w][tid];
-    a.partials[((long long)b * r.per_scene + role) * ACC_COUNT + tid] = v;
-  }
+  write_partial_row(acc, partial, a.partials + ((long long)b * r.per_scene + role) * ACC_COUNT);
 }
 
 __global__ void __launch_bounds__(kLossBlock) loss_finalize_kernel(LossArgs a) {
@@ -106,20 +137,7 @@ __global__ void __launch_bounds__(kLossBlock) loss_finalize_kernel(LossArgs a) {
   __shared__ float share[kLossBlock / 32][32];
   const Roles r = roles(a);
   const int role = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  {  // the global sums: lane (group, column) adds every 8th partial row, then the 8 shares
-    const int col = tid & 31, group = tid >> 5, rows = a.B * r.per_scene;
-    float v = 0.0f;
-    if (col < ACC_COUNT)
-      for (int row = group; row < rows; row += kLossBlock / 32)
-        v += a.partials[(long long)row * ACC_COUNT + col];
-    share[group][col] = v;
-    __syncthreads();
-    if (tid < ACC_COUNT) {
-      float t = 0.0f;
-      for (int g = 0; g < kLossBlock / 32; ++g) t += share[g][tid];
-      total[tid] = t;
-    }
-  }
+  sum_partial_rows(a, a.B * r.per_scene, share, total);
   if (role < r.proposal_blocks) {
     stage_ground_truth(a, b, gtc, gtm);
     for (int t = tid; t < a.G; t += kLossBlock) nearest[t] = a.gt_nearest[(long long)b * a.G + t];
@@ -143,6 +161,56 @@ __global__ void __launch_bounds__(kLossBlock) loss_finalize_kernel(LossArgs a) {
       vote_grad(a, b, s, arg, m, acc);
     }
   }
+}
+
+// ---- the test-time criterion (loss_core.h: eval_*), forward only --------------------------------------
+__global__ void __launch_bounds__(256) eval_decode_kernel(LossArgs a) {
+  const int item = blockIdx.x * blockDim.x + threadIdx.x;
+  const int props = a.B * a.K;
+  if (item < props) {
+    eval_decode_prediction(a, item / a.K, item % a.K);
+  } else if (item < props + a.B * a.G) {
+    const int t = item - props;
+    decode_ground_truth(a, t / a.G, t % a.G);
+  }
+}
+
+// the grid and the three roles of loss_terms_kernel; writes the labels and the partial row, nothing else
+__global__ void __launch_bounds__(kLossBlock) eval_terms_kernel(LossArgs a) {
+  __shared__ float gtc[kMaxG * 3], gtm[kMaxG], ctr[kMaxK * 3];
+  __shared__ float partial[kLossBlock / kWave][ACC_COUNT];
+  const Roles r = roles(a);
+  const int role = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  stage_ground_truth(a, b, gtc, gtm);
+  if (role == r.gt_block)
+    for (int t = tid; t < a.K * 3; t += kLossBlock) ctr[t] = lt_at(a.center, b, t / 3, t % 3);
+  __syncthreads();
+  SceneView sv;
+  sv.gt_center = gtc; sv.gt_mask = gtm; sv.center = ctr; sv.nearest = nullptr;
+  float acc[ACC_COUNT];
+#pragma unroll
+  for (int i = 0; i < ACC_COUNT; ++i) acc[i] = 0.0f;
+  if (role < r.proposal_blocks) {
+    const int k = role * kLossBlock + tid;
+    if (k < a.K) eval_proposal(a, sv, b, k, acc);
+  } else if (role == r.gt_block) {
+    for (int g = tid; g < a.G; g += kLossBlock) eval_ground_truth(a, sv, g, acc);
+  } else {
+    const int s = (role - r.gt_block - 1) * kLossBlock + tid;
+    float m;
+    if (s < a.S) loss_seed(a, b, s, acc, &m);
+  }
+  write_partial_row(acc, partial, a.partials + ((long long)b * r.per_scene + role) * ACC_COUNT);
+}
+
+// one workgroup: the rows added in a fixed order, the statistics, and the epoch's running sums --
+// the only writer of `accum`, ordered by the stream, so the sums are the same bits every time
+__global__ void __launch_bounds__(kLossBlock) eval_stats_kernel(LossArgs a, float *stats, float *accum) {
+  __shared__ float total[ACC_COUNT];
+  __shared__ float share[kLossBlock / 32][32];
+  sum_partial_rows(a, a.B * roles(a).per_scene, share, total);
+  __syncthreads();
+  if (threadIdx.x == 0) eval_stats(a, total, stats, accum);
 }
 
 bool valid(const VnLossArgs *a) {
@@ -175,6 +243,32 @@ int votenet_loss_forward_backward(const VnLossArgs *args, void *stream) {
   const dim3 grid(loss_blocks_per_scene(args->K, args->S), args->B);
   hipLaunchKernelGGL(loss_terms_kernel, grid, dim3(kLossBlock), 0, (hipStream_t)stream, *args);
   hipLaunchKernelGGL(loss_finalize_kernel, grid, dim3(kLossBlock), 0, (hipStream_t)stream, *args);
+  return (int)hipGetLastError();
+}
+
+namespace {
+bool eval_valid(const VnLossArgs *a) {
+  if (!a) return false;
+  VnLossArgs plain = *a;
+  plain.consistency = 0;
+  return valid(&plain);
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("default")))
+int votenet_eval_loss_decode(const VnLossArgs *args, void *stream) {
+  if (!eval_valid(args)) return (int)hipErrorInvalidValue;
+  const int items = args->B * (args->K + args->G);
+  hipLaunchKernelGGL(eval_decode_kernel, dim3((items + 255) / 256), dim3(256), 0, (hipStream_t)stream, *args);
+  return (int)hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("default")))
+int votenet_eval_loss(const VnLossArgs *args, float *stats, float *accum, void *stream) {
+  if (!eval_valid(args) || !args->partials || !stats) return (int)hipErrorInvalidValue;
+  const dim3 grid(loss_blocks_per_scene(args->K, args->S), args->B);
+  hipLaunchKernelGGL(eval_terms_kernel, grid, dim3(kLossBlock), 0, (hipStream_t)stream, *args);
+  hipLaunchKernelGGL(eval_stats_kernel, dim3(1), dim3(kLossBlock), 0, (hipStream_t)stream, *args, stats, accum);
   return (int)hipGetLastError();
 }
 

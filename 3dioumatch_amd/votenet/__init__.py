@@ -5,10 +5,10 @@ from .backbone import Pointnet2Backbone  # noqa: F401
 from .config import DatasetConfig, scannet_config, sunrgbd_config  # noqa: F401
 from .detector import VoteNet  # noqa: F401
 from .heads import GridConv, ProposalModule, VotingModule  # noqa: F401
-from .losses import get_labeled_loss  # noqa: F401
+from .losses import get_labeled_loss, get_loss  # noqa: F401
 from .data import make_batch, make_semi_batch  # noqa: F401
 from .step import (SemiSupervisedStep, SupervisedStep, update_ema_variables, lr_at,  # noqa: F401
                    bn_momentum_at)
-from .eval_helper import (APCalculator, DeviceAPCalculator, parse_groundtruths,  # noqa: F401
+from .eval_helper import (APCalculator, DeviceAPCalculator, EvalLossMeter, parse_groundtruths,  # noqa: F401
                           parse_groundtruths_device, parse_predictions, parse_predictions_device)
 from .eval_det import eval_det, eval_det_cls, voc_ap  # noqa: F401

@@ -381,3 +381,50 @@ class DeviceAPCalculator(object):
             ret_dict['AR'] = np.mean([last[key] for key in sorted(ap.keys())])
             ret.append(ret_dict)
         return ret
+
+
+class EvalLossMeter(object):
+    """The loss statistics of an evaluation epoch (train.py:395-414, :427): the sum over batches of each of
+    the 20 keys losses.get_loss fills, on the device, and the number of batches on the host.
+
+    step() runs the criterion on one batch's end_points (predictions and labels).  On the fused path the
+    statistics kernel adds the batch's values to the sums itself (votenet_eval_loss' accum); on the tensor
+    path one torch.stack is added to the same vector.  Neither reads a value on the host: nothing in step()
+    waits for the device.  result() makes ONE device->host copy and divides by the batch count -- a plain
+    mean of per-batch means, not weighted by batch size, as in the reference."""
+
+    def __init__(self, device):
+        from .fused_loss import EV_COUNT
+        self.device = torch.device(device)
+        self.accum = torch.zeros(EV_COUNT, dtype=torch.float32, device=self.device)
+        self.batches = 0
+
+    def step(self, end_points, dataset_config):
+        """(loss, end_points) of losses.get_loss on this batch, its statistics added to the sums."""
+        from . import fused_loss, losses
+        losses.check_eval_labels(end_points)
+        if 'iou_scores' not in end_points:
+            raise ValueError("EvalLossMeter.step: the end_points have no 'iou_scores' (iou_loss is one of the "
+                             "logged keys)")
+        dev = end_points['center'].device
+        if dev != self.accum.device:
+            raise ValueError("EvalLossMeter.step: end_points on %s, the meter on %s" % (dev, self.accum.device))
+        if fused_loss.eval_supported(end_points):
+            out = fused_loss.get_loss_fused(end_points, dataset_config, accum=self.accum)
+        else:
+            out = losses.get_loss(end_points, dataset_config)
+            values = [end_points[key].float() for key in losses.EVAL_STAT_KEYS]
+            values.append(end_points['objectness_label'].sum().float())
+            self.accum += torch.stack(values)
+        self.batches += 1
+        return out
+
+    def result(self):
+        """{key: epoch mean} of the 20 keys plus 'mean_loss' (= the mean detection_loss)."""
+        from .losses import EVAL_STAT_KEYS
+        if self.batches == 0:
+            raise ValueError("EvalLossMeter.result: no batch was evaluated")
+        host = self.accum.cpu().numpy().astype(np.float64) / self.batches
+        stats = {key: float(host[i]) for i, key in enumerate(EVAL_STAT_KEYS)}
+        stats['mean_loss'] = stats['detection_loss']
+        return stats

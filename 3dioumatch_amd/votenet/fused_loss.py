@@ -9,6 +9,9 @@ below just hands those buffers over, scaled by the incoming gradient of `loss`. 
 `get_pseudo_detection_loss_fused` is the same for the consistency loss on pseudo labels (the kernels'
 consistency mode), `get_semi_loss_fused` both losses of the semi-supervised step on one gradient buffer.
 
+`get_loss_fused` is the test-time criterion (losses.get_loss, models/loss_helper.py:222-291) on the eval kernels:
+forward only, four launches, and optionally the running sums of an epoch added on the device.
+
 Written once each: the differentiable inputs and their gradients (_HEADS, _grad_layout), the pass that
 fills VnLossArgs and launches (_loss_pass, both modes), the backward (_split_grads), the pseudo labels
 (_pseudo_labels), the end_points entries of each loss (_fill_supervised, _fill_unlabeled) and the
@@ -87,6 +90,7 @@ def enabled():
 
 
 _HOST_BUILD = None  # tests: ctypes handle of tests/loss_host.cpp (same arithmetic, host pointers)
+_EVAL_HOST_BUILD = None  # tests: the same of tests/eval_loss_host.cpp (the test-time criterion)
 
 
 def available(device):
@@ -185,16 +189,9 @@ _INPUTS = (("agg_xyz", 'aggregated_vote_xyz'), ("seed_xyz", 'seed_xyz'))
 _JITTER_INPUTS = (("jit_center", 'jitter_center'), ("jit_size", 'jitter_size'), ("jit_heading", 'jitter_heading'))
 
 
-def _loss_pass(consistency, src, config, heads, grad_dest=None, grad_scale=1.0):
-    """The launches of one mode over the scenes of `heads`.
-
-    supervised: decode -> scene IoU -> forward_backward; `src` is end_points (_LABELS, seed_inds, _INPUTS,
-    _JITTER_INPUTS; their first scenes are read), `heads` the ten tensors of _HEADS cut to the labeled scenes
-    (iou_scores_jitter None: no jitter).  consistency: forward_backward alone with S = VF = N = 0, NI = 1;
-    `src` holds the pseudo labels and 'aggregated_vote_xyz', `heads` the first seven tensors.
-    grad_dest: {gradient field: device address} to write the gradient rows somewhere the caller owns (a buffer
-    both modes share); None: a buffer of its own.  Returns (stats, objectness_label, objectness_mask,
-    object_assignment, pred_bbox or None, that buffer or None, its _grad_layout)."""
+def _fill_args(consistency, src, config, heads, grad_scale=1.0):
+    """VnLossArgs with the sizes, labels and predictions of one pass filled in (see _loss_pass for `src` and
+    `heads`) -> (args, tensors the struct points into, ptr() to add more, _dims, device)."""
     preds = dict(zip(_FIELDS, heads))
     center, has_jitter = preds["center"], preds.get("iou_jit") is not None
     dev, (nb, k) = center.device, center.shape[:2]
@@ -236,7 +233,21 @@ def _loss_pass(consistency, src, config, heads, grad_dest=None, grad_scale=1.0):
             raise RuntimeError("%s must be a float32 tensor on %s" % (name, dev))
         keep.append(t)
         setattr(a, name, _view(t))
+    return a, keep, ptr, dims, dev
 
+
+def _loss_pass(consistency, src, config, heads, grad_dest=None, grad_scale=1.0):
+    """The launches of one mode over the scenes of `heads`.
+
+    supervised: decode -> scene IoU -> forward_backward; `src` is end_points (_LABELS, seed_inds, _INPUTS,
+    _JITTER_INPUTS; their first scenes are read), `heads` the ten tensors of _HEADS cut to the labeled scenes
+    (iou_scores_jitter None: no jitter).  consistency: forward_backward alone with S = VF = N = 0, NI = 1;
+    `src` holds the pseudo labels and 'aggregated_vote_xyz', `heads` the first seven tensors.
+    grad_dest: {gradient field: device address} to write the gradient rows somewhere the caller owns (a buffer
+    both modes share); None: a buffer of its own.  Returns (stats, objectness_label, objectness_mask,
+    object_assignment, pred_bbox or None, that buffer or None, its _grad_layout)."""
+    a, keep, ptr, dims, dev = _fill_args(consistency, src, config, heads, grad_scale)
+    nb, k, has_jitter = a.B, a.K, bool(a.has_jitter)
     f32 = dict(dtype=torch.float32, device=dev)
     pred_bbox = None
     if not consistency:
@@ -447,3 +458,83 @@ def get_semi_loss_fused(end_points, config, labeled_num, weight):
     _fill_unlabeled(end_points, stats_u, lab_u, mask_u, assign_u)
     end_points['loss'] = total
     return total, end_points
+
+
+# ---- the test-time criterion ----------------------------------------------------------------------------
+EV_COUNT = 21  # include/loss_hip.h VN_EV_COUNT: losses.EVAL_STAT_KEYS in order, then the positive count
+EV_LOSS, EV_OBJ_COUNT = 0, 20
+
+
+def eval_supported(end_points):
+    """the eval kernels may run: the gate of get_labeled_loss (VOTENET_FUSED_LOSS, an IoU head, (B,K,C) head
+    outputs) on the GPU (tests: the host build)"""
+    on_device = end_points['center'].device.type == "cuda" or _EVAL_HOST_BUILD is not None
+    return enabled() and supported(end_points, None) and on_device
+
+
+def _launch_eval(name, a, device, *more):
+    """votenet_eval_loss_decode(args) / votenet_eval_loss(args, stats, accum) on the current stream (tests:
+    the host build's host_eval_loss*)"""
+    more = [None if t is None else ctypes.c_void_p(t.data_ptr()) for t in more]
+    if device.type != "cuda":
+        if _EVAL_HOST_BUILD is None:
+            raise RuntimeError("the fused loss runs on the GPU only (no CPU path)")
+        rc = getattr(_EVAL_HOST_BUILD, name.replace("votenet_", "host_"))(ctypes.byref(a), *more)
+        assert rc == 0
+        return
+    _L = importlib.import_module("3dioumatch_amd._lib")
+    with torch.cuda.device(device):
+        _L.check(getattr(_L.lib, name)(ctypes.byref(a), *more, _L.current_stream_ptr(device)), name)
+
+
+def _eval_pass(src, config, heads, size_residuals, accum=None):
+    """decode -> scene IoU -> terms -> statistics of the test-time criterion over every scene of `heads` (the
+    tensors of _HEADS, iou_scores_jitter None); `src` as in _loss_pass, `size_residuals` (B,K,NS,3) the
+    unnormalised residuals the boxes are decoded from.  accum: EV_COUNT floats the statistics are added to.
+    Returns (stats, objectness_label, objectness_mask, object_assignment, iou_labels, pred_bbox)."""
+    a, keep, ptr, dims, dev = _fill_args(False, src, config, heads)
+    nb, k = a.B, a.K
+    if size_residuals.dtype != torch.float32 or size_residuals.device != dev:
+        raise RuntimeError("size_residuals must be a float32 tensor on %s" % (dev,))
+    keep.append(size_residuals)
+    a.jit_size = _view(size_residuals)
+    if accum is not None and (accum.dtype != torch.float32 or accum.device != dev or accum.numel() != EV_COUNT
+                              or not accum.is_contiguous()):
+        raise RuntimeError("accum must be %d contiguous float32 values on %s" % (EV_COUNT, dev))
+    f32 = dict(dtype=torch.float32, device=dev)
+    boxes, gt_boxes = torch.empty((nb, k, 7), **f32), torch.empty((nb, a.G, 7), **f32)
+    a.boxes, a.gt_boxes = ptr(boxes), ptr(gt_boxes)
+    _launch_eval("votenet_eval_loss_decode", a, dev)
+    iou_lab, _ = _scene_iou(boxes, gt_boxes)
+    a.iou_lab = ptr(iou_lab)
+    out = {"objectness_label": torch.empty((nb, k), dtype=torch.int64, device=dev),
+           "objectness_mask": torch.empty((nb, k), **f32),
+           "object_assignment": torch.empty((nb, k), dtype=torch.int64, device=dev)}
+    for name, t in out.items():
+        setattr(a, name, ptr(t))
+    scratch = (_scratch_floats(a, dev) if dev.type == "cuda" or _EVAL_HOST_BUILD is None
+               else int(_EVAL_HOST_BUILD.host_eval_loss_scratch_floats(ctypes.byref(a))))
+    a.partials = ptr(torch.empty(max(1, scratch), **f32))
+    stats = torch.empty(EV_COUNT, **f32)
+    _launch_eval("votenet_eval_loss", a, dev, stats, accum)
+    return stats, out["objectness_label"], out["objectness_mask"], out["object_assignment"], iou_lab, boxes
+
+
+@torch.no_grad()
+def get_loss_fused(end_points, dataset_config, accum=None):
+    """Same contract as losses.get_loss: the 20 keys of losses.EVAL_STAT_KEYS as views of one statistics vector,
+    'loss', the objectness labels / mask / assignment, 'iou_labels' and 'pred_bbox'.  accum: a device vector of
+    EV_COUNT floats the kernel adds this batch's statistics to (votenet_eval_loss), no host round trip."""
+    from .losses import EVAL_STAT_KEYS
+    heads = [end_points[key].detach() if key != 'iou_scores_jitter' else None for _, _, key, _ in _HEADS]
+    stats, label, mask, assignment, iou_labels, pred_bbox = _eval_pass(
+        end_points, dataset_config, heads, end_points['size_residuals'].detach(), accum)
+    for i, key in enumerate(EVAL_STAT_KEYS):
+        end_points[key] = stats[i]
+    end_points['objectness_label'] = label
+    end_points['objectness_mask'] = mask
+    end_points['object_assignment'] = assignment
+    end_points['iou_labels'] = iou_labels
+    end_points['pred_bbox'] = pred_bbox
+    end_points['loss'] = end_points['detection_loss']
+    return end_points['loss'], end_points

@@ -158,16 +158,19 @@ class InferenceEngine(object):
 
 
 def evaluate(engine, batches, config_dict, opt_step=0, opt_rate=5e-4, ap_iou_thresholds=(0.25, 0.5),
-             device_ap=False):
+             device_ap=False, with_loss=False):
     """iou_opt.evaluate(engine.detector, batches, ...) with the engine's forward: for every batch (a dict
     with 'point_clouds' and the labels parse_groundtruths reads) the engine's end_points, for
     opt_step > 0 the IoU optimisation of the boxes (iou_opt.optimize_boxes), parse_predictions /
     parse_groundtruths and one APCalculator per threshold.  Returns the compute_metrics() dicts.
     device_ap: the device forms of the two parsers and one DeviceAPCalculator for all thresholds
     instead -- labels on the host are moved with non-blocking copies and nothing in the loop waits
-    for the GPU, so the next batch's index chain really runs beside this one's forward."""
-    from .eval_helper import (APCalculator, DeviceAPCalculator, parse_groundtruths, parse_groundtruths_device,
-                              parse_predictions, parse_predictions_device)
+    for the GPU, so the next batch's index chain really runs beside this one's forward.
+    with_loss: also the test-time criterion on every batch (losses.get_loss after the box optimisation, as
+    train.py:486-502 orders them; the batch then needs losses.EVAL_LABEL_KEYS) through one EvalLossMeter,
+    which never reads the device inside the loop; returns (metrics, the meter's result())."""
+    from .eval_helper import (APCalculator, DeviceAPCalculator, EvalLossMeter, parse_groundtruths,
+                              parse_groundtruths_device, parse_predictions, parse_predictions_device)
     from .iou_opt import _check_detector, optimize_boxes
     detector = engine.detector
     if detector.training:
@@ -180,15 +183,18 @@ def evaluate(engine, batches, config_dict, opt_step=0, opt_rate=5e-4, ap_iou_thr
         calc = DeviceAPCalculator(ap_iou_thresholds, class2type)
     else:
         calcs = [APCalculator(t, class2type) for t in ap_iou_thresholds]
+    meter = EvalLossMeter(engine.device) if with_loss else None
     for batch, end_points in zip(batches, engine.run(b['point_clouds'] for b in batches)):
         if opt_step > 0:
             end_points = optimize_boxes(detector, end_points, opt_rate, opt_step)
         for key in batch:
             if key not in end_points:
                 value = batch[key]
-                if device_ap and torch.is_tensor(value):
+                if (device_ap or with_loss) and torch.is_tensor(value):
                     value = value.to(engine.device, non_blocking=True)
                 end_points[key] = value
+        if with_loss:
+            meter.step(end_points, config_dict['dataset_config'])
         if device_ap:
             calc.step(parse_predictions_device(end_points, config_dict),
                       parse_groundtruths_device(end_points, config_dict))
@@ -197,6 +203,5 @@ def evaluate(engine, batches, config_dict, opt_step=0, opt_rate=5e-4, ap_iou_thr
         gt = parse_groundtruths(end_points, config_dict)
         for calc in calcs:
             calc.step(pred, gt)
-    if device_ap:
-        return calc.compute_metrics()
-    return [calc.compute_metrics() for calc in calcs]
+    metrics = calc.compute_metrics() if device_ap else [calc.compute_metrics() for calc in calcs]
+    return (metrics, meter.result()) if with_loss else metrics

@@ -3,7 +3,7 @@
 Host-side mirror of the reference train.py:431-491 (evaluate_with_opt, run by run_eval_opt.sh):
 every predicted box climbs the gradient of its own IoU logit -- centre and half size move, the
 heading stays -- before the NMS of parse_predictions(use_iou_for_nms=True).  evaluate() is
-evaluate_one_epoch / evaluate_with_opt without the loss statistics and TensorBoard.
+evaluate_one_epoch / evaluate_with_opt without TensorBoard (the loss statistics with with_loss=True).
 
 Two engines compute the same ascent:
   * "autograd": the reference loop written literally, with forward_onlyiou_faster and the
@@ -239,16 +239,19 @@ def optimize_boxes(detector, end_points, opt_rate, opt_step=10, engine="auto"):
 
 
 def evaluate(detector, batches, config_dict, opt_step=0, opt_rate=5e-4, ap_iou_thresholds=(0.25, 0.5),
-             engine="auto", device_ap=False):
+             engine="auto", device_ap=False, with_loss=False):
     """evaluate_one_epoch (opt_step = 0) / evaluate_with_opt (opt_step > 0) of the reference
-    train.py:384-425 / :431-507, without the loss statistics: for every batch (a dict with
+    train.py:384-425 / :431-507: for every batch (a dict with
     'point_clouds' and the ground-truth labels parse_groundtruths reads) a no-grad forward, the
     IoU optimisation of the boxes, parse_predictions / parse_groundtruths and one APCalculator per
     threshold.  Returns the list of compute_metrics() dicts, one per threshold.
     device_ap: the device forms of the two parsers and one DeviceAPCalculator for all thresholds
-    instead (labels on the host are moved with non-blocking copies; no host round trip per batch)."""
-    from .eval_helper import (APCalculator, DeviceAPCalculator, parse_groundtruths, parse_groundtruths_device,
-                              parse_predictions, parse_predictions_device)
+    instead (labels on the host are moved with non-blocking copies; no host round trip per batch).
+    with_loss: also the loss statistics -- the test-time criterion on every batch (losses.get_loss after the box
+    optimisation, train.py:400 / :486-502; the batch then needs losses.EVAL_LABEL_KEYS) through one
+    EvalLossMeter; returns (metrics, the meter's result(): the epoch mean of each logged key and 'mean_loss')."""
+    from .eval_helper import (APCalculator, DeviceAPCalculator, EvalLossMeter, parse_groundtruths,
+                              parse_groundtruths_device, parse_predictions, parse_predictions_device)
     if detector.training:
         raise ValueError("evaluate: the detector must be in eval mode")
     if opt_step > 0:
@@ -258,6 +261,7 @@ def evaluate(detector, batches, config_dict, opt_step=0, opt_rate=5e-4, ap_iou_t
         calc = DeviceAPCalculator(ap_iou_thresholds, class2type)
     else:
         calcs = [APCalculator(t, class2type) for t in ap_iou_thresholds]
+    meter = EvalLossMeter(next(detector.parameters()).device) if with_loss else None
     for batch in batches:
         with torch.no_grad():
             end_points = detector({'point_clouds': batch['point_clouds']})
@@ -266,9 +270,11 @@ def evaluate(detector, batches, config_dict, opt_step=0, opt_rate=5e-4, ap_iou_t
         for key in batch:
             if key not in end_points:
                 value = batch[key]
-                if device_ap and torch.is_tensor(value):
+                if (device_ap or with_loss) and torch.is_tensor(value):
                     value = value.to(end_points['center'].device, non_blocking=True)
                 end_points[key] = value
+        if with_loss:
+            meter.step(end_points, config_dict['dataset_config'])
         if device_ap:
             calc.step(parse_predictions_device(end_points, config_dict),
                       parse_groundtruths_device(end_points, config_dict))
@@ -277,6 +283,5 @@ def evaluate(detector, batches, config_dict, opt_step=0, opt_rate=5e-4, ap_iou_t
         gt = parse_groundtruths(end_points, config_dict)
         for calc in calcs:
             calc.step(pred, gt)
-    if device_ap:
-        return calc.compute_metrics()
-    return [calc.compute_metrics() for calc in calcs]
+    metrics = calc.compute_metrics() if device_ap else [calc.compute_metrics() for calc in calcs]
+    return (metrics, meter.result()) if with_loss else metrics

@@ -340,3 +340,132 @@ def get_labeled_loss(end_points, dataset_config, config_dict=None):
     end_points['obj_acc'] = _masked_mean((obj_pred == objectness_label.long()).float(),
                                          objectness_mask)
     return loss, end_points
+
+
+# ---- the test-time criterion (models/loss_helper.py) ------------------------------------------------
+# the 20 keys evaluate_one_epoch / evaluate_with_opt average over an epoch (train.py:411-414), in the
+# order of the fused kernels' statistics vector (include/loss_hip.h VN_EV_*)
+EVAL_STAT_KEYS = ('detection_loss', 'vote_loss', 'objectness_loss', 'center_loss', 'heading_cls_loss',
+                  'heading_reg_loss', 'size_cls_loss', 'size_reg_loss', 'sem_cls_loss', 'box_loss',
+                  'iou_loss', 'pos_ratio', 'neg_ratio', 'obj_acc', 'cls_acc', 'cls_acc_obj',
+                  'pred_iou_value', 'pred_iou_obj_value', 'iou_acc', 'iou_acc_obj')
+# the label keys get_loss reads
+EVAL_LABEL_KEYS = ('center_label', 'box_label_mask', 'heading_class_label', 'heading_residual_label',
+                   'size_class_label', 'size_residual_label', 'sem_cls_label', 'vote_label',
+                   'vote_label_mask')
+
+
+def check_eval_labels(batch):
+    """ValueError naming the first label key of EVAL_LABEL_KEYS that `batch` lacks."""
+    for key in EVAL_LABEL_KEYS:
+        if key not in batch:
+            raise ValueError("get_loss: the batch has no %r (the test-time criterion reads %s)"
+                             % (key, ", ".join(EVAL_LABEL_KEYS)))
+
+
+@torch.no_grad()
+def get_loss(end_points, dataset_config):
+    """The criterion of the evaluation loops (models/loss_helper.py:get_loss :222-291; train.py:400,
+    :502): every scene is supervised, no jitter term, no gradient.  Same end_points keys in and out as
+    the reference: EVAL_STAT_KEYS, 'loss', the objectness labels / mask / assignment, 'iou_labels' and
+    'pred_bbox'.  Returns (loss, end_points).
+
+    Where it differs from get_labeled_loss: the objectness labels come from the RAW centre labels
+    (:86-92; empty slots keep their stored centre and tie exactly, the first index wins), cls_acc is
+    over all B*K proposals (:188-189) next to cls_acc_obj over the positives (:190-192), the IoU
+    channel is the predicted class (:208-210) and iou_loss is averaged over the positives (:216-218).
+    The boxes of the IoU labels are decoded from 'heading_residuals' / 'size_residuals' and 'center'
+    (:196-201), so after iou_opt.optimize_boxes the loss reads the optimised boxes (train.py:486-502).
+    On the GPU the whole criterion is four launches (fused_loss.get_loss_fused)."""
+    check_eval_labels(end_points)
+    from . import fused_loss
+    if fused_loss.eval_supported(end_points):
+        return fused_loss.get_loss_fused(end_points, dataset_config)
+
+    nh = dataset_config.num_heading_bin
+    end_points['vote_loss'] = compute_vote_loss(end_points, None)
+
+    # objectness: nearest RAW centre label, first index on ties (:86-111)
+    raw = end_points['center_label'][:, :, 0:3]
+    agg = end_points['aggregated_vote_xyz']
+    dist_all = torch.sum((agg.unsqueeze(2) - raw.unsqueeze(1)) ** 2, dim=-1)
+    assign = torch.argmin(dist_all, dim=2)
+    dist = torch.sqrt(torch.gather(dist_all, 2, assign.unsqueeze(-1)).squeeze(-1) + 1e-6)
+    label = (dist < NEAR_THRESHOLD).long()
+    mask = ((dist < NEAR_THRESHOLD) | (dist > FAR_THRESHOLD)).float()
+    scores = end_points['objectness_scores']
+    ce = F.cross_entropy(scores.transpose(2, 1), label, weight=_objectness_weights(scores.device),
+                         reduction='none')
+    end_points['objectness_loss'] = _masked_mean(ce, mask)
+    end_points['objectness_label'] = label
+    end_points['objectness_mask'] = mask
+    end_points['object_assignment'] = assign
+    total = float(label.shape[0] * label.shape[1])
+    obj = label.float()
+    count = torch.sum(obj)
+    end_points['pos_ratio'] = count / total
+    end_points['neg_ratio'] = torch.sum(mask) / total - end_points['pos_ratio']
+    end_points['obj_acc'] = _masked_mean((torch.argmax(scores, 2) == label).float(), mask)
+
+    def pick(key):
+        return torch.gather(end_points[key], 1, assign)
+
+    terms = {}  # per-proposal (B,K) quantities averaged over the positive proposals
+    terms['center1'], _, dist2, _ = nn_distance(end_points['center'], raw)
+    center_back = _masked_mean(dist2, end_points['box_label_mask'])
+    h_cls_label = pick('heading_class_label')
+    terms['heading_cls'] = F.cross_entropy(end_points['heading_scores'].transpose(2, 1), h_cls_label,
+                                           reduction='none')
+    h_res_pred = _select(end_points['heading_residuals_normalized'], h_cls_label)
+    terms['heading_reg'] = huber_loss(h_res_pred, delta=1.0,
+                                      target=pick('heading_residual_label') / (np.pi / nh))
+    s_cls_label = pick('size_class_label')
+    terms['size_cls'] = F.cross_entropy(end_points['size_scores'].transpose(2, 1), s_cls_label,
+                                        reduction='none')
+    s_res_label = torch.gather(end_points['size_residual_label'], 1, assign.unsqueeze(-1).expand(-1, -1, 3))
+    s_res_pred = _select(end_points['size_residuals_normalized'], s_cls_label)
+    mean_size_label = dataset_config.mean_size(s_res_pred.device)[s_cls_label]
+    terms['size_reg'] = torch.mean(huber_loss(s_res_pred, delta=1.0, target=s_res_label / mean_size_label), -1)
+    sem_label = pick('sem_cls_label')
+    sem_scores = end_points['sem_cls_scores']
+    sem_pred = sem_scores.argmax(dim=-1)
+    terms['sem_cls'] = F.cross_entropy(sem_scores.transpose(2, 1), sem_label, reduction='none')
+    terms['cls_acc_obj'] = (sem_label == sem_pred).float()
+    end_points['cls_acc'] = torch.sum(terms['cls_acc_obj']) / total
+
+    # IoU labels of the decoded boxes (:196-205), IoU estimation at the predicted class (:207-218)
+    iou_labels, _, _ = compute_iou_labels(
+        end_points, None, agg, end_points['center'], None, None, end_points['heading_scores'],
+        end_points['heading_residuals'], end_points['size_scores'], end_points['size_residuals'],
+        config_dict={'dataset_config': dataset_config}, with_objectness=False,
+        gt_bbox=_gt_boxes(end_points, None, dataset_config))
+    end_points['iou_labels'] = iou_labels
+    end_points['pred_iou_value'] = torch.sum(iou_labels) / total
+    terms['pred_iou_obj'] = iou_labels
+    if 'iou_scores' in end_points:
+        iou_pred = torch.sigmoid(end_points['iou_scores'])
+        iou_pred = _select(iou_pred, sem_pred) if iou_pred.shape[2] > 1 else iou_pred.squeeze(-1)
+        terms['iou_acc_obj'] = torch.abs(iou_pred - iou_labels)
+        end_points['iou_acc'] = torch.sum(terms['iou_acc_obj']) / total
+        terms['iou'] = huber_loss(iou_pred, delta=1.0, target=iou_labels)
+
+    names = list(terms)
+    means = torch.sum(torch.stack([terms[n] for n in names]) * obj, dim=(1, 2)) / (count + 1e-6)
+    mean = dict(zip(names, means.unbind(0)))
+    end_points['center_loss'] = mean['center1'] + center_back
+    for key, name in (('heading_cls_loss', 'heading_cls'), ('heading_reg_loss', 'heading_reg'),
+                      ('size_cls_loss', 'size_cls'), ('size_reg_loss', 'size_reg'), ('sem_cls_loss', 'sem_cls'),
+                      ('cls_acc_obj', 'cls_acc_obj'), ('pred_iou_obj_value', 'pred_iou_obj'),
+                      ('iou_acc_obj', 'iou_acc_obj'), ('iou_loss', 'iou')):
+        if name in mean:
+            end_points[key] = mean[name]
+    box_loss = 0.1 * end_points['heading_cls_loss'] + end_points['heading_reg_loss'] \
+        + 0.1 * end_points['size_cls_loss'] + end_points['size_reg_loss'] + end_points['center_loss']
+    end_points['box_loss'] = box_loss
+    loss = end_points['vote_loss'] + 0.5 * end_points['objectness_loss'] + box_loss + 0.1 * end_points['sem_cls_loss']
+    if 'iou_loss' in end_points:
+        loss = loss + end_points['iou_loss']
+    loss = loss * 10
+    end_points['detection_loss'] = loss
+    end_points['loss'] = loss
+    return loss, end_points

@@ -88,6 +88,36 @@ int votenet_loss_forward_backward(const VnLossArgs *args, void *stream);
  * means of models/loss_helper_labeled.py:70-74, :118-123 and :283-297 */
 int votenet_loss_scratch_floats(const VnLossArgs *args);
 
+/* indices into the statistics of votenet_eval_loss: the 20 keys the evaluation loops average
+ * (train.py:411-414) and the count of positive proposals */
+enum {
+  VN_EV_LOSS, VN_EV_VOTE, VN_EV_OBJ, VN_EV_CENTER, VN_EV_HCLS, VN_EV_HREG, VN_EV_SCLS, VN_EV_SREG,
+  VN_EV_SEM, VN_EV_BOX, VN_EV_IOU, VN_EV_POS_RATIO, VN_EV_NEG_RATIO, VN_EV_OBJ_ACC, VN_EV_CLS_ACC,
+  VN_EV_CLS_ACC_OBJ, VN_EV_PRED_IOU, VN_EV_PRED_IOU_OBJ, VN_EV_IOU_ACC, VN_EV_IOU_ACC_OBJ,
+  VN_EV_OBJ_COUNT, VN_EV_COUNT
+};
+
+/* replaces the box decoding of compute_iou_labels as the test-time criterion calls it
+ * (models/loss_helper.py:196-201 -> models/loss_helper_iou.py:64-88): as votenet_loss_decode with
+ * has_jitter = 0, but the predicted size is mean_size + end_points['size_residuals'], the tensor
+ * evaluate_with_opt rewrites after the box optimisation (train.py:480-487).  args->jit_size is that
+ * (B,K,NS,3) tensor; has_jitter, consistency and the g_* pointers are ignored. */
+int votenet_eval_loss_decode(const VnLossArgs *args, void *stream);
+
+/* replaces get_loss (models/loss_helper.py:222-291), the criterion of evaluate_one_epoch and
+ * evaluate_with_opt (train.py:378-530), after the IoU labels are known; forward only.  Two launches:
+ * the terms on the grid of votenet_loss_forward_backward (labels, one row of partial sums per
+ * workgroup, no gradient stores), then one workgroup that adds the rows in a fixed order and writes
+ * stats[VN_EV_COUNT]; with accum != NULL also accum[i] += stats[i] (one writer, stream-ordered: an
+ * epoch's sums without a host round trip, train.py:411-414).  Against the training criterion: the
+ * objectness labels use the RAW centre labels (:86-92), cls_acc is over all proposals (:188-192),
+ * the IoU channel is the predicted class (:208-210), iou_loss is over the positives (:216-218).
+ * Reads of args: the labels, predictions, iou_lab, the label outputs and partials
+ * (votenet_loss_scratch_floats(args) floats); has_jitter, consistency, grad_scale, stats,
+ * gt_nearest, iou_assign and the g_* pointers are ignored (may be NULL).  Limits: G <= 256,
+ * K <= 2048. */
+int votenet_eval_loss(const VnLossArgs *args, float *stats, float *accum, void *stream);
+
 /* replaces optimizer.step() of torch.optim.Adam(net.parameters(), lr, weight_decay)
  * (pretrain.py:186, :289; train.py:201, :339) on ONE flat parameter buffer, and -- with ema != NULL
  * -- the teacher update that follows it in the semi-supervised stage (train.py:232-236
