@@ -104,6 +104,7 @@ _SIGNATURES = {
     "mlp_eval_lin4_supported": [_c_int] * 6,
     "mlp_eval_lin4_pool": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mlp_eval_stored_supported": [_c_int] * 6,
+    "mlp_eval_stored_tiles_per_wave": [_c_int] * 4,
     "mlp_eval_stored_image_bytes": [_c_int],
     "mlp_eval_stored_prepare": [_c_int, _vp, _vp, _vp, _vp],
     "mlp_eval_stored_pool": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -446,6 +446,13 @@ int eval_cus() {
   return cus;
 }
 
+// tiles per wave of the STORED launch: two where the chip is covered anyway (fewer LDS image loads;
+// NS == 64 always, a group is two tiles), one otherwise
+int stored_tiles_per_wave(int b, int m, int ns) {
+  const long long total_tiles = (long long)b * m * ns / 32;
+  return (ns == 64 || total_tiles >= 4 * 2 * 2 * eval_cus()) ? 2 : 1;
+}
+
 template <typename Kern, typename Args>
 void eval_launch(Kern kern, int wgs, size_t lds_bytes, hipStream_t stream, const Args &args) {
   // once per kernel (by address: the instantiations share one pointer type); the engine runs its
@@ -499,6 +506,11 @@ MLP_API int mlp_eval_stored_supported(int b, int c_in, int c_mid, int c_out, int
   return stored_shape_ok(b, c_in, c_mid, c_out, m, ns) ? 1 : 0;
 }
 
+// tiles per wave (1 or 2) of mlp_eval_stored_pool's launch on this shape, 0 where it is unsupported
+MLP_API int mlp_eval_stored_tiles_per_wave(int b, int c_out, int m, int ns) {
+  return stored_shape_ok(b, 128, 128, c_out, m, ns) ? stored_tiles_per_wave(b, m, ns) : 0;
+}
+
 // bytes of the weight image mlp_eval_stored_prepare fills (c_out 128 / 256)
 MLP_API size_t mlp_eval_stored_image_bytes(int c_out) {
   return (c_out == 128 || c_out == 256) ? (size_t)(kStW1Bytes + st_w2_bytes(c_out)) : 0;
@@ -527,8 +539,7 @@ MLP_API int mlp_eval_stored_pool(int b, int c_out, int m, int ns, const float *y
   StoredArgs a = {};
   a.r = m * ns; a.tiles_per_cloud = a.r / 32;
   a.total_tiles = (int)((long long)b * a.tiles_per_cloud);
-  // two tiles per wave where the chip is covered anyway (fewer LDS image loads), one otherwise
-  a.tpw = (ns == 64 || a.total_tiles >= 4 * 2 * 2 * eval_cus()) ? 2 : 1;
+  a.tpw = stored_tiles_per_wave(b, m, ns);
   a.y0 = y0; a.wimg = (const char *)img;
   a.sc0 = sc0; a.sh0 = sh0; a.sc1 = sc1; a.sh1 = sh1; a.sc2 = sc2; a.sh2 = sh2; a.out = out;
   const int wgs = pn2_ceil_div(a.total_tiles, 4 * a.tpw);

@@ -935,6 +935,11 @@ def eval_stored_supported(b, c_in, c_mid, c_out, m, ns):
     return bool(_lib.mlp_eval_stored_supported(int(b), int(c_in), int(c_mid), int(c_out), int(m), int(ns)))
 
 
+def eval_stored_tiles_per_wave(b, c_out, m, ns):
+    """Tiles per wave (1 or 2) of eval_stored_pool's launch on a (b, 128, m, ns) input; 0: unsupported."""
+    return int(_lib.mlp_eval_stored_tiles_per_wave(int(b), int(c_out), int(m), int(ns)))
+
+
 def fold_bn(bn):
     """(scale, shift) of an eval-mode nn.BatchNorm: bn_coefficients(..., training=False), the same bits
     the plain eval path uses.  Reads the parameters and running buffers, writes none of them."""

@@ -418,6 +418,10 @@ int mlp_eval_lin4_pool(int b, int m, int ns, const float *x4, const void *img, c
  * y0 (b,128,m,ns) is given: 1 when covered (ns 16 / 32 / 64, m * ns % 32 == 0), else 0
  * (pytorch_utils.py:14-39) */
 int mlp_eval_stored_supported(int b, int c_in, int c_mid, int c_out, int m, int ns);
+/* tiles per wave (1 or 2) of mlp_eval_stored_pool's launch on this shape, 0 where
+ * mlp_eval_stored_supported says no: the launch decision, for the tests of its two branches
+ * (pytorch_utils.py:14-39) */
+int mlp_eval_stored_tiles_per_wave(int b, int c_out, int m, int ns);
 /* bytes of the weight image of mlp_eval_stored_prepare (nn.Conv2d weights, pytorch_utils.py:70-124) */
 size_t mlp_eval_stored_image_bytes(int c_out);
 /* w1 (128,128), w2 (c_out,128) -> img (16-byte aligned): fragment-ordered bf16 images, exact
