@@ -192,6 +192,7 @@ EXPORTS = tuple(_SIGNATURES)
 _LOADER_SIGNATURES = {
     "scene_batch_build": [_vp, _vp],
     "scene_sunrgbd_batch_build": [_vp, _vp],
+    "scene_sunrgbd_votes": [_vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp],
 }
 
 

@@ -16,7 +16,15 @@
 //                       rounded to float32 after each stage as the reference's float32 cloud is,
 //                       and on vote rows the gathered (mask, 3 votes) row carried through the same
 //                       flip, rotation and scale.  rot(p + v) - rot(p) is computed as rot(v): the
-//                       two differ by the float32 rounding of the rotated point only.
+//                       two differ by the float32 rounding of the rotated point only.  For a
+//                       store without vote rows (votes == NULL) the <true> instantiation computes
+//                       the row from the SOURCE point and the scene's boxes instead of loading it.
+// One launch for the whole store (scene_sunrgbd_votes), for inspection and export:
+//   sun_votes_kernel    (point chunks, grid-strided) x scenes: the (mask, 3 votes) row of every
+//                       stored point in the reference's layout.
+// The vote rule (sunrgbd/sunrgbd_data.py:232-257 with the hull of sunrgbd_utils.py:227-237, which
+// is the oriented box itself) is sun_vote_row, shared by the two kernels: the scene's boxes staged
+// once per workgroup in LDS (64 x 8 doubles), every test in float64, the slot picked by selects.
 // No atomics, no scratch tables: a slot's outputs depend on its own source row alone.
 #include "common.h"
 #include "scene_common.h"
@@ -132,14 +140,78 @@ struct SunColor {
   double bright[3], shift[3];
 };
 
+// one staged box of the vote rule: centre, |half sizes|, cos / sin of the heading
+struct SunBox {
+  double cx, cy, cz, hx, hy, hz, c, s;
+};
+
+// Stage the scene's first `nb` (<= SUN_MAX_OBJ) box rows; the caller synchronises.  The hull of a
+// box with a zero half size is flat: the reference's hull call raises and the object is skipped
+// (sunrgbd_data.py:258-259), so such a box gets negative half sizes, which no point satisfies.
+__device__ __forceinline__ void sun_stage_boxes(SunBox *s_box, const double *boxes, int scene, int nb,
+                                                int t) {
+  for (int k = t; k < nb; k += kBlock) {
+    const double *src = boxes + ((size_t)scene * SUN_MAX_OBJ + k) * SUN_BOX_COLS;
+    SunBox b;
+    b.cx = src[0]; b.cy = src[1]; b.cz = src[2];
+    b.hx = fabs(src[3]); b.hy = fabs(src[4]); b.hz = fabs(src[5]);
+    if (b.hx == 0.0 || b.hy == 0.0 || b.hz == 0.0) b.hx = b.hy = b.hz = -1.0;
+    b.c = cos(src[6]);
+    b.s = sin(src[6]);
+    s_box[k] = b;
+  }
+}
+
+// The vote row of one point in the stored packing (mask x1 | y1 z1 | x2 y2 | z2 x3 | y3 z3): the
+// first containing box in table order sets the mask and all three slots, the second slot 1, the
+// third and every later one slot 2 (point_vote_idx saturates at 2, so the LAST one stays there).
+// The loop keeps the three slots' BOX INDICES, chosen by selects on the hit count (never by
+// indexing a register array); the votes are formed once after it.  `nb` is uniform in the
+// workgroup and every lane reads the same LDS address inside the loop.
+__device__ __forceinline__ void sun_vote_row(const SunBox *s_box, int nb, float px, float py, float pz,
+                                             float2 (&w)[5]) {
+  const double x = (double)px, y = (double)py, z = (double)pz;
+  int k1 = 0, k2 = 0, k3 = 0, hits = 0;
+  for (int k = 0; k < nb; ++k) {
+    const SunBox b = s_box[k];
+    const double dx = x - b.cx, dy = y - b.cy, dz = z - b.cz;
+    const double lx = dx * b.c - dy * b.s;
+    const double ly = dx * b.s + dy * b.c;
+    const bool in = fabs(lx) <= b.hx && fabs(ly) <= b.hy && fabs(dz) <= b.hz;
+    k1 = in && hits == 0 ? k : k1;
+    k2 = in && hits <= 1 ? k : k2;
+    k3 = in && hits != 1 ? k : k3;
+    hits += in ? 1 : 0;
+  }
+  float v[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // constant indices only
+  if (hits) {  // centre - point, as the reference forms it
+    const int ks[3] = {k1, k2, k3};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const SunBox *b = s_box + ks[q];
+      v[q * 3 + 0] = (float)(b->cx - x);
+      v[q * 3 + 1] = (float)(b->cy - y);
+      v[q * 3 + 2] = (float)(b->cz - z);
+    }
+  }
+  w[0] = make_float2(hits ? 1.0f : 0.0f, v[0]);
+  w[1] = make_float2(v[1], v[2]);
+  w[2] = make_float2(v[3], v[4]);
+  w[3] = make_float2(v[5], v[6]);
+  w[4] = make_float2(v[7], v[8]);
+}
+
 __device__ __forceinline__ double sun_color_uniform(const SunBatchArgs &a, int row, int k) {
   if (a.u_color_in) return a.u_color_in[row * 6 + k];
   return (double)draw_key(a.seed, a.counter, (unsigned)row, SUN_DRAW_COLOR + k) * 0x1p-32;
 }
 
+// kFromBoxes: the store holds no vote rows (a.votes == NULL); they are computed from the boxes
+template <bool kFromBoxes>
 __global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a) {
   __shared__ SunAug s_aug;
   __shared__ SunColor s_col;
+  __shared__ SunBox s_box[kFromBoxes ? SUN_MAX_OBJ : 1];
   const int chunk = blockIdx.x, row = blockIdx.y, teacher = blockIdx.z, t = threadIdx.x;
   const int scene = a.scene[row];
   const int n = a.count[scene], N = a.N, C = a.C;
@@ -151,6 +223,13 @@ __global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a
   if (t < 3 && color) {
     s_col.bright[t] = 1.0 + 0.4 * sun_color_uniform(a, row, t) - 0.2;
     s_col.shift[t] = 0.1 * sun_color_uniform(a, row, 3 + t) - 0.05;
+  }
+  int nb = 0;
+  if constexpr (kFromBoxes) {
+    if (votes) {
+      nb = min(a.nbox[scene], SUN_MAX_OBJ);
+      sun_stage_boxes(s_box, a.boxes, scene, nb, t);
+    }
   }
   __syncthreads();
   SunAug g{};
@@ -177,9 +256,13 @@ __global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a
     for (int c = 0; c < 7; ++c) v[c] = c < C ? src[c] : 0.0f;
     float2 w[5];  // mask x1 | y1 z1 | x2 y2 | z2 x3 | y3 z3 (rows are 8-byte aligned)
     if (votes) {
-      const float2 *vs = reinterpret_cast<const float2 *>(vrow + (size_t)p * SUN_VOTE_COLS);
+      if constexpr (kFromBoxes) {
+        sun_vote_row(s_box, nb, v[0], v[1], v[2], w);
+      } else {
+        const float2 *vs = reinterpret_cast<const float2 *>(vrow + (size_t)p * SUN_VOTE_COLS);
 #pragma unroll
-      for (int q = 0; q < 5; ++q) w[q] = vs[q];
+        for (int q = 0; q < 5; ++q) w[q] = vs[q];
+      }
     }
     if (div256) {
       v[3] *= 0.00390625f;
@@ -245,6 +328,33 @@ __global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a
   }
 }
 
+constexpr int kVoteChunks = 32;  // grid.x of sun_votes_kernel: a 50k-point scan is 25 chunks
+
+__global__ void __launch_bounds__(kBlock) sun_votes_kernel(const float *cloud, int C,
+                                                           const long long *offset, const int *count,
+                                                           const double *boxes, const int *nbox,
+                                                           float *votes_out) {
+  __shared__ SunBox s_box[SUN_MAX_OBJ];
+  const int scene = blockIdx.y, t = threadIdx.x;
+  const int n = count[scene];
+  const int nb = min(nbox[scene], SUN_MAX_OBJ);
+  sun_stage_boxes(s_box, boxes, scene, nb, t);
+  __syncthreads();
+  const long long off = offset[scene];
+  for (long long base = (long long)blockIdx.x * kChunk; base < n; base += (long long)gridDim.x * kChunk) {
+    for (int k = 0; k < kPerThread; ++k) {
+      const long long j = base + k * kBlock + t;
+      if (j >= n) break;
+      const float *src = cloud + (size_t)(off + j) * C;
+      float2 w[5];
+      sun_vote_row(s_box, nb, src[0], src[1], src[2], w);
+      float2 *dst = reinterpret_cast<float2 *>(votes_out + (size_t)(off + j) * SUN_VOTE_COLS);
+#pragma unroll
+      for (int q = 0; q < 5; ++q) dst[q] = w[q];
+    }
+  }
+}
+
 bool valid(const SunBatchArgs *a) {
   if (!a || a->B < 1 || a->B > SUN_MAX_B || a->N < 1 || a->C < 3 || a->C > 7) return false;
   if (a->vote_rows < 0 || a->vote_rows > a->B || a->box_rows < 0 || a->box_rows > a->B) return false;
@@ -254,7 +364,8 @@ bool valid(const SunBatchArgs *a) {
   if (a->ema && !a->ema_point_clouds) return false;
   if (a->color_aug && a->C < 6) return false;
   if (a->u_point_in && a->u_point_stride < 1) return false;
-  if (a->vote_rows && (!a->votes || !a->vote_label || !a->vote_label_mask)) return false;
+  if (a->vote_rows && (!a->vote_label || !a->vote_label_mask)) return false;
+  if (a->vote_rows && !a->votes && (!a->boxes || !a->nbox)) return false;  // votes from the boxes
   if (a->box_rows && (!a->boxes || !a->nbox || !a->mean_size || !a->center_label ||
                       !a->heading_class_label || !a->heading_residual_label ||
                       !a->size_class_label || !a->size_residual_label || !a->sem_cls_label ||
@@ -271,7 +382,20 @@ PN2_API int scene_sunrgbd_batch_build(const SunBatchArgs *args, void *stream) {
   const hipStream_t s = (hipStream_t)stream;
   const SunBatchArgs &a = *args;
   hipLaunchKernelGGL(sun_boxes_kernel, dim3(a.B), dim3(SUN_MAX_OBJ), 0, s, a);
-  hipLaunchKernelGGL(sun_points_kernel, dim3(pn2_ceil_div(a.N, kChunk), a.B, a.ema ? 2 : 1),
-                     dim3(kBlock), 0, s, a);
+  const dim3 grid(pn2_ceil_div(a.N, kChunk), a.B, a.ema ? 2 : 1);
+  if (a.vote_rows && !a.votes)
+    hipLaunchKernelGGL(sun_points_kernel<true>, grid, dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL(sun_points_kernel<false>, grid, dim3(kBlock), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+PN2_API int scene_sunrgbd_votes(const float *cloud, int C, const long long *offset, const int *count,
+                                const double *boxes, const int *nbox, int scenes, float *votes_out,
+                                void *stream) {
+  if (!cloud || !offset || !count || !boxes || !nbox || !votes_out || C < 3 || scenes < 1 || scenes > 65535)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(sun_votes_kernel, dim3(kVoteChunks, scenes), dim3(kBlock), 0, (hipStream_t)stream,
+                     cloud, C, offset, count, boxes, nbox, votes_out);
   return (int)hipGetLastError();
 }

@@ -7,9 +7,15 @@ the WHOLE 50k-point scan before they sample it.  Here the preprocessed scans (`<
 read ONCE into flat device arrays (`SunRgbdScenes`), and a batch is two kernel launches
 (csrc/sunrgbd_batch.hip, include/sunrgbd_hip.h) on the train step's side stream (scannet_data.feed).
 
+The vote rows are a pure function of the cloud and the boxes (the vote loop of the reference's
+extraction, sunrgbd/sunrgbd_data.py:232-257).  `votes="boxes"` loads a folder that holds only
+`_pc.npz` and `_bbox.npy`: the store then keeps no vote rows and the batch builder computes them per
+sampled point (`compute_votes` is the numpy restatement; `SunRgbdScenes.vote_rows` and
+`export_votes` give the whole store's rows, the latter in the reference's file layout).
+
 What differs from the ScanNet loader: boxes are oriented (heading class / residual of 12 bins, size
-residuals from 2 x the stored half sizes), the vote labels are INPUT data carried through the
-augmentation, the labeled and the unlabeled dataset normalise colour differently (rgb - 0.5 and
+residuals from 2 x the stored half sizes), the vote labels are carried through the augmentation
+(read from `_votes.npz` by default, computed from the boxes with votes="boxes"), the labeled and the unlabeled dataset normalise colour differently (rgb - 0.5 and
 (rgb - 0.5) / 256: the store keeps the first, the second is applied per row at build time), and the
 detection dataset augments colour per point.  The draw hash, the sampler, epoch_plan, feed and
 eval_batches are scannet_data's.
@@ -40,13 +46,22 @@ _c_int, _c_uint, _vp = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p
 
 
 # ------------------------------------------------------------------ reading scans and splits
-def read_scene(data_dir, name, use_color=False, use_height=True):
+def _votes_mode(votes):
+    if votes not in ("file", "boxes"):
+        raise ValueError("votes must be 'file' or 'boxes', got %r" % (votes,))
+    return votes
+
+
+def read_scene(data_dir, name, use_color=False, use_height=True, votes="file"):
     """One preprocessed scan -> the per-scene state the batches are built from, computed once in the
     file's dtype as the reference does and then held in float32: cloud (n, C) = xyz, [rgb - 0.5],
     [z - floor]; the floor height (np.percentile(z, 0.99)); the vote rows (n, 10) float32; the box
-    table (K, 8) float64 = centre, half sizes, heading, class."""
-    paths = {"pc": os.path.join(data_dir, name + "_pc.npz"), "bbox": os.path.join(data_dir, name + "_bbox.npy"),
-             "votes": os.path.join(data_dir, name + "_votes.npz")}
+    table (K, 8) float64 = centre, half sizes, heading, class.  votes="boxes": `_votes.npz` is
+    neither required nor opened and the scene's "votes" is None (compute_votes gives the rows)."""
+    from_file = _votes_mode(votes) == "file"
+    paths = {"pc": os.path.join(data_dir, name + "_pc.npz"), "bbox": os.path.join(data_dir, name + "_bbox.npy")}
+    if from_file:
+        paths["votes"] = os.path.join(data_dir, name + "_votes.npz")
     for p in paths.values():
         if not os.path.exists(p):
             raise SceneError("scan %s: missing %s" % (name, p))
@@ -54,10 +69,12 @@ def read_scene(data_dir, name, use_color=False, use_height=True):
         if "pc" not in f.files:
             raise SceneError("scan %s: %s has no 'pc'" % (name, paths["pc"]))
         pc = f["pc"]
-    with np.load(paths["votes"]) as f:
-        if "point_votes" not in f.files:
-            raise SceneError("scan %s: %s has no 'point_votes'" % (name, paths["votes"]))
-        votes = f["point_votes"]
+    votes = None
+    if from_file:
+        with np.load(paths["votes"]) as f:
+            if "point_votes" not in f.files:
+                raise SceneError("scan %s: %s has no 'point_votes'" % (name, paths["votes"]))
+            votes = f["point_votes"]
     bbox = np.load(paths["bbox"])
     if pc.ndim != 2 or pc.shape[1] < (6 if use_color else 3):
         raise SceneError("scan %s: pc has shape %s, expected (n, %s)"
@@ -65,7 +82,7 @@ def read_scene(data_dir, name, use_color=False, use_height=True):
     n = pc.shape[0]
     if n == 0 or n >= 1 << 30:
         raise SceneError("scan %s: %d points" % (name, n))
-    if votes.ndim != 2 or votes.shape[0] != n or votes.shape[1] != VOTE_COLS:
+    if from_file and (votes.ndim != 2 or votes.shape[0] != n or votes.shape[1] != VOTE_COLS):
         raise SceneError("scan %s: %d points but point_votes has shape %s, expected (%d, %d)"
                          % (name, n, votes.shape, n, VOTE_COLS))
     if bbox.size == 0:
@@ -89,8 +106,40 @@ def read_scene(data_dir, name, use_color=False, use_height=True):
     if use_height:
         cloud = np.concatenate([cloud, np.expand_dims(cloud[:, 2] - floor, 1)], 1)
     return {"name": name, "cloud": np.ascontiguousarray(cloud, np.float32), "floor": float(floor),
-            "votes": np.ascontiguousarray(votes, np.float32), "boxes": np.array(bbox, np.float64),
-            "dtype": str(pc.dtype)}
+            "votes": np.ascontiguousarray(votes, np.float32) if from_file else None,
+            "boxes": np.array(bbox, np.float64), "dtype": str(pc.dtype)}
+
+
+def compute_votes(cloud_xyz, boxes):
+    """The vote rows (n, 10) float32 of the points `cloud_xyz` (n, >= 3; the store's float32 cloud)
+    from the box table `boxes` (K, 8), by the rule of the reference's extraction
+    (sunrgbd/sunrgbd_data.py:232-257; the hull of sunrgbd_utils.py:227-237 is the oriented box): in
+    float64, d = p - centre, lx = d.x cos t - d.y sin t, ly = d.x sin t + d.y cos t, inside iff
+    |lx| <= |l|, |ly| <= |w|, |d.z| <= |h|.  In table order the first containing box sets the mask
+    and all three votes to float32(centre - p), the second the second vote, the third and every later
+    one the third (the LAST containing box stays there).  A box with a zero half size contains nothing
+    (the reference's hull call raises on its flat corners and the object is skipped).  This is
+    csrc/sunrgbd_batch.hip:sun_vote_row."""
+    p = np.asarray(cloud_xyz)[:, 0:3].astype(np.float64)
+    boxes = np.asarray(boxes, np.float64).reshape(-1, 8)
+    rows = np.zeros((p.shape[0], VOTE_COLS), np.float32)
+    hits = np.zeros(p.shape[0], np.int64)
+    for k in range(boxes.shape[0]):
+        half = np.abs(boxes[k, 3:6])
+        if (half == 0).any():
+            continue
+        d = p - boxes[k, 0:3]
+        c, s = np.cos(boxes[k, 6]), np.sin(boxes[k, 6])
+        lx, ly = d[:, 0] * c - d[:, 1] * s, d[:, 0] * s + d[:, 1] * c
+        within = (np.abs(lx) <= half[0]) & (np.abs(ly) <= half[1]) & (np.abs(d[:, 2]) <= half[2])
+        v = (boxes[k, 0:3] - p).astype(np.float32)
+        first, second, later = within & (hits == 0), within & (hits == 1), within & (hits >= 2)
+        rows[first, 0] = 1.0
+        rows[first, 1:10] = np.tile(v[first], (1, 3))
+        rows[second, 4:7] = v[second]
+        rows[later, 7:10] = v[later]
+        hits += within
+    return rows
 
 
 def available_scans(data_dir):
@@ -130,14 +179,17 @@ class SunRgbdScenes(object):
     """Every scan of `scan_names` read once and packed into flat device arrays with a per-scene
     offset / count table: the cloud (P, C) float32, the vote rows (P, 10) float32, the box table
     (S, 64, 8) float64.  At 50k points a scene is 50k x (4 C + 40) bytes = 2.8 MB with the height
-    channel, 4 MB with colour too.  `device=None` keeps the host copy only (the CPU path)."""
+    channel, 4 MB with colour too.  votes="boxes": no `_votes.npz` is read and no vote rows are
+    kept (50k x 4 C bytes a scene: 0.8 MB, 1.4 MB with colour); the batch builder computes them from
+    the boxes.  `device=None` keeps the host copy only (the CPU path)."""
 
-    def __init__(self, data_dir, scan_names, device, use_color=False, use_height=True):
+    def __init__(self, data_dir, scan_names, device, use_color=False, use_height=True, votes="file"):
         if not scan_names:
             raise SceneError("no scans to load from %s" % data_dir)
+        self.votes = _votes_mode(votes)
         self.scan_names = list(scan_names)
         self.use_color, self.use_height = use_color, use_height
-        self.scenes = [read_scene(data_dir, s, use_color, use_height) for s in self.scan_names]
+        self.scenes = [read_scene(data_dir, s, use_color, use_height, votes) for s in self.scan_names]
         self.channels = self.scenes[0]["cloud"].shape[1]
         self.count = np.array([s["cloud"].shape[0] for s in self.scenes], np.int32)
         self.offset = np.concatenate([[0], np.cumsum(self.count, dtype=np.int64)[:-1]]).astype(np.int64)
@@ -152,10 +204,11 @@ class SunRgbdScenes(object):
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
             self.dev = {
                 "cloud": t(np.concatenate([s["cloud"] for s in self.scenes])),
-                "votes": t(np.concatenate([s["votes"] for s in self.scenes])),
                 "offset": t(self.offset), "count": t(self.count),
                 "boxes": t(self.boxes), "nbox": t(self.nbox),
             }
+            if self.votes == "file":
+                self.dev["votes"] = t(np.concatenate([s["votes"] for s in self.scenes]))
 
     def __len__(self):
         return len(self.scan_names)
@@ -163,6 +216,40 @@ class SunRgbdScenes(object):
     def index(self, names):
         where = {s: i for i, s in enumerate(self.scan_names)}
         return np.array([where[s] for s in names], np.int64)
+
+    def vote_rows(self):
+        """The (P, 10) float32 vote rows of the whole store on the device, in the reference's layout
+        (mask, three votes): the stored rows of a "file" store, one scene_sunrgbd_votes launch on the
+        current stream for a "boxes" store."""
+        if self.dev is None:
+            raise RuntimeError("SunRgbdScenes: the store has no device copy (device=None); use compute_votes")
+        if self.votes == "file":
+            return self.dev["votes"]
+        _L = importlib.import_module("3dioumatch_amd._lib")
+        d = self.dev
+        out = torch.empty((d["cloud"].shape[0], VOTE_COLS), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _L.check(_L.lib.scene_sunrgbd_votes(d["cloud"].data_ptr(), self.channels, d["offset"].data_ptr(),
+                                                d["count"].data_ptr(), d["boxes"].data_ptr(),
+                                                d["nbox"].data_ptr(), len(self.scenes), out.data_ptr(),
+                                                torch.cuda.current_stream(self.device).cuda_stream),
+                     "scene_sunrgbd_votes")
+        return out
+
+    def export_votes(self, out_dir):
+        """Write `<name>_votes.npz` with 'point_votes' (n, 10) float64 for every scan: the layout of
+        the reference's extraction (sunrgbd/sunrgbd_data.py:260-261), so that a folder prepared here
+        loads in the reference and as a "file" store.  The rows are vote_rows()'s (compute_votes'
+        for a store without a device copy)."""
+        if self.dev is not None:
+            rows = self.vote_rows().cpu().numpy()
+        else:
+            rows = np.concatenate([s["votes"] if s["votes"] is not None else
+                                   compute_votes(s["cloud"], s["boxes"]) for s in self.scenes])
+        os.makedirs(out_dir, exist_ok=True)
+        for name, off, n in zip(self.scan_names, self.offset, self.count):
+            np.savez_compressed(os.path.join(out_dir, name + "_votes.npz"),
+                                point_votes=rows[off:off + n].astype(np.float64))
 
 
 # ------------------------------------------------------------------ host restatement
@@ -195,7 +282,10 @@ def host_scene(scene, idx, u=None, votes=True, boxes="raw", mean_size=None, has_
         pc[:, 3:6] = pc[:, 3:6] / 256.0
     bb = scene["boxes"].copy()
     out = {}
-    pv = scene["votes"][idx].astype(np.float64) if votes else None
+    pv = None
+    if votes:  # a scene without vote rows: from the boxes (the rule is per point: only the sample)
+        pv = scene["votes"][idx] if scene["votes"] is not None else compute_votes(scene["cloud"][idx], bb)
+        pv = pv.astype(np.float64)
     if u is not None:
         fx, angle, scale = augmentation(u)
         aug_boxes = boxes == "aug"
@@ -429,8 +519,9 @@ class SunRgbdLoader(object):
         for r in range(B):
             a.scene[r], a.scan_idx[r], a.supervised[r] = int(scene[r]), int(scan_idx[r]), int(r < nl)
         d = self.scenes.dev
-        for k in ("cloud", "votes", "offset", "count", "boxes", "nbox"):
+        for k in ("cloud", "offset", "count", "boxes", "nbox"):
             setattr(a, k, d[k].data_ptr())
+        a.votes = d["votes"].data_ptr() if "votes" in d else None  # NULL: computed from the boxes
         a.mean_size = self._mean_dev.data_ptr()
         keep = []  # device memory this call allocates on the current stream and `stream` writes or reads
         for key, field in (("idx", "idx_in"), ("ema_idx", "ema_idx_in"), ("u", "u_in"),

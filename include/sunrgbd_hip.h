@@ -1,12 +1,16 @@
 /* sunrgbd_hip.h -- C ABI of the SUN RGB-D batch builder (csrc/sunrgbd_batch.hip).
  *
- * A batch is built from a RESIDENT scene store (every scan's cloud, its (n, 10) vote rows and its
- * oriented-box table packed once into device memory, votenet/sunrgbd_data.py:SunRgbdScenes) with
+ * A batch is built from a RESIDENT scene store (every scan's cloud, its oriented-box table and,
+ * optionally, its (n, 10) vote rows packed once into device memory,
+ * votenet/sunrgbd_data.py:SunRgbdScenes) with
  * the semantics of the reference's loaders (sunrgbd/sunrgbd_detection_dataset.py,
  * sunrgbd/sunrgbd_ssl_dataset.py): point sampling, flip-x / rotz(+-30 deg) / isotropic scale of the
  * student cloud, the per-point colour augmentation of the detection dataset, oriented-box labels
  * (heading through pi - theta, theta - rot_angle and angle2class; size residuals from 2 x the
- * half sizes), and the stored votes carried through the same flip, rotation and scale.  Every
+ * half sizes), and the votes carried through the same flip, rotation and scale.  The vote rows
+ * are either input data (the reference's extraction wrote them) or, when the store holds none,
+ * computed per sampled point from the boxes by the extraction's own rule
+ * (sunrgbd/sunrgbd_data.py:232-257); scene_sunrgbd_votes computes them for the whole store.  Every
  * random draw is the counter-based hash of scene_hip.h; per-point colour draws are keyed by the
  * SOURCE point index.  The struct travels by value; nothing is copied host -> device per batch.
  */
@@ -48,7 +52,7 @@ typedef struct SunBatchArgs {
   int supervised[SUN_MAX_B]; /* written to supervised_mask */
   /* the resident store (device pointers) */
   const float *cloud;          /* (P, C) */
-  const float *votes;          /* (P, SUN_VOTE_COLS) */
+  const float *votes;          /* (P, SUN_VOTE_COLS); NULL: computed from boxes / nbox */
   const long long *offset;     /* (S,) first point of each scene */
   const int *count;            /* (S,) points of each scene (>= 1) */
   const double *boxes;         /* (S, SUN_MAX_OBJ, SUN_BOX_COLS) */
@@ -83,6 +87,22 @@ typedef struct SunBatchArgs {
 /* Build one batch: two launches on `stream` (draws + box labels; sample + gather + augment +
  * votes).  `args` is a HOST struct of device pointers. */
 int scene_sunrgbd_batch_build(const SunBatchArgs *args, void *stream);
+
+/* The vote rows of a whole store from its boxes: sunrgbd/sunrgbd_data.py:232-257 (the vote loop of
+ * extract_sunrgbd_data(save_votes=True)) with the membership test of sunrgbd/sunrgbd_utils.py:215-237
+ * (the hull of my_compute_box_3d's corners, i.e. the oriented box).  For point p (float32) of scene
+ * s and its box rows k = 0 .. nbox[s]-1 in table order, in float64: d = p - centre, lx = d.x cos t -
+ * d.y sin t, ly = d.x sin t + d.y cos t; p is inside iff |lx| <= |l|, |ly| <= |w|, |d.z| <= |h|; a
+ * box with a zero half size contains nothing (its hull is flat: the extraction skips the object).
+ * The first containing box sets the mask and writes (float)(centre - p) to all three vote slots,
+ * the second to slot 1, the third and every later one to slot 2.  A point in no box gets ten zeros.
+ *   cloud (P, C) float32 with C >= 3; offset / count (scenes,): the rows of each scene; boxes
+ *   (scenes, SUN_MAX_OBJ, SUN_BOX_COLS) float64; votes_out (P, SUN_VOTE_COLS) float32.
+ * One launch on `stream`.  hipErrorInvalidValue, and nothing launched, for a NULL pointer, C < 3,
+ * scenes < 1 or scenes > 65535 (the grid's second dimension). */
+int scene_sunrgbd_votes(const float *cloud, int C, const long long *offset, const int *count,
+                        const double *boxes, const int *nbox, int scenes, float *votes_out,
+                        void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 """Measure the SUN RGB-D scene loader (votenet/sunrgbd_data.py, csrc/sunrgbd_batch.hip) on one GPU:
 
     python tools/sunrgbd_loader_bench.py [--scenes 24] [--steps 20] [--repeats 3] [--builds-only]
+                                         [--votes {file,boxes}] [--compare-votes]
 
 SUN RGB-D-sized synthetic scans (50k points, 12 oriented boxes, votes) are written in the on-disk
 layout into a temporary directory and loaded through the real reader.  Prints ONE JSON line:
@@ -16,6 +17,10 @@ layout into a temporary directory and loaded through the real reader.  Prints ON
                     device sets, one copy stream), the two alternated, --repeats each: median and
                     spread (max - min) of the repeats
   host_ms_per_scene the numpy restatement per scene on this host's CPU (one core), the comparison
+--votes boxes measures a store without vote rows (the builder computes them from the boxes; the vote
+files of the synthetic scans are then never opened).  --compare-votes holds BOTH stores in one
+process and alternates them: `votes_ab` = store_bytes, build_ms (median and spread of --repeats per
+store and batch kind) and, unless --builds-only, the supervised step fed by each store.
 Kernel times: `rocprofv3 --kernel-trace --stats -f csv -d DIR -o run -- python
 tools/sunrgbd_loader_bench.py --builds-only`.
 """
@@ -42,16 +47,45 @@ NPTS, B, LAB, UNL = 20000, 16, 4, 8
 PEAK_HBM = 8.0e12  # bytes / s, the MI355X's nominal HBM3E rate
 
 
-def batch_bytes(kind, channels):
-    """Bytes one batch must move: per student slot of a vote row a cloud row and a vote row read, a
-    cloud row, nine vote floats and an int64 mask written; other slots (unlabeled students, every
-    teacher slot) a cloud row read and written.  Box labels and draws are a few KB: left out."""
+def batch_bytes(kind, channels, votes="file"):
+    """Bytes one batch must move: per student slot of a vote row a cloud row and (a "file" store) a
+    vote row read, a cloud row, nine vote floats and an int64 mask written; other slots (unlabeled
+    students, every teacher slot) a cloud row read and written.  Box labels and draws are a few KB:
+    left out."""
     cloud = 4 * channels
     vote_rows, rows, copies = (B, B, 1) if kind == "pretrain" else (LAB, LAB + UNL, 2)
-    return NPTS * (rows * copies * 2 * cloud + vote_rows * (40 + 36 + 8))
+    return NPTS * (rows * copies * 2 * cloud + vote_rows * ((40 if votes == "file" else 0) + 36 + 8))
 
 
-def build_ms(loader, kind, reps=20):
+def store_bytes(scenes):
+    return int(sum(t.numel() * t.element_size() for t in scenes.dev.values()))
+
+
+def compare_votes(stores, loaders, cfg, args):
+    """Both stores in one process, alternated: device time per batch and the fed supervised step."""
+    out = {"store_bytes": {m: store_bytes(stores[m]) for m in stores}, "build_ms": {}}
+    for kind in ("pretrain", "semi"):
+        runs = {m: [] for m in loaders}
+        for _ in range(args.repeats):
+            for m in loaders:
+                runs[m].append(build_ms(loaders[m], kind, replays=50)[0])
+        out["build_ms"][kind] = {m: {"median": round(float(np.median(r)), 4), "spread": round(max(r) - min(r), 4),
+                                     "runs": [round(x, 4) for x in r]} for m, r in runs.items()}
+    if args.builds_only:
+        return out
+    runner = V.SupervisedStep(cfg, torch.device("cuda", 0), num_proposal=256, lr=1e-3)
+    for m in loaders:
+        fed_ms(runner, loaders[m], "pretrain", 4, 1000)  # capture + warm-up
+    runs = {m: [] for m in loaders}
+    for r in range(args.repeats):
+        for m in loaders:
+            runs[m].append(fed_ms(runner, loaders[m], "pretrain", args.steps, 10 * r))
+    out["fed_step_ms"] = {m: {"median": round(float(np.median(r)), 4), "spread": round(max(r) - min(r), 4),
+                              "runs": [round(x, 4) for x in r]} for m, r in runs.items()}
+    return out
+
+
+def build_ms(loader, kind, reps=20, replays=5):
     out = loader.allocate(kind, B if kind == "pretrain" else LAB, 0 if kind == "pretrain" else UNL)
     ids = np.arange(B) % len(loader.labeled)
 
@@ -76,11 +110,11 @@ def build_ms(loader, kind, reps=20):
     torch.cuda.synchronize()
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0.record()
-    for _ in range(5):
+    for _ in range(replays):
         graph.replay()
     t1.record()
     torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / (5 * reps), host
+    return t0.elapsed_time(t1) / (replays * reps), host
 
 
 def plan_of(kind, loader, steps, epoch0):
@@ -126,17 +160,32 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--builds-only", action="store_true", help="no train steps (for a kernel trace)")
+    ap.add_argument("--votes", choices=("file", "boxes"), default="file",
+                    help="the store's vote rows: read from _votes.npz, or computed from the boxes")
+    ap.add_argument("--compare-votes", action="store_true",
+                    help="measure a 'file' and a 'boxes' store alternated in this process, and nothing else")
     args = ap.parse_args()
     if args.scenes < B + UNL:
         ap.error("--scenes must be at least %d" % (B + UNL))
     dev = torch.device("cuda", 0)
-    result = {"num_points": NPTS, "batch": {"pretrain": B, "semi": [LAB, UNL]}}
+    result = {"num_points": NPTS, "batch": {"pretrain": B, "semi": [LAB, UNL]}, "votes": args.votes}
     with tempfile.TemporaryDirectory() as tmp:
         names = ["%06d" % (i + 1) for i in range(args.scenes)]
         SD.write_synthetic_scans(tmp, names, num_points=50000, boxes=12, seed=0)
+        if args.compare_votes:
+            cfg = V.sunrgbd_config()
+            stores = {m: SD.SunRgbdScenes(tmp, names, dev, use_color=False, use_height=True, votes=m)
+                      for m in ("file", "boxes")}
+            loaders = {m: SD.SunRgbdLoader(st, cfg, NPTS, seed=0, labeled=names[:B], unlabeled=names[B:])
+                       for m, st in stores.items()}
+            del result["votes"]
+            result["votes_ab"] = compare_votes(stores, loaders, cfg, args)
+            print(json.dumps(result))
+            return
         t = time.perf_counter()
-        scenes = SD.SunRgbdScenes(tmp, names, dev, use_color=False, use_height=True)
+        scenes = SD.SunRgbdScenes(tmp, names, dev, use_color=False, use_height=True, votes=args.votes)
         result["load_s"] = round(time.perf_counter() - t, 3)
+        result["store_bytes"] = store_bytes(scenes)
     with tempfile.TemporaryDirectory() as tmp:
         result["scannet_build_ms"] = {"pretrain_8x40000": round(scannet_build_ms(tmp), 4)}
     cfg = V.sunrgbd_config()
@@ -144,7 +193,7 @@ def main():
     result["build_ms"], result["build_host_ms"], result["build_bytes"] = {}, {}, {}
     for k in ("pretrain", "semi"):
         dev_ms, host_ms = build_ms(loader, k)
-        nbytes = batch_bytes(k, scenes.channels)
+        nbytes = batch_bytes(k, scenes.channels, args.votes)
         result["build_ms"][k], result["build_host_ms"][k] = round(dev_ms, 4), round(host_ms, 4)
         result["build_bytes"][k] = {"bytes": nbytes, "bytes_per_s": round(nbytes / (dev_ms * 1e-3), 0),
                                     "fraction_of_peak_hbm": round(nbytes / (dev_ms * 1e-3) / PEAK_HBM, 4)}
