@@ -171,7 +171,9 @@ __device__ __forceinline__ float stage_a2_slice(char *base, int row, int seg_c, 
 // sparse part and the staging piece that follows them.  The dense part has the pair-level barriers
 // only: with barriers behind each of ITS two-MFMA groups as well, this compiler (ROCm 7.2) produced a
 // kernel that returns garbage -- each of the two sets alone is correct and as fast
-// (tests/test_gpu_mlp.py::test_pooled_backward_from_the_gram_matrix guards the shipped form).
+// (tests/test_pool_gram256_gpu.py::test_gram256_backward_vs_float64 guards the shipped form: da2, dW3
+// and the sums against float64 torch at every kind of chunk range, within three times plain fp32's
+// own error).
 #define G256_SB() __builtin_amdgcn_sched_barrier(0)
 #define G256_SBS() __builtin_amdgcn_sched_barrier(0)
 #define G256_SBD() do {} while (0)
