@@ -979,6 +979,9 @@ def eval_lin4_pool(x4, img, coeff1, coeff2):
 def eval_stored_prepare(w1, w2, img=None):
     """The weight image of eval_stored_pool: w1 (128,128), w2 (C_out,128)."""
     _f32c(w1, "w1"); _f32c(w2, "w2")
+    # a weight that is a view into one flat parameter buffer (votenet/step.py flatten_parameters) starts at
+    # any float, and the prepare kernel wants 16-byte rows: it reads an aligned copy (once, here)
+    w1, w2 = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (w1, w2))
     c_out = w2.shape[0]
     if img is None:
         img = torch.empty(int(_lib.mlp_eval_stored_image_bytes(c_out)), dtype=torch.uint8, device=w1.device)

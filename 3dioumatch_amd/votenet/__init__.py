@@ -12,3 +12,5 @@ from .step import (SemiSupervisedStep, SupervisedStep, update_ema_variables, lr_
 from .eval_helper import (APCalculator, DeviceAPCalculator, EvalLossMeter, parse_groundtruths,  # noqa: F401
                           parse_groundtruths_device, parse_predictions, parse_predictions_device)
 from .eval_det import eval_det, eval_det_cls, voc_ap  # noqa: F401
+from .train_meter import TrainMeter, tb_name  # noqa: F401
+from .trainer import Trainer, engine_evaluator, loader_epochs  # noqa: F401

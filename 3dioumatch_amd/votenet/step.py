@@ -121,8 +121,24 @@ class SupervisedStep(object):
     """
 
     def __init__(self, cfg, device, world_size=1, num_proposal=256, lr=1e-3, seed=0, graphs=None,
-                 graphs_fallback=False):
+                 graphs_fallback=False, meter=False, guard=False, clip_grad_norm=None):
         self.cfg = cfg
+        # Off by default (the step then launches what it always did).  guard: the update goes
+        # through votenet_adam_step_guarded -- a step whose loss or (exchanged) gradient is not
+        # finite changes neither the parameters, the moments, Adam's step nor the teacher; the
+        # BatchNorm running statistics are written in the forward pass and are NOT rolled back.
+        # clip_grad_norm: torch.nn.utils.clip_grad_norm_ of the flat gradient inside the same
+        # entry (implies guard).  meter: a TrainMeter adds the logged scalars behind the update.
+        self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
+        self.guarded = bool(guard) or self.clip_grad_norm is not None
+        self._guard = torch.zeros(4, dtype=torch.float64, device=device) if self.guarded else None
+        self._guard_partials = None
+        self._last_loss = self._last_end_points = None
+        if meter:
+            from .train_meter import TrainMeter
+            self.meter = TrainMeter(device, guarded=self.guarded)
+        else:
+            self.meter = None
         # False: a failed HIP-graph capture raises.  True: it is reported on stderr and the
         # runner continues with eager launches (`runner.graphs` tells which one is running).
         self.graphs_fallback = bool(graphs_fallback)
@@ -311,6 +327,7 @@ class SupervisedStep(object):
         """Data parallelism: the mean of the per-rank gradients, one collective per step."""
         if not self._exchanges():
             return
+        self._share_verdict()
         if self.time_exchange and self.device.type == "cuda" and \
                 not torch.cuda.is_current_stream_capturing():
             if not hasattr(self, "exchange_events"):
@@ -322,6 +339,58 @@ class SupervisedStep(object):
             self.exchange_events.append((e0, e1))
             return
         torch.distributed.all_reduce(self.flat_grad)
+
+    def _share_verdict(self):
+        """Guarded, more than one rank: a rank whose OWN loss is not finite makes one element of
+        its gradient NaN ahead of the exchange, so that every rank reaches the same verdict from
+        the summed gradient (the loss is per rank, the skip must not be)."""
+        if not self.guarded or self.world <= 1 or self._last_loss is None:
+            return
+        head = self.flat_grad[:1]
+        head.copy_(torch.where(torch.isfinite(self._last_loss.detach()).reshape(1), head,
+                               torch.full_like(head, float("nan"))))
+
+    def guard_report(self):
+        """{"norm", "coefficient", "skipped_last", "skipped_total"} of the guarded update (a host
+        read: for logging, not for the step loop)."""
+        if self._guard is None:
+            raise RuntimeError("guard_report: the runner was built without guard / clip_grad_norm")
+        norm, coef, last, total = self._guard.cpu().tolist()
+        return {"norm": norm, "coefficient": coef, "skipped_last": bool(last),
+                "skipped_total": int(total)}
+
+    def _note(self, loss, end_points):
+        """what the update behind a forward/backward pass reads: the loss (guard), the scalars (meter)"""
+        self._last_loss, self._last_end_points = loss, end_points
+        return loss, end_points
+
+    def _update(self):
+        """The update and, behind it (so that it sees the verdict), the meter's launch."""
+        self._apply()
+        if self.meter is not None:
+            self.meter.add(self._last_end_points, self._guard)
+
+    def _apply_cpu_guarded(self, teacher, ema_weight):
+        """The guarded entry's semantics with tensor operations (CPU: host logic, gloo)."""
+        rec, grad = self._guard, self.flat_grad
+        scaled = grad * (1.0 / self.world) if self.world > 1 else grad
+        s = scaled.double().square().sum()
+        loss = self._last_loss
+        ok = bool(torch.isfinite(s)) and (loss is None or bool(torch.isfinite(loss.detach()).all()))
+        norm = s.sqrt()
+        coef = 1.0
+        if self.clip_grad_norm is not None and self.clip_grad_norm > 0:
+            coef = min(1.0, self.clip_grad_norm / (float(norm) + 1e-6))
+        rec[0], rec[1], rec[2] = norm, coef, 0.0 if ok else 1.0
+        rec[3] += 0.0 if ok else 1.0
+        if not ok:
+            return
+        coef32 = torch.tensor(coef, dtype=grad.dtype)
+        if self.world > 1 or float(coef32) != 1.0:
+            grad.copy_(scaled * coef32)
+        self.optimizer.step()
+        if teacher is not None:
+            teacher.lerp_(self.flat_params.data, ema_weight)
 
     def exchange_report(self):
         """{"backend", "world_size", "allreduce_us" (median device time, None if untimed),
@@ -344,6 +413,8 @@ class SupervisedStep(object):
         update): one kernel of the gfx950 library on the GPU, torch's optimizer elsewhere.  The
         state lives in self.optimizer.state under torch's own keys either way."""
         if self.device.type != "cuda":
+            if self.guarded:
+                return self._apply_cpu_guarded(teacher, ema_weight)
             if self.world > 1:
                 self.flat_grad.mul_(1.0 / self.world)
             self.optimizer.step()
@@ -364,6 +435,29 @@ class SupervisedStep(object):
         if group.get("amsgrad") or group.get("maximize"):
             raise RuntimeError("the flat Adam step implements neither amsgrad nor maximize")
         beta1, beta2 = group["betas"]
+        if self.guarded:
+            n = self.flat_params.numel()
+            if self._guard_partials is None:
+                self._guard_partials = torch.empty(_L.lib.votenet_adam_guard_partials(n),
+                                                   dtype=torch.float64, device=self.device)
+            loss = self._last_loss
+            if loss is not None:
+                loss = loss.detach()
+                if loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != self.flat_grad.device:
+                    raise RuntimeError("the guarded update reads the loss as one float32 device scalar")
+            self._guard_loss = loss  # (kept: a captured launch reads its address)
+            with torch.cuda.device(self.device):
+                _L.check(_L.lib.votenet_adam_step_guarded(
+                    n, self.flat_params.data_ptr(), self.flat_grad.data_ptr(),
+                    st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr(),
+                    lr.data_ptr(), float(beta1), float(beta2), float(group["eps"]),
+                    float(group["weight_decay"]), 1.0 / self.world,
+                    None if teacher is None else teacher.data_ptr(),
+                    None if teacher is None else ema_weight.data_ptr(), self._adam_scratch.data_ptr(),
+                    None if loss is None else loss.data_ptr(), self.clip_grad_norm or 0.0,
+                    self._guard.data_ptr(), self._guard_partials.data_ptr(),
+                    torch.cuda.current_stream(self.device).cuda_stream), "votenet_adam_step_guarded")
+            return
         with torch.cuda.device(self.device):
             _L.check(_L.lib.votenet_adam_step(
                 self.flat_params.numel(), self.flat_params.data_ptr(), self.flat_grad.data_ptr(),
@@ -397,7 +491,10 @@ class SupervisedStep(object):
 
     def _state(self):
         """Every tensor a step mutates besides the optimizer state (restored after capture)."""
-        return [b for b in self.net.buffers()] + [self.flat_params.data]
+        extra = [] if self._guard is None else [self._guard]
+        if self.meter is not None and self.meter.accum is not None:
+            extra.append(self.meter.accum)
+        return [b for b in self.net.buffers()] + [self.flat_params.data] + extra
 
     def _refresh_lr(self):
         """param_groups[0]["lr"] -> the device scalar the (possibly captured) Adam kernel reads."""
@@ -534,6 +631,7 @@ class SupervisedStep(object):
         # state touched by the warm-up iterations and by the capture itself
         state = self._state()
         saved_state = [t.clone() for t in state]
+        had_meter = self.meter is not None and self.meter.accum is not None
         saved_rng = torch.cuda.get_rng_state(dev)
         had_state = len(self.optimizer.state) > 0
         saved_opt = {k: v.clone() for k, v in self.optimizer.state.get(self.flat_params, {}).items()
@@ -557,9 +655,11 @@ class SupervisedStep(object):
             for _ in range(2):  # lazy initialisations (MIOpen/hipBLASLt handles, autograd)
                 geometry = body_geometry(self._slots[0])
                 self._cur_geometry = {k: v.clone() for k, v in geometry.items()}
-                body_step()
+                self._note(*body_step())
+                if self.meter is not None:  # (its sums exist from here on: see the restore below)
+                    self.meter.bind_table(self._last_end_points)
                 self.flat_grad.zero_()
-                self._apply()  # creates the Adam state; a zero gradient leaves the weights alone
+                self._update()  # creates the Adam state; a zero gradient leaves the weights alone
         torch.cuda.current_stream(dev).wait_stream(warm)
         torch.cuda.synchronize(dev)
 
@@ -580,8 +680,9 @@ class SupervisedStep(object):
             try:  # the collective as the first node of G2 (the zero gradient makes it harmless here)
                 g2 = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g2, **mode):
+                    self._share_verdict()
                     torch.distributed.all_reduce(self.flat_grad)
-                    self._apply()
+                    self._update()
                 self._g2, self._exchange_in_graph = g2, True
             except Exception as err:  # noqa: BLE001
                 sys.stderr.write("SupervisedStep: all-reduce not capturable (%s: %s); it stays an "
@@ -592,8 +693,12 @@ class SupervisedStep(object):
         elif not self._exchange_in_graph:
             self._g2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._g2, **mode):
-                self._apply()
+                self._update()
         torch.cuda.synchronize(dev)
+        if self.meter is not None:
+            self.meter.finish_capture()
+            if not had_meter:  # made by the warm-up, after _state() was taken: nothing to restore
+                self.meter.reset()
 
         # undo every side effect of warm-up and capture
         for t, saved in zip(state, saved_state):
@@ -616,9 +721,9 @@ class SupervisedStep(object):
         """forward + loss + backward (+ the update when nothing separates them) as self._g1"""
         self._g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._g1, **mode):
-            self._loss, self._end_points = self._forward_backward(make_inputs())
+            self._loss, self._end_points = self._note(*self._forward_backward(make_inputs()))
             if self._merged:
-                self._apply()
+                self._update()
 
     def _replay_step(self):
         self._g1.replay()
@@ -682,11 +787,11 @@ class SupervisedStep(object):
         ready = batch.pop("_geometry_ready", None)
         if ready is not None:
             torch.cuda.current_stream(self.device).wait_event(ready)
-        loss, end_points = self._forward_backward(batch)
+        loss, end_points = self._note(*self._forward_backward(batch))
         batch.pop("geometry", None)  # consumed: every step computes (or prefetches) its own
         self._exchange_gradients()
         self._before_apply()
-        self._apply()
+        self._update()
         self._expose_gradients()
         return loss, end_points
 
@@ -713,9 +818,10 @@ class SemiSupervisedStep(SupervisedStep):
 
     def __init__(self, cfg, device, world_size=1, num_proposal=256, lr=2e-3, seed=0, graphs=None,
                  unlabeled_loss_weight=2.0, ema_decay=0.999, dataset="scannet", config_dict=None,
-                 graphs_fallback=False):
+                 graphs_fallback=False, meter=False, guard=False, clip_grad_norm=None):
         super().__init__(cfg, device, world_size=world_size, num_proposal=num_proposal, lr=lr,
-                         seed=seed, graphs=graphs, graphs_fallback=graphs_fallback)
+                         seed=seed, graphs=graphs, graphs_fallback=graphs_fallback, meter=meter,
+                         guard=guard, clip_grad_norm=clip_grad_norm)
         from .losses_unlabeled import default_config_dict
         self.teacher = build_detector(cfg, num_proposal=num_proposal, seed=seed).to(device).train()
         for p in self.teacher.parameters():
@@ -899,9 +1005,10 @@ class SemiSupervisedStep(SupervisedStep):
             student = self._student_forward(inputs)
         self._g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._g1, pool=self._g1a.pool(), **mode):
-            self._loss, self._end_points = self._losses_backward(student, self._ema_end_points, inputs)
+            self._loss, self._end_points = self._note(
+                *self._losses_backward(student, self._ema_end_points, inputs))
             if self._merged:
-                self._apply()
+                self._update()
         self._pick_teacher_replay_stream()
 
     def _another_stream(self, *others):

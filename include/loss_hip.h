@@ -131,6 +131,40 @@ int votenet_adam_step(long long n, float *p, float *g, float *m, float *v, float
                       double grad_scale, float *ema, const float *ema_weight, float *scratch,
                       void *stream);
 
+/* votenet_adam_step behind a device-side verdict, for a captured step no host looks into: the
+ * gradient clipping of torch.nn.utils.clip_grad_norm_ and a non-finite guard in front of
+ * optimizer.step() (train.py:339-354, pretrain.py:289).  The arguments of votenet_adam_step, then
+ * loss (NULL or a device scalar), max_norm (<= 0: no clipping), guard (4 doubles, zeroed once by the
+ * caller) and partials (votenet_adam_guard_partials(n) doubles).  Three launches, no host
+ * synchronisation, no atomics (two launches on equal inputs give equal bits):
+ *   s  = sum ((double)(float)(g_i * grad_scale))^2, one partial per span of
+ *        votenet_adam_guard_span() elements, summed in a fixed order
+ *   ok = isfinite(s) && (loss == NULL || isfinite(*loss))
+ *   c  = max_norm > 0 ? min(1, max_norm / (sqrt(s) + 1e-6)) : 1
+ * ok: the update of votenet_adam_step with (g * grad_scale) * c, g rewritten with that value when
+ * grad_scale != 1 or c != 1; with c == 1 every output is bit-equal to votenet_adam_step.  Not ok:
+ * p, m, v, ema, g, step and scratch are not written.  guard[0] = sqrt(s), [1] = c, [2] = 1 if
+ * skipped else 0, [3] += [2] (doubles: two entries of 3e38 have a finite norm above FLT_MAX and
+ * must not skip). */
+int votenet_adam_step_guarded(long long n, float *p, float *g, float *m, float *v, float *step,
+                              const float *lr, double beta1, double beta2, double eps,
+                              double weight_decay, double grad_scale, float *ema,
+                              const float *ema_weight, float *scratch, const float *loss,
+                              double max_norm, double *guard, double *partials, void *stream);
+/* host queries of the guard in front of optimizer.step() (train.py:339-354, pretrain.py:289): the
+ * length of `partials` in doubles for n parameters, and the span of elements behind each */
+int votenet_adam_guard_partials(long long n);
+int votenet_adam_guard_span(void);
+
+/* replaces the statistics loop of train_one_epoch (train.py:356-360: stat_dict[key] +=
+ * end_points[key].item() for every logged key, a host round trip each) with one launch of one
+ * workgroup: table = count device pointers to float scalars, accum = count + 3 doubles, guard =
+ * NULL or the record of votenet_adam_step_guarded.  guard == NULL or guard[2] == 0:
+ * accum[i] += (double)*table[i], accum[count] += 1 (steps), accum[count + 2] += guard[0] (with a
+ * guard).  guard[2] == 1: only accum[count + 1] += 1 (skipped steps).  No atomics. */
+int votenet_train_meter_add(int count, const float *const *table, const double *guard, double *accum,
+                            void *stream);
+
 /* replaces features.div(torch.norm(features, p=2, dim=1).unsqueeze(1)) on the vote features
  * (models/votenet_iou_branch.py:103-104): x (b,c,n) -> y = x / ||x||_2 over c, norm (b,n) */
 int votenet_channel_normalize(int b, int c, int n, const float *x, float *y, float *norm,

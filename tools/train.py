@@ -1,0 +1,165 @@
+"""Train the detector: the front end of votenet/trainer.py with the reference's flag names
+(train.py:31-70, pretrain.py:28-62) for what is supported.
+
+    python tools/train.py --stage pretrain --data_dir scans --meta_dir meta --log_dir log
+    python tools/train.py --stage semi --synthetic 24 --max_epoch 4 --eval_interval 2 --log_dir /tmp/run
+    python tools/train.py --stage semi --synthetic 24 --max_epoch 6 --resume --log_dir /tmp/run
+
+--stage pretrain is pretrain.py (labeled scenes, no teacher), --stage semi is train.py (labeled +
+unlabeled scenes, EMA teacher).  --synthetic N trains on N seeded stand-in scans
+(scannet_data.write_synthetic_scans), so that the loop runs with no dataset at hand.  The statistics
+are summed on the device and read once per --print_interval steps; --no_guard / --clip_grad_norm
+choose what stands in front of the update (votenet/step.py)."""
+import argparse
+import importlib
+import os
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--stage', choices=('pretrain', 'semi'), default='semi')
+    ap.add_argument('--synthetic', type=int, default=0, metavar='N', help='train on N synthetic scans')
+    ap.add_argument('--dataset', default='scannet', choices=('scannet',), help='Dataset name.')
+    ap.add_argument('--data_dir', default=None, help='preprocessed scans (scannet_train_detection_data)')
+    ap.add_argument('--meta_dir', default=None, help='the split lists (scannet/meta_data)')
+    ap.add_argument('--labeled_sample_list', default='scannetv2_train.txt')
+    ap.add_argument('--detector_checkpoint', default='none')
+    ap.add_argument('--log_dir', default='./temp', help='Dump dir to save model checkpoint')
+    ap.add_argument('--num_point', type=int, default=40000, help='Point Number')
+    ap.add_argument('--use_color', action='store_true')
+    ap.add_argument('--no_height', action='store_true')
+    ap.add_argument('--num_target', type=int, default=None, help='Proposal number [256 / 128]')
+    ap.add_argument('--ap_iou_thresh', type=float, default=0.25)
+    ap.add_argument('--max_epoch', type=int, default=1001, help='Epoch to run')
+    ap.add_argument('--batch_size', default=None, help="'8' (pretrain) or labeled,unlabeled: '4,8' (semi)")
+    ap.add_argument('--learning_rate', type=float, default=None, help='[0.001 pretrain / 0.002 semi]')
+    ap.add_argument('--lr_decay_steps', default=None, help="[train.py: '400, 600, 800, 900']")
+    ap.add_argument('--lr_decay_rates', default=None, help="[train.py: '0.3, 0.3, 0.1, 0.1']")
+    ap.add_argument('--ema_decay', type=float, default=0.999, metavar='ALPHA')
+    ap.add_argument('--unlabeled_loss_weight', type=float, default=2.0, metavar='WEIGHT')
+    ap.add_argument('--print_interval', type=int, default=25, help='batch interval to print loss')
+    ap.add_argument('--eval_interval', type=int, default=25, help='epoch interval to evaluate model')
+    ap.add_argument('--save_interval', type=int, default=200, help='epoch interval to save model')
+    ap.add_argument('--resume', action='store_true', help='continue from log_dir/checkpoint.tar')
+    ap.add_argument('--conf_thresh', type=float, default=0.05)
+    ap.add_argument('--view_stats', action='store_true')
+    ap.add_argument('--no_guard', action='store_true', help='the plain update: no non-finite guard')
+    ap.add_argument('--clip_grad_norm', type=float, default=None, metavar='NORM')
+    ap.add_argument('--seed', type=int, default=None, help='re-seed torch with seed + epoch at every epoch')
+    ap.add_argument('--device', default='cuda:0')
+    return ap
+
+
+def settings(flags):
+    """The flags resolved against the stage's defaults (train.py:46-70 / pretrain.py:40-62)."""
+    semi = flags.stage == 'semi'
+    batch = flags.batch_size or ('4,8' if semi else '8')
+    sizes = [int(x) for x in str(batch).split(',')]
+    if len(sizes) != (2 if semi else 1):
+        raise SystemExit("--batch_size: 'labeled,unlabeled' for --stage semi, one number for pretrain")
+    steps = flags.lr_decay_steps or ('400, 600, 800, 900' if semi else '400, 600, 800')
+    rates = flags.lr_decay_rates or ('0.3, 0.3, 0.1, 0.1' if semi else '0.1, 0.1, 0.1')
+    steps, rates = [int(x) for x in steps.split(',')], [float(x) for x in rates.split(',')]
+    if len(steps) != len(rates):
+        raise SystemExit("--lr_decay_steps and --lr_decay_rates differ in length")
+    return {
+        'semi': semi, 'labeled_batch': sizes[0], 'unlabeled_batch': sizes[1] if semi else 0,
+        'learning_rate': flags.learning_rate if flags.learning_rate is not None else (2e-3 if semi else 1e-3),
+        'lr_decay_steps': steps, 'lr_decay_rates': rates,
+        'num_target': flags.num_target if flags.num_target is not None else (128 if semi else 256),
+        'guard': not flags.no_guard, 'clip_grad_norm': flags.clip_grad_norm,
+    }
+
+
+def eval_config_dict(cfg, flags):
+    """train.py:263-275"""
+    return {'dataset_config': cfg, 'remove_empty_box': False, 'use_3d_nms': True, 'nms_iou': 0.25,
+            'use_old_type_nms': False, 'cls_nms': True, 'use_iou_for_nms': False,
+            'per_class_proposal': True, 'conf_thresh': flags.conf_thresh}
+
+
+def main(argv=None):
+    flags = parser().parse_args(argv)
+    opt = settings(flags)
+    sys.path.insert(0, ROOT)
+    import torch
+    importlib.import_module("3dioumatch_amd")
+    V = importlib.import_module("3dioumatch_amd.votenet")
+    SD = importlib.import_module("3dioumatch_amd.votenet.scannet_data")
+    T = importlib.import_module("3dioumatch_amd.votenet.trainer")
+    U = importlib.import_module("3dioumatch_amd.votenet.losses_unlabeled")
+    dev = torch.device(flags.device)
+    if dev.type != "cuda":
+        raise SystemExit("tools/train.py builds its batches on the GPU (--device cuda:N)")
+    cfg = V.scannet_config()
+    use_height = not flags.no_height
+
+    tmp = None
+    if flags.synthetic:
+        tmp = tempfile.TemporaryDirectory()
+        names = ["scene%04d_00" % i for i in range(flags.synthetic)]
+        SD.write_synthetic_scans(tmp.name, names, num_points=max(flags.num_point, 2000) * 5 // 4, seed=0)
+        # a quarter for evaluation, the rest halved into labeled and unlabeled scans
+        n_val = max(1, flags.synthetic // 4)
+        val, train = names[:n_val], names[n_val:]
+        labeled = train[:len(train) // 2] if opt['semi'] else train
+        unlabeled = train[len(train) // 2:] if opt['semi'] else None
+        data_dir = tmp.name
+    else:
+        if not flags.data_dir or not flags.meta_dir:
+            raise SystemExit("--data_dir and --meta_dir (or --synthetic N)")
+        data_dir = flags.data_dir
+        labeled = SD.labeled_split(data_dir, flags.meta_dir, flags.labeled_sample_list)
+        unlabeled = SD.unlabeled_split(data_dir, flags.meta_dir, flags.labeled_sample_list) if opt['semi'] else None
+        val = SD.val_split(data_dir, flags.meta_dir)
+        names = sorted(set(labeled) | set(unlabeled or ()) | set(val))
+    scenes = SD.ScanNetScenes(data_dir, names, dev, use_color=flags.use_color, use_height=use_height)
+    if tmp is not None:
+        tmp.cleanup()  # the store is resident
+    loader = SD.ScanNetLoader(scenes, cfg, flags.num_point, seed=flags.seed or 0, labeled=labeled,
+                              unlabeled=unlabeled)
+    val_loader = SD.ScanNetLoader(scenes, cfg, flags.num_point, seed=flags.seed or 0, labeled=val)
+
+    common = dict(num_proposal=opt['num_target'], lr=opt['learning_rate'], meter=True, guard=opt['guard'],
+                  clip_grad_norm=opt['clip_grad_norm'])
+    if opt['semi']:
+        cd = U.default_config_dict(cfg, unlabeled_batch_size=opt['unlabeled_batch'], view_stats=flags.view_stats)
+        runner = V.SemiSupervisedStep(cfg, dev, unlabeled_loss_weight=flags.unlabeled_loss_weight,
+                                      ema_decay=flags.ema_decay, config_dict=cd, **common)
+    else:
+        runner = V.SupervisedStep(cfg, dev, **common)
+    if flags.detector_checkpoint != 'none':  # train.py:205-215: both networks start from the pretrained one
+        ckpt = torch.load(flags.detector_checkpoint, map_location=dev, weights_only=False)
+        runner.net.load_state_dict(ckpt['model_state_dict'])
+        if opt['semi']:
+            runner.teacher.load_state_dict(ckpt['model_state_dict'])
+
+    batches = T.loader_epochs(runner, loader, flags.stage, opt['labeled_batch'], opt['unlabeled_batch'],
+                              seed=flags.seed or 0, unlabeled_labels=flags.view_stats)
+    eval_bs = opt['labeled_batch'] + opt['unlabeled_batch']
+    evaluate = T.engine_evaluator(lambda: SD.eval_batches(val_loader, eval_bs), eval_config_dict(cfg, flags),
+                                  ap_iou_thresholds=(flags.ap_iou_thresh, 0.5)
+                                  if flags.ap_iou_thresh != 0.5 else (0.25, 0.5))
+    trainer = T.Trainer(runner, batches, evaluate=evaluate, log_dir=flags.log_dir,
+                        print_interval=flags.print_interval, eval_interval=flags.eval_interval,
+                        save_interval=flags.save_interval, base_lr=opt['learning_rate'],
+                        lr_decay_steps=opt['lr_decay_steps'], lr_decay_rates=opt['lr_decay_rates'],
+                        seed=flags.seed)
+    trainer.log(str(flags))
+    if flags.resume:
+        path = os.path.join(flags.log_dir, 'checkpoint.tar')
+        trainer.log('resumed %s at epoch %d' % (path, trainer.resume(path)))
+    trainer.fit(flags.max_epoch)
+    torch.cuda.synchronize(dev)
+    trainer.log('host reads of the training statistics: %d' % runner.meter.host_reads)
+    if opt['guard']:
+        trainer.log('guard: %s' % runner.guard_report())
+    return trainer
+
+
+if __name__ == '__main__':
+    main()
