@@ -178,6 +178,7 @@ _SIGNATURES = {
                                   _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp],
     "votenet_adam_guard_partials": [ctypes.c_longlong],
     "votenet_adam_guard_span": [],
+    "votenet_guard_state_sync": [ctypes.c_longlong, _vp, _vp, _vp, _vp],
     "votenet_train_meter_add": [_c_int, _vp, _vp, _vp, _vp],
     "iou3d_corners_iou3d": [_c_int, _vp, _c_int, _vp, _vp, _vp],
     "iou3d_corners_best_match": [_c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -165,6 +165,21 @@ int adam_launch(long long n, float *p, float *g, float *m, float *v, float *step
   return pn2_launch_status();
 }
 
+// Behind a guarded update: the verdict applied to the state a step writes OUTSIDE the update, in its
+// forward passes (the BatchNorm buffers, one byte arena: votenet/step.py flatten_buffers).  Applied
+// (guard[2] == 0): shadow <- state, the state is the last good one.  Skipped: state <- shadow.  Both
+// directions in one kernel, so a captured launch serves either verdict.  One 16-byte load and one
+// 16-byte store per lane; guard is only read.
+__global__ void __launch_bounds__(256)
+guard_state_sync_kernel(long long nvec, uint4 *state, uint4 *shadow, const double *__restrict__ guard) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nvec) return;
+  const bool skipped = guard[2] != 0.0;
+  const uint4 *src = skipped ? shadow : state;
+  uint4 *dst = skipped ? state : shadow;
+  dst[i] = src[i];
+}
+
 }  // namespace
 
 // One Adam step on flat buffers of n floats (16-byte aligned); step (1 float, the count of steps
@@ -203,4 +218,22 @@ PN2_API int votenet_adam_step_guarded(long long n, float *p, float *g, float *m,
     return (int)hipErrorInvalidValue;
   return adam_launch(n, p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, grad_scale, ema,
                      ema_weight, scratch, loss, max_norm, guard, partials, (hipStream_t)stream_);
+}
+
+// The verdict of votenet_adam_step_guarded (guard[2], read on the device) applied to nbytes of state
+// that the step's forward passes wrote: applied -> shadow <- state, skipped -> state <- shadow.  One
+// launch on `stream`, behind the guarded update; nbytes a multiple of 16, both pointers 16-byte
+// aligned, the two ranges disjoint.  guard is not written.
+PN2_API int votenet_guard_state_sync(long long nbytes, void *state, void *shadow, const double *guard,
+                                     void *stream_) {
+  if (nbytes == 0) return 0;
+  if (nbytes < 0 || nbytes % 16 != 0 || !state || !shadow || !guard ||
+      (uintptr_t)state % 16 != 0 || (uintptr_t)shadow % 16 != 0)
+    return (int)hipErrorInvalidValue;
+  const long long nvec = nbytes / 16;
+  const long long blocks = (nvec + 255) / 256;
+  if (blocks > 0x7fffffffLL) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(guard_state_sync_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     (hipStream_t)stream_, nvec, (uint4 *)state, (uint4 *)shadow, guard);
+  return pn2_launch_status();
 }

@@ -91,6 +91,45 @@ def flatten_parameters(module):
     return torch.nn.Parameter(flat, requires_grad=True)
 
 
+STATE_ALIGN = 256  # bytes between buffer offsets in a state arena: what the allocator gave each one
+
+
+def flatten_buffers(modules):
+    """Re-home every buffer of `modules` (one module or a sequence) as a view into ONE contiguous
+    byte arena (torch.uint8) and return the arena: the running statistics, the int64
+    num_batches_tracked and whatever else is registered, in named_buffers() order with duplicates
+    removed, each at an offset that is a multiple of STATE_ALIGN, the size padded to a multiple of
+    16 bytes.  Everything a forward pass writes outside the parameters then moves with one copy.
+    The tensor objects stay (only their storage changes), so state_dict()/load_state_dict() keep
+    working -- they copy in place -- with the same keys, dtypes, shapes and `persistent` flags.
+    Call it where flatten_parameters is called: before anything captures a pointer."""
+    if isinstance(modules, torch.nn.Module):
+        modules = [modules]
+    buffers, seen = [], set()
+    for module in modules:
+        for _, b in module.named_buffers():
+            if id(b) not in seen:
+                seen.add(id(b))
+                buffers.append(b)
+    if not buffers:
+        return torch.zeros(0, dtype=torch.uint8)
+    device = buffers[0].device
+    offsets, total = [], 0
+    for b in buffers:
+        if b.device != device:
+            raise ValueError("flatten_buffers: buffers on %s and on %s" % (device, b.device))
+        offsets.append(total)
+        nbytes = b.numel() * b.element_size()
+        total += -(-nbytes // STATE_ALIGN) * STATE_ALIGN
+    arena = torch.zeros(-(-total // 16) * 16, dtype=torch.uint8, device=device)
+    for b, off in zip(buffers, offsets):
+        nbytes = b.numel() * b.element_size()
+        view = arena[off:off + nbytes].view(b.dtype).view(b.shape)
+        view.copy_(b.data)
+        b.data = view
+    return arena
+
+
 def _tensor_items(batch):
     return {k: v for k, v in batch.items() if torch.is_tensor(v)}
 
@@ -110,7 +149,8 @@ class SupervisedStep(object):
         G1  forward_with_pred_jitter -> get_labeled_loss -> backward -> gradients packed into
             one flat buffer
         --  world_size > 1: ONE all-reduce of the flat gradient (RCCL / gloo), between graphs
-        G2  Adam on the flat parameter buffer
+        G2  Adam on the flat parameter buffer (guarded: then the verdict applied to the buffers
+            the forward pass wrote, votenet_guard_state_sync; with a meter: then its launch)
 
     In graph mode the returned loss / end_points are the graphs' STATIC output buffers: the next
     replay overwrites them, so callers that accumulate statistics across steps must clone().
@@ -125,8 +165,9 @@ class SupervisedStep(object):
         self.cfg = cfg
         # Off by default (the step then launches what it always did).  guard: the update goes
         # through votenet_adam_step_guarded -- a step whose loss or (exchanged) gradient is not
-        # finite changes neither the parameters, the moments, Adam's step nor the teacher; the
-        # BatchNorm running statistics are written in the forward pass and are NOT rolled back.
+        # finite changes neither the parameters, the moments, Adam's step nor the teacher, and
+        # the buffers its forward passes wrote (BatchNorm running statistics, num_batches_tracked)
+        # are put back from the shadow of the last good state (_home_guard_state).
         # clip_grad_norm: torch.nn.utils.clip_grad_norm_ of the flat gradient inside the same
         # entry (implies guard).  meter: a TrainMeter adds the logged scalars behind the update.
         self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
@@ -150,6 +191,9 @@ class SupervisedStep(object):
         self.flat_params = flatten_parameters(self.net)
         self.flat_grad = torch.zeros_like(self.flat_params.data)
         self.flat_params.grad = self.flat_grad
+        self.state_arena = self.state_shadow = None
+        if self.guarded:
+            self._home_guard_state([self.net])
         on_gpu = device.type == "cuda"
         self.graphs = on_gpu if graphs is None else (bool(graphs) and on_gpu)
         if os.environ.get("VOTENET_HIP_GRAPHS", "1") == "0":
@@ -170,6 +214,50 @@ class SupervisedStep(object):
         self._mask_cache = (None, None, None)
         self._token = 0
         self.global_step = 0
+
+    # ---------------------------------------------------------------- the guard's buffer state
+    def _home_guard_state(self, modules):
+        """Guarded runners only: every buffer of `modules` moves into one byte arena
+        (flatten_buffers) with a shadow of the same size beside it, the state the last applied step
+        left.  Behind each guarded update ONE copy follows the verdict (_sync_state_by_verdict):
+        applied, shadow <- arena; skipped, arena <- shadow.  load_state_dict() of a module re-arms
+        the shadow through a post-hook; a caller that writes a buffer in place calls
+        sync_guard_state() itself.  (A module homed before moves again: the semi-supervised runner
+        re-homes the student together with its teacher, inside its constructor.)"""
+        self.state_arena = flatten_buffers(modules)
+        self.state_shadow = self.state_arena.clone()
+        hooked = self.__dict__.setdefault("_guard_hooked", set())
+        ref = weakref.ref(self)
+
+        def rearm(module, incompatible_keys):
+            runner = ref()
+            if runner is not None:
+                runner.sync_guard_state()
+        for module in modules:
+            if id(module) not in hooked:
+                hooked.add(id(module))
+                module.register_load_state_dict_post_hook(rearm)
+
+    @torch.no_grad()
+    def sync_guard_state(self):
+        """shadow <- arena: declare the buffers as they are now the last good state.  Runs by itself
+        after load_state_dict() of the student or the teacher; call it after writing a buffer in
+        place (such writes are not tracked).  Nothing to do on an unguarded runner."""
+        if self.state_arena is not None:
+            self.state_shadow.copy_(self.state_arena)
+
+    def _sync_state_by_verdict(self):
+        """The launch behind votenet_adam_step_guarded, on its stream: the verdict it left in
+        self._guard, applied to the buffer arena (votenet_guard_state_sync)."""
+        if self.state_arena is None or self.state_arena.numel() == 0:
+            return
+        import importlib
+        _L = importlib.import_module("3dioumatch_amd._lib")
+        with torch.cuda.device(self.device):
+            _L.check(_L.lib.votenet_guard_state_sync(
+                self.state_arena.numel(), self.state_arena.data_ptr(), self.state_shadow.data_ptr(),
+                self._guard.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
+                "votenet_guard_state_sync")
 
     # ---------------------------------------------------------------- schedules
     def set_epoch(self, epoch, base_lr=1e-3):
@@ -384,6 +472,8 @@ class SupervisedStep(object):
         rec[0], rec[1], rec[2] = norm, coef, 0.0 if ok else 1.0
         rec[3] += 0.0 if ok else 1.0
         if not ok:
+            if self.state_arena is not None:
+                self.state_arena.copy_(self.state_shadow)  # the forward passes did not happen either
             return
         coef32 = torch.tensor(coef, dtype=grad.dtype)
         if self.world > 1 or float(coef32) != 1.0:
@@ -391,6 +481,7 @@ class SupervisedStep(object):
         self.optimizer.step()
         if teacher is not None:
             teacher.lerp_(self.flat_params.data, ema_weight)
+        self.sync_guard_state()
 
     def exchange_report(self):
         """{"backend", "world_size", "allreduce_us" (median device time, None if untimed),
@@ -457,6 +548,7 @@ class SupervisedStep(object):
                     None if loss is None else loss.data_ptr(), self.clip_grad_norm or 0.0,
                     self._guard.data_ptr(), self._guard_partials.data_ptr(),
                     torch.cuda.current_stream(self.device).cuda_stream), "votenet_adam_step_guarded")
+            self._sync_state_by_verdict()
             return
         with torch.cuda.device(self.device):
             _L.check(_L.lib.votenet_adam_step(
@@ -492,6 +584,8 @@ class SupervisedStep(object):
     def _state(self):
         """Every tensor a step mutates besides the optimizer state (restored after capture)."""
         extra = [] if self._guard is None else [self._guard]
+        if self.state_shadow is not None:  # (the arena itself: the modules' buffers below)
+            extra.append(self.state_shadow)
         if self.meter is not None and self.meter.accum is not None:
             extra.append(self.meter.accum)
         return [b for b in self.net.buffers()] + [self.flat_params.data] + extra
@@ -828,6 +922,8 @@ class SemiSupervisedStep(SupervisedStep):
             p.requires_grad_(False)  # train.py:176-178 (detach_)
         self.flat_teacher = flatten_parameters(self.teacher).data
         self.flat_teacher.copy_(self.flat_params.data)  # both start from the same checkpoint
+        if self.guarded:  # ONE arena over the student and then the teacher: one launch serves both
+            self._home_guard_state([self.net, self.teacher])
         self.unlabeled_loss_weight = unlabeled_loss_weight
         self.ema_decay = ema_decay
         self.config_dict = config_dict or default_config_dict(cfg, dataset=dataset)

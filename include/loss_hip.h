@@ -156,6 +156,19 @@ int votenet_adam_step_guarded(long long n, float *p, float *g, float *m, float *
 int votenet_adam_guard_partials(long long n);
 int votenet_adam_guard_span(void);
 
+/* makes a step that votenet_adam_step_guarded skipped a step that did not happen for the state its
+ * forward passes wrote as well: the BatchNorm running statistics and num_batches_tracked, which
+ * forward_with_pred_jitter moves before loss.backward() / optimizer.step() / update_ema_variables
+ * (train.py:350-354; pretrain.py:331-332) get to decide anything.  state and shadow: nbytes each
+ * (a multiple of 16), 16-byte aligned, disjoint; guard: the record of votenet_adam_step_guarded,
+ * read on the device by every workgroup, never written.  guard[2] == 0 (applied): shadow <- state.
+ * guard[2] != 0 (skipped): state <- shadow.  One launch of 256-lane workgroups, one 16-byte load
+ * and store per lane, both directions in the one kernel (a captured launch replays with whichever
+ * verdict the step reaches).  nbytes == 0: returns 0 without a launch; a NULL pointer, an nbytes
+ * that is no multiple of 16 or a misaligned pointer: hipErrorInvalidValue, nothing launched. */
+int votenet_guard_state_sync(long long nbytes, void *state, void *shadow, const double *guard,
+                             void *stream);
+
 /* replaces the statistics loop of train_one_epoch (train.py:356-360: stat_dict[key] +=
  * end_points[key].item() for every logged key, a host round trip each) with one launch of one
  * workgroup: table = count device pointers to float scalars, accum = count + 3 doubles, guard =

@@ -3,12 +3,15 @@
 
     python tools/train_telemetry_bench.py [--steps 50] [--repeats 3] [--out profiles/train_telemetry.json]
 
-Three arms per stage, alternated inside ONE process (boxes differ by 2-3 %):
+Four arms per stage, alternated inside ONE process (boxes differ by 2-3 %):
   a  everything off: the step as it was before the meter and the guard existed
   b  meter + guard on, the meter read once per 25 steps (the loop of votenet/trainer.py)
   c  everything off, plus the reference's statistics loop: one .item() per logged key and step
      (train.py:356-360), over the same keys
-b - a is what the feature costs, c - a what it saves.  Nothing here asserts a time."""
+  d  b without the buffer rollback: no state arena, no votenet_guard_state_sync launch (the guard
+     as it was before the rollback existed)
+b - a is what the feature costs, c - a what it saves, b - d what the rollback's one launch adds.
+Nothing here asserts a time."""
 import argparse
 import importlib
 import json
@@ -55,11 +58,19 @@ def fed_ms(runner, loader, kind, steps, epoch0, arm):
             stat = {}
             for k in keys:
                 stat[k] = stat.get(k, 0) + ep[k].item()
-        elif arm == "b" and (i + 1) % PRINT == 0:
+        elif arm in ("b", "d") and (i + 1) % PRINT == 0:
             runner.meter.result()
     t1.record(main)
     torch.cuda.synchronize()
     return t0.elapsed_time(t1) / steps
+
+
+def without_rollback(step_class):
+    """arm d: the guarded runner of `step_class` that homes no buffers and so launches no state sync"""
+    class NoRollback(step_class):
+        def _home_guard_state(self, modules):
+            pass
+    return NoRollback
 
 
 def main():
@@ -81,13 +92,16 @@ def main():
     loader = SD.ScanNetLoader(scenes, cfg, NPTS, seed=0, labeled=names[:max(half, B)],
                               unlabeled=names[half:] if args.scenes - half >= UNL else names)
     out = {"what": "ms per fed training step, ScanNet shapes (N = %d, K = 256); a: meter and guard off, "
-                   "b: both on + one read per %d steps, c: off + one .item() per logged key and step"
+                   "b: both on + one read per %d steps, c: off + one .item() per logged key and step, "
+                   "d: b without the buffer rollback (no arena, no state-sync launch)"
                    % (NPTS, PRINT), "device": torch.cuda.get_device_name(0), "steps": args.steps,
            "repeats": args.repeats}
     for kind in ("pretrain", "semi"):
-        make = (lambda **kw: V.SemiSupervisedStep(cfg, dev, num_proposal=256, lr=2e-3, **kw)) if kind == "semi" \
-            else (lambda **kw: V.SupervisedStep(cfg, dev, num_proposal=256, lr=1e-3, **kw))
-        runners = {"a": make(), "b": make(meter=True, guard=True), "c": make()}
+        step_class, lr = (V.SemiSupervisedStep, 2e-3) if kind == "semi" else (V.SupervisedStep, 1e-3)
+        make = lambda cls=step_class, **kw: cls(cfg, dev, num_proposal=256, lr=lr, **kw)  # noqa: E731
+        runners = {"a": make(), "b": make(meter=True, guard=True), "c": make(),
+                   "d": make(without_rollback(step_class), meter=True, guard=True)}
+        assert runners["d"].state_arena is None and runners["b"].state_arena is not None
         runs = {arm: [] for arm in runners}
         for arm, runner in runners.items():
             fed_ms(runner, loader, kind, 4, 1000, arm)  # capture + warm-up
@@ -103,6 +117,9 @@ def main():
             "b_minus_a_percent": round((med["b"] - med["a"]) / med["a"] * 100, 2),
             "c_minus_a_us": round((med["c"] - med["a"]) * 1e3, 1),
             "c_minus_a_percent": round((med["c"] - med["a"]) / med["a"] * 100, 2),
+            "d_ms": round(med["d"], 4), "b_minus_d_us": round((med["b"] - med["d"]) * 1e3, 1),
+            "b_minus_d_percent": round((med["b"] - med["d"]) / med["d"] * 100, 2),
+            "state_arena_bytes": int(runners["b"].state_arena.numel()),
             "spread_ms": {arm: round(max(v) - min(v), 4) for arm, v in runs.items()},
             "logged_keys": len(runners["b"].meter.keys), "skipped_total": rep["skipped_total"],
             "meter_host_reads": runners["b"].meter.host_reads}
