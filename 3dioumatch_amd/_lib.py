@@ -200,6 +200,10 @@ _LOADER_SIGNATURES = {
     "scene_batch_build": [_vp, _vp],
     "scene_sunrgbd_batch_build": [_vp, _vp],
     "scene_sunrgbd_votes": [_vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp],
+    # the label-free scan path (include/scan_hip.h)
+    "scene_scan_prepare": [_vp, _vp],
+    "scene_scan_batch_build": [_vp, _vp],
+    "scene_detections_pack": [_vp, _vp],
 }
 
 

@@ -14,3 +14,5 @@ from .eval_helper import (APCalculator, DeviceAPCalculator, EvalLossMeter, parse
 from .eval_det import eval_det, eval_det_cls, voc_ap  # noqa: F401
 from .train_meter import TrainMeter, tb_name  # noqa: F401
 from .trainer import Trainer, engine_evaluator, loader_epochs  # noqa: F401
+from .scan_data import ScanLoader, ScanStore  # noqa: F401
+from .detect import Detections, detect  # noqa: F401

@@ -1,0 +1,303 @@
+"""Scans WITHOUT labels: a resident store of raw clouds and the eval batches built from it on the GPU.
+
+Both labeled stores (scannet_data.ScanNetScenes, sunrgbd_data.SunRgbdScenes) refuse a scan without
+its label files.  `ScanStore` takes bare (n, 3) xyz or (n, 6) xyz + rgb clouds -- arrays, `.npy`
+files or `.npz` files with a `pc` member (the SUN RGB-D `_pc.npz` layout) -- keeps the RAW float32
+rows in one flat device array with an offset / count table, and does in ONE launch at construction
+(scene_scan_prepare, include/scan_hip.h) everything that needs a pass over the points: the floor
+height np.percentile(z, 0.99) of every scan and its count of non-finite values.  The constructor reads
+that small table once -- the only host read of the store's life -- and raises for a NaN or Inf.
+
+`ScanLoader.batch` is one launch (scene_scan_batch_build): the eval sampling of the labeled loaders
+(the same counter-based draw, so the same rows for the same (seed, counter, ids)), the dataset's
+colour normalisation rounded once from double as read_scene does, and height = z - floor in float32.
+`host_floor` and `ScanLoader.host_batch` restate both in numpy: the CPU path and the yardstick.
+
+One difference from the SUN RGB-D reader: float64 input is cast to float32 on the host BEFORE the
+floor and the colour normalisation, where sunrgbd_data.read_scene works in the file's dtype and
+rounds afterwards.  For float32 files (and every ScanNet `_vert.npy`, which the ScanNet reader casts
+first too) the batches are bit-equal to the labeled loaders' eval batches.
+
+Zero sign: -0.0 and +0.0 compare equal in numpy's partition, so where the selected order statistic is
+a zero its sign is unspecified; floors are compared with ==, everything else bit for bit.
+"""
+import ctypes
+import importlib
+import os
+
+import numpy as np
+import torch
+
+from .scannet_data import DRAW_STUDENT, MAX_BATCH, SceneError, sample_indices
+
+DATASETS = ("scannet", "sunrgbd")
+MEAN_COLOR_RGB = {"scannet": np.array([109.8, 97.2, 83.8]),  # scannet_detection_dataset.py:24
+                  "sunrgbd": np.array([0.5, 0.5, 0.5])}      # sunrgbd_detection_dataset.py:41
+
+_c_int, _c_uint, _vp = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p
+
+
+def host_floor(z):
+    """np.percentile(z.astype(float32), 0.99) restated: the two order statistics of numpy's linear
+    method and its float32 interpolation (numpy.lib._function_base_impl._quantile / _lerp), every
+    operation rounded to float32.  Bit-equal to np.percentile apart from the sign of a zero."""
+    z = np.asarray(z, np.float32).reshape(-1)
+    n = z.shape[0]
+    if n == 0:
+        raise ValueError("host_floor: an empty cloud")
+    f = np.float32
+    q = f(0.99) / f(100)
+    v = f(q * f(n - 1))
+    lo = min(int(np.floor(v)), n - 1)
+    hi = min(lo + 1, n - 1)
+    g = f(v - f(lo))
+    part = np.partition(z, sorted({lo, hi}))
+    a, b = part[lo], part[hi]
+    d = f(b - a)
+    if g >= f(0.5):
+        return f(b - f(d * f(f(1) - g)))
+    return f(a + f(d * g))
+
+
+class _PrepareArgs(ctypes.Structure):  # field order == include/scan_hip.h ScanPrepareArgs
+    _fields_ = [("S", _c_int), ("C", _c_int)] + [(n, _vp) for n in ("cloud", "offset", "count", "floor", "nonfinite")]
+
+
+class _BatchArgs(ctypes.Structure):  # field order == include/scan_hip.h ScanBatchArgs
+    _fields_ = ([(n, _c_int) for n in ("B", "N", "C", "use_color", "use_height", "dataset")] +
+                [("seed", _c_uint), ("counter", _c_uint)] +
+                [(n, _c_int * MAX_BATCH) for n in ("scene", "scan_idx")] +
+                [(n, _vp) for n in ("cloud", "offset", "count", "floor", "idx_in", "point_clouds", "scan_idx_out")])
+
+
+def _load_cloud(path):
+    name = os.path.basename(path)
+    for suffix in ("_vert.npy", "_pc.npz", ".npy", ".npz"):
+        if name.endswith(suffix):
+            name = name[:-len(suffix)]
+            break
+    if not os.path.exists(path):
+        raise SceneError("scan %s: missing %s" % (name, path))
+    if path.endswith(".npz"):
+        with np.load(path) as f:
+            if "pc" not in f.files:
+                raise SceneError("scan %s: %s has no 'pc'" % (name, path))
+            return name, f["pc"]
+    if path.endswith(".npy"):
+        return name, np.load(path)
+    raise SceneError("scan %s: %s is neither .npy nor .npz" % (name, path))
+
+
+def scan_prepare_gpu(cloud, offset, count):
+    """(floor (S,) f32, nonfinite (S,) i32) of the scans of a flat (P, C) device cloud: one launch."""
+    _L = importlib.import_module("3dioumatch_amd._lib")
+    S = count.shape[0]
+    floor = torch.empty(S, dtype=torch.float32, device=cloud.device)
+    nonfinite = torch.empty(S, dtype=torch.int32, device=cloud.device)
+    a = _PrepareArgs()
+    a.S, a.C = S, cloud.shape[1]
+    a.cloud, a.offset, a.count = cloud.data_ptr(), offset.data_ptr(), count.data_ptr()
+    a.floor, a.nonfinite = floor.data_ptr(), nonfinite.data_ptr()
+    with torch.cuda.device(cloud.device):
+        _L.check(_L.lib.scene_scan_prepare(ctypes.byref(a), _L.current_stream_ptr(cloud.device)),
+                 "scene_scan_prepare")
+    return floor, nonfinite
+
+
+class ScanStore(object):
+    """`clouds`: a list of (n_i, 3) or (n_i, 6) arrays (xyz, optionally rgb), 1 <= n_i < 2^30, all of
+    one width; float64 is cast to float32 here (see the module docstring).  The raw rows live in one
+    flat device array; `device=None` keeps the host copy only (the CPU path: floors by host_floor).
+    Malformed input raises SceneError naming the scan."""
+
+    def __init__(self, clouds, device, dataset="scannet", names=None):
+        if dataset not in DATASETS:
+            raise ValueError("dataset must be one of %s, got %r" % (DATASETS, dataset))
+        clouds = list(clouds)
+        if not clouds:
+            raise SceneError("no scans to load")
+        self.names = list(names) if names is not None else ["scan%04d" % i for i in range(len(clouds))]
+        if len(self.names) != len(clouds) or len(set(self.names)) != len(clouds):
+            raise ValueError("names: one distinct name per cloud")
+        self.dataset = dataset
+        rows = []
+        for name, c in zip(self.names, clouds):
+            c = np.asarray(c)
+            if c.ndim != 2:
+                raise SceneError("scan %s: the cloud has shape %s, expected (n, 3) or (n, 6)" % (name, c.shape))
+            if c.shape[1] not in (3, 6):
+                raise SceneError("scan %s: %d columns, expected 3 (xyz) or 6 (xyz rgb)" % (name, c.shape[1]))
+            if c.shape[0] == 0 or c.shape[0] >= 1 << 30:
+                raise SceneError("scan %s: %d points" % (name, c.shape[0]))
+            if c.dtype.kind not in "fiu":
+                raise SceneError("scan %s: dtype %s is not numeric" % (name, c.dtype))
+            rows.append(np.ascontiguousarray(c, np.float32))
+        self.columns = rows[0].shape[1]
+        for name, c in zip(self.names, rows):
+            if c.shape[1] != self.columns:
+                raise SceneError("scan %s: %d columns, but scan %s has %d (one width per store)"
+                                 % (name, c.shape[1], self.names[0], self.columns))
+        self.clouds = rows
+        self.count = np.array([c.shape[0] for c in rows], np.int32)
+        self.offset = np.concatenate([[0], np.cumsum(self.count, dtype=np.int64)[:-1]]).astype(np.int64)
+        self.device = torch.device(device) if device is not None else None
+        self.dev = None
+        if self.device is None:
+            nonfinite = np.array([int((~np.isfinite(c)).sum()) for c in rows], np.int64)
+            self._refuse(nonfinite)
+            self.floor = np.array([host_floor(c[:, 2]) for c in rows], np.float32)
+            return
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
+        self.dev = {"cloud": t(np.concatenate(rows)), "offset": t(self.offset), "count": t(self.count)}
+        floor, nonfinite = scan_prepare_gpu(self.dev["cloud"], self.dev["offset"], self.dev["count"])
+        self.dev["floor"] = floor
+        table = torch.stack([floor.double(), nonfinite.double()]).cpu().numpy()  # the one host read
+        self._refuse(table[1].astype(np.int64))
+        self.floor = table[0].astype(np.float32)
+
+    def _refuse(self, nonfinite):
+        bad = ["%s (%d)" % (self.names[i], nonfinite[i]) for i in np.nonzero(nonfinite)[0]]
+        if bad:
+            raise SceneError("scans with NaN or Inf coordinates or colours (count): " + ", ".join(bad))
+
+    @classmethod
+    def from_files(cls, paths, device, dataset="scannet", names=None):
+        """`.npy` files, and `.npz` files with a `pc` member; the default names are the file names
+        without `_vert.npy` / `_pc.npz` / the extension."""
+        loaded = [_load_cloud(p) for p in paths]
+        if names is None:
+            names = [n for n, _ in loaded]
+        return cls([c for _, c in loaded], device, dataset, names)
+
+    def __len__(self):
+        return len(self.names)
+
+
+class ScanLoader(object):
+    """Batches of `num_points` points per scan: {'point_clouds': (B, N, 3 + C) f32, 'scan_idx': (B,)
+    i64}, the rows ScannetDetectionDataset / SunrgbdDetectionDataset('val', augment=False) give for a
+    scan (scannet_detection_dataset.py:85-223, sunrgbd_detection_dataset.py:119-246) without their
+    labels.  The sample of row r is the draw (seed, counter, r, DRAW_STUDENT) of the labeled
+    loaders; `draws={'idx': (B, N) ints}` replaces it.  With use_color=False a 6-column store
+    serves xyz only."""
+
+    def __init__(self, store, num_points, use_color=False, use_height=True, seed=0):
+        if use_color and store.columns != 6:
+            raise ValueError("ScanLoader: use_color needs a store of 6-column clouds (xyz rgb)")
+        self.store, self.num_points, self.seed = store, int(num_points), int(seed)
+        if self.num_points < 1:
+            raise ValueError("ScanLoader: num_points >= 1")
+        self.use_color, self.use_height = bool(use_color), bool(use_height)
+        self.channels = 3 + 3 * self.use_color + self.use_height
+
+    def __len__(self):
+        return len(self.store)
+
+    def _ids(self, ids):
+        ids = np.asarray(ids, np.int64).reshape(-1)
+        if not 1 <= len(ids) <= MAX_BATCH:
+            raise ValueError("a batch holds 1..%d scans, got %d" % (MAX_BATCH, len(ids)))
+        if (ids < 0).any() or (ids >= len(self.store)).any():
+            raise ValueError("scan ids out of range of the store's %d scans" % len(self.store))
+        return ids
+
+    def _given(self, ids, draws):
+        v = np.asarray(draws["idx"]).reshape(len(ids), self.num_points)
+        if (v < 0).any() or (v >= self.store.count[ids][:, None]).any():
+            raise ValueError("explicit draws 'idx' out of range of the scans' point counts")
+        return np.ascontiguousarray(v, np.int32)
+
+    def allocate(self, B):
+        dev = self.store.device
+        return {"point_clouds": torch.empty((B, self.num_points, self.channels), dtype=torch.float32, device=dev),
+                "scan_idx": torch.empty((B,), dtype=torch.int64, device=dev)}
+
+    def batch(self, ids, counter=0, out=None, draws=None, stream=None):
+        ids = self._ids(ids)
+        B, N = len(ids), self.num_points
+        given = self._given(ids, draws) if draws is not None and "idx" in draws else None
+        st = self.store
+        if st.dev is None:
+            raise RuntimeError("ScanLoader: the store has no device copy (device=None); use host_batch")
+        _L = importlib.import_module("3dioumatch_amd._lib")
+        current = torch.cuda.current_stream(st.device)
+        if stream is None:
+            stream = current
+        fresh = out is None
+        if fresh:
+            out = self.allocate(B)
+        pc, si = out["point_clouds"], out["scan_idx"]
+        if tuple(pc.shape) != (B, N, self.channels) or pc.dtype != torch.float32 or not pc.is_contiguous() or \
+                tuple(si.shape) != (B,) or si.dtype != torch.int64 or pc.device != st.device:
+            raise ValueError("output set does not match the batch layout")
+        a = _BatchArgs()
+        a.B, a.N, a.C = B, N, st.columns
+        a.use_color, a.use_height = int(self.use_color), int(self.use_height)
+        a.dataset = DATASETS.index(st.dataset)
+        a.seed, a.counter = self.seed & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF
+        for r in range(B):
+            a.scene[r], a.scan_idx[r] = int(ids[r]), int(ids[r])
+        for k in ("cloud", "offset", "count", "floor"):
+            setattr(a, k, st.dev[k].data_ptr())
+        keep = []  # device memory this call allocates on the current stream and `stream` writes or reads
+        if given is not None:
+            t = torch.from_numpy(given).to(st.device)
+            keep.append(t)
+            a.idx_in = t.data_ptr()
+        if fresh:
+            keep += [pc, si]
+        a.point_clouds, a.scan_idx_out = pc.data_ptr(), si.data_ptr()
+        if keep and stream != current:
+            stream.wait_stream(current)
+        with torch.cuda.device(st.device):
+            _L.check(_L.lib.scene_scan_batch_build(ctypes.byref(a), stream.cuda_stream), "scene_scan_batch_build")
+        for t in keep:
+            t.record_stream(stream)
+        return {"point_clouds": pc, "scan_idx": si}
+
+    def batches(self, batch_size, counter=0):
+        """Every scan of the store in order, batch_size at a time (the last batch may be smaller),
+        batch i with counter + i."""
+        n = len(self.store)
+        for i, start in enumerate(range(0, n, batch_size)):
+            yield self.batch(np.arange(start, min(n, start + batch_size)), counter + i)
+
+    # ---------------------------------------------------------------- the host restatement
+    def host_draws(self, ids, counter=0):
+        ids = self._ids(ids)
+        n = self.store.count[ids]
+        return {"idx": np.stack([sample_indices(self.seed, counter, r, DRAW_STUDENT, n[r], self.num_points)
+                                 for r in range(len(ids))])}
+
+    def host_batch(self, ids, counter=0, draws=None):
+        """numpy restatement of batch(): the same outputs for the same draws (default: the device's)."""
+        ids = self._ids(ids)
+        idx = self._given(ids, draws) if draws is not None and "idx" in draws else self.host_draws(ids, counter)["idx"]
+        st = self.store
+        rows = []
+        for r, s in enumerate(ids):
+            raw = st.clouds[s][idx[r]]
+            cols = [raw[:, 0:3]]
+            if self.use_color:
+                rgb = raw[:, 3:6] - MEAN_COLOR_RGB[st.dataset]  # float32 - float64: double
+                if st.dataset == "scannet":
+                    rgb = rgb / 256.0
+                cols.append(rgb.astype(np.float32))
+            if self.use_height:
+                cols.append((raw[:, 2] - np.float32(st.floor[s]))[:, None])
+            rows.append(np.concatenate(cols, 1).astype(np.float32))
+        return {"point_clouds": np.stack(rows), "scan_idx": ids.astype(np.int64)}
+
+
+def synthetic_clouds(count, num_points, seed=0, dataset="scannet", color=True):
+    """Seeded room-sized stand-in clouds (for tools/ and tests, where no data is at hand)."""
+    g = np.random.default_rng(seed)
+    out = []
+    for _ in range(count):
+        xyz = g.random((num_points, 3)) * [8.0, 6.0, 3.0] - [4.0, 3.0, 0.1]
+        if not color:
+            out.append(xyz.astype(np.float32))
+            continue
+        rgb = g.integers(0, 256, (num_points, 3)).astype(np.float64) if dataset == "scannet" else g.random((num_points, 3))
+        out.append(np.concatenate([xyz, rgb], 1).astype(np.float32))
+    return out

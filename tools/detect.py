@@ -1,0 +1,124 @@
+"""Boxes for scans without labels: the front end of votenet/detect.py.
+
+    python tools/detect.py --checkpoint log/checkpoint.tar --out boxes scans/          # every .npy / .npz
+    python tools/detect.py --checkpoint log/checkpoint.tar --out boxes a.npy b_pc.npz --dataset sunrgbd
+    python tools/detect.py --synthetic 16 --out /tmp/boxes                             # no data, seeded weights
+
+Inputs are (n, 3) xyz or (n, 6) xyz + rgb clouds: `.npy` files, `.npz` files with a `pc` member, or
+a directory of them.  --num_point / --use_color / --no_height / --num_target must be those the
+checkpoint was trained with (tools/train.py); the eval flags are train.py's eval_config_dict keys.
+--out gets one <name>.npz per scan (votenet/detect.py: Detections.save)."""
+import argparse
+import importlib
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIRST_WEIGHT = 'backbone_net.sa1.mlp_module.layer0.conv.weight'
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('inputs', nargs='*', help='cloud files (.npy, .npz with pc) or directories of them')
+    ap.add_argument('--checkpoint', default=None, help="a tools/train.py checkpoint ('model_state_dict')")
+    ap.add_argument('--dataset', default='scannet', choices=('scannet', 'sunrgbd'))
+    ap.add_argument('--num_point', type=int, default=None, help='Point Number [40000 scannet / 20000 sunrgbd]')
+    ap.add_argument('--use_color', action='store_true')
+    ap.add_argument('--no_height', action='store_true')
+    ap.add_argument('--num_target', type=int, default=256, help='Proposal number [256 / 128]')
+    ap.add_argument('--conf_thresh', type=float, default=0.05)
+    ap.add_argument('--nms_iou', type=float, default=0.25)
+    ap.add_argument('--use_iou_for_nms', action='store_true')
+    ap.add_argument('--per_class_proposal', action='store_true')
+    ap.add_argument('--opt_step', type=int, default=0, help='test-time IoU optimisation steps')
+    ap.add_argument('--opt_rate', type=float, default=5e-4)
+    ap.add_argument('--batch_size', type=int, default=8)
+    ap.add_argument('--out', default=None, help='directory for <name>.npz')
+    ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--synthetic', type=int, default=0, metavar='N', help='run on N synthetic scans')
+    ap.add_argument('--seed', type=int, default=0, help='seed of the point sampling')
+    return ap
+
+
+def input_feature_dim(flags):
+    return 3 * int(flags.use_color) + int(not flags.no_height)
+
+
+def check_checkpoint(state, flags):
+    """Refuse a checkpoint whose first SA1 weight does not take 3 + input_feature_dim channels."""
+    if FIRST_WEIGHT not in state:
+        raise SystemExit("the checkpoint has no %s: not a detector of this project" % FIRST_WEIGHT)
+    have = int(state[FIRST_WEIGHT].shape[1]) - 3
+    want = input_feature_dim(flags)
+    if have == want:
+        return
+    fits = {0: '--no_height', 1: '(neither --use_color nor --no_height)', 3: '--use_color --no_height',
+            4: '--use_color'}
+    raise SystemExit("the checkpoint's first SA1 layer takes %d feature channels, the flags give %d; "
+                     "the flags should be: %s" % (have, want, fits.get(have, 'none that this tool has')))
+
+
+def eval_config_dict(cfg, flags):
+    """train.py:263-275"""
+    return {'dataset_config': cfg, 'remove_empty_box': False, 'use_3d_nms': True, 'nms_iou': flags.nms_iou,
+            'use_old_type_nms': False, 'cls_nms': True, 'use_iou_for_nms': flags.use_iou_for_nms,
+            'per_class_proposal': flags.per_class_proposal, 'conf_thresh': flags.conf_thresh}
+
+
+def cloud_files(inputs):
+    paths = []
+    for p in inputs:
+        if os.path.isdir(p):
+            paths += sorted(os.path.join(p, f) for f in os.listdir(p) if f.endswith(('.npy', '.npz')))
+        else:
+            paths.append(p)
+    return paths
+
+
+def main(argv=None):
+    flags = parser().parse_args(argv)
+    if not flags.synthetic and not flags.inputs:
+        raise SystemExit("cloud files or a directory (or --synthetic N)")
+    if not flags.synthetic and flags.checkpoint is None:
+        raise SystemExit("--checkpoint (or --synthetic N, which runs seeded weights)")
+    sys.path.insert(0, ROOT)
+    import torch
+    state = None
+    if flags.checkpoint is not None:
+        state = torch.load(flags.checkpoint, map_location='cpu', weights_only=False)['model_state_dict']
+        check_checkpoint(state, flags)
+    dev = torch.device(flags.device)
+    if dev.type != "cuda":
+        raise SystemExit("tools/detect.py builds its batches on the GPU (--device cuda:N)")
+    importlib.import_module("3dioumatch_amd")
+    V = importlib.import_module("3dioumatch_amd.votenet")
+    SC = importlib.import_module("3dioumatch_amd.votenet.scan_data")
+    I = importlib.import_module("3dioumatch_amd.votenet.inference")
+    step = importlib.import_module("3dioumatch_amd.votenet.step")
+    cfg = V.scannet_config() if flags.dataset == 'scannet' else V.sunrgbd_config()
+    num_point = flags.num_point or (40000 if flags.dataset == 'scannet' else 20000)
+    if flags.synthetic:
+        clouds = SC.synthetic_clouds(flags.synthetic, num_point * 5 // 4, dataset=flags.dataset,
+                                     color=flags.use_color)
+        store = SC.ScanStore(clouds, dev, flags.dataset)
+    else:
+        store = SC.ScanStore.from_files(cloud_files(flags.inputs), dev, flags.dataset)
+    loader = SC.ScanLoader(store, num_point, use_color=flags.use_color, use_height=not flags.no_height,
+                           seed=flags.seed)
+    detector = step.build_detector(cfg, num_proposal=flags.num_target, input_feature_dim=input_feature_dim(flags))
+    if state is not None:
+        detector.load_state_dict(state)
+    detector = detector.to(dev).eval()
+    found = V.detect(I.InferenceEngine(detector), loader, eval_config_dict(cfg, flags),
+                     batch_size=flags.batch_size, opt_step=flags.opt_step, opt_rate=flags.opt_rate)
+    counts = found.planes()["count"]
+    for name, c in zip(found.names, counts):
+        print("%s: %d boxes" % (name, int(c)))
+    if flags.out:
+        found.save(flags.out)
+        print("wrote %d files to %s" % (len(found), flags.out))
+    return found
+
+
+if __name__ == '__main__':
+    main()
