@@ -1,7 +1,8 @@
 // 3dioumatch_amd/csrc/scene_common.h -- what the batch builders share (scene_batch.hip for ScanNet,
-// sunrgbd_batch.hip for SUN RGB-D): the counter-based draw hash and the point sampler.  The host
-// form of every function here is in votenet/scannet_data.py (mix32, draw_key, _element, _feistel,
-// sample_indices); a change here changes every batch of both datasets.
+// sunrgbd_batch.hip for SUN RGB-D, scan_batch.hip for scans without labels): the counter-based draw
+// hash and the point sampler.  The host form of every function here is in votenet/scene_loader.py
+// (mix32, draw_key, _element, _feistel, sample_indices), which all three loaders import; a change
+// here changes every batch of every loader.
 #pragma once
 #include "common.h"
 

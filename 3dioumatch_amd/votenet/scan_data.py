@@ -12,6 +12,8 @@ that small table once -- the only host read of the store's life -- and raises fo
 (the same counter-based draw, so the same rows for the same (seed, counter, ids)), the dataset's
 colour normalisation rounded once from double as read_scene does, and height = z - floor in float32.
 `host_floor` and `ScanLoader.host_batch` restate both in numpy: the CPU path and the yardstick.
+The draw, the bounds check of explicit indices and the launch with its stream discipline are
+scene_loader's, the same functions the labeled loaders use.
 
 One difference from the SUN RGB-D reader: float64 input is cast to float32 on the host BEFORE the
 floor and the colour normalisation, where sunrgbd_data.read_scene works in the file's dtype and
@@ -28,7 +30,8 @@ import os
 import numpy as np
 import torch
 
-from .scannet_data import DRAW_STUDENT, MAX_BATCH, SceneError, sample_indices
+from .scene_loader import (DRAW_STUDENT, MAX_BATCH, SceneError, draw_key, epoch_plan, eval_batches,  # noqa: F401
+                           explicit_indices, feed, launch, sample_indices, scene_offsets, to_device)
 
 DATASETS = ("scannet", "sunrgbd")
 MEAN_COLOR_RGB = {"scannet": np.array([109.8, 97.2, 83.8]),  # scannet_detection_dataset.py:24
@@ -139,7 +142,7 @@ class ScanStore(object):
                                  % (name, c.shape[1], self.names[0], self.columns))
         self.clouds = rows
         self.count = np.array([c.shape[0] for c in rows], np.int32)
-        self.offset = np.concatenate([[0], np.cumsum(self.count, dtype=np.int64)[:-1]]).astype(np.int64)
+        self.offset = scene_offsets(self.count)
         self.device = torch.device(device) if device is not None else None
         self.dev = None
         if self.device is None:
@@ -147,8 +150,8 @@ class ScanStore(object):
             self._refuse(nonfinite)
             self.floor = np.array([host_floor(c[:, 2]) for c in rows], np.float32)
             return
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
-        self.dev = {"cloud": t(np.concatenate(rows)), "offset": t(self.offset), "count": t(self.count)}
+        self.dev = {"cloud": to_device(np.concatenate(rows), self.device),
+                    "offset": to_device(self.offset, self.device), "count": to_device(self.count, self.device)}
         floor, nonfinite = scan_prepare_gpu(self.dev["cloud"], self.dev["offset"], self.dev["count"])
         self.dev["floor"] = floor
         table = torch.stack([floor.double(), nonfinite.double()]).cpu().numpy()  # the one host read
@@ -202,10 +205,7 @@ class ScanLoader(object):
         return ids
 
     def _given(self, ids, draws):
-        v = np.asarray(draws["idx"]).reshape(len(ids), self.num_points)
-        if (v < 0).any() or (v >= self.store.count[ids][:, None]).any():
-            raise ValueError("explicit draws 'idx' out of range of the scans' point counts")
-        return np.ascontiguousarray(v, np.int32)
+        return explicit_indices(draws["idx"], self.store.count[ids], self.num_points, "idx", "scans'")
 
     def allocate(self, B):
         dev = self.store.device
@@ -219,10 +219,6 @@ class ScanLoader(object):
         st = self.store
         if st.dev is None:
             raise RuntimeError("ScanLoader: the store has no device copy (device=None); use host_batch")
-        _L = importlib.import_module("3dioumatch_amd._lib")
-        current = torch.cuda.current_stream(st.device)
-        if stream is None:
-            stream = current
         fresh = out is None
         if fresh:
             out = self.allocate(B)
@@ -239,20 +235,12 @@ class ScanLoader(object):
             a.scene[r], a.scan_idx[r] = int(ids[r]), int(ids[r])
         for k in ("cloud", "offset", "count", "floor"):
             setattr(a, k, st.dev[k].data_ptr())
-        keep = []  # device memory this call allocates on the current stream and `stream` writes or reads
+        keep = [pc, si] if fresh else []
         if given is not None:
-            t = torch.from_numpy(given).to(st.device)
-            keep.append(t)
-            a.idx_in = t.data_ptr()
-        if fresh:
-            keep += [pc, si]
+            keep.append(to_device(given, st.device))
+            a.idx_in = keep[-1].data_ptr()
         a.point_clouds, a.scan_idx_out = pc.data_ptr(), si.data_ptr()
-        if keep and stream != current:
-            stream.wait_stream(current)
-        with torch.cuda.device(st.device):
-            _L.check(_L.lib.scene_scan_batch_build(ctypes.byref(a), stream.cuda_stream), "scene_scan_batch_build")
-        for t in keep:
-            t.record_stream(stream)
+        launch("scene_scan_batch_build", a, keep, stream, st.device)
         return {"point_clouds": pc, "scan_idx": si}
 
     def batches(self, batch_size, counter=0):

@@ -5,7 +5,7 @@ sunrgbd/sunrgbd_ssl_dataset.py:53-181, :221-312) redo per-scene numpy work in ev
 the WHOLE 50k-point scan before they sample it.  Here the preprocessed scans (`<name>_pc.npz`,
 `<name>_bbox.npy`, `<name>_votes.npz`, the sunrgbd_pc_bbox_votes_50k_v1_{train,val} folders) are
 read ONCE into flat device arrays (`SunRgbdScenes`), and a batch is two kernel launches
-(csrc/sunrgbd_batch.hip, include/sunrgbd_hip.h) on the train step's side stream (scannet_data.feed).
+(csrc/sunrgbd_batch.hip, include/sunrgbd_hip.h) on the train step's side stream (scene_loader.feed).
 
 The vote rows are a pure function of the cloud and the boxes (the vote loop of the reference's
 extraction, sunrgbd/sunrgbd_data.py:232-257).  `votes="boxes"` loads a folder that holds only
@@ -17,8 +17,9 @@ What differs from the ScanNet loader: boxes are oriented (heading class / residu
 residuals from 2 x the stored half sizes), the vote labels are carried through the augmentation
 (read from `_votes.npz` by default, computed from the boxes with votes="boxes"), the labeled and the unlabeled dataset normalise colour differently (rgb - 0.5 and
 (rgb - 0.5) / 256: the store keeps the first, the second is applied per row at build time), and the
-detection dataset augments colour per point.  The draw hash, the sampler, epoch_plan, feed and
-eval_batches are scannet_data's.
+detection dataset augments colour per point.  Only that is here: the draw hash, the sampler, the
+store's and the loader's skeleton, the launch, epoch_plan, feed and eval_batches are scene_loader's,
+shared with scannet_data and scan_data and re-exported here.
 
 Keys, dtypes and shapes are those of data.make_batch (pretrain, eval) and data.make_semi_batch
 (semi-supervised) for sunrgbd_config(); semi batches also carry `supervised_mask_host`.
@@ -30,17 +31,15 @@ import os
 import numpy as np
 import torch
 
-from .scannet_data import (SceneError, _element, _stack, draw_key, epoch_plan, eval_batches,  # noqa: F401
-                           feed, rotz, sample_indices)
+from .scene_loader import (DRAW_EMA, DRAW_STUDENT, MAX_BATCH, MAX_NUM_OBJ, SceneError, SceneLoader,  # noqa: F401
+                           SceneStore, _element, _read_list, draw_key, epoch_plan, eval_batches, feed,
+                           launch, rotz, sample_indices, unit_uniform)
 
-MAX_NUM_OBJ = 64   # sunrgbd_detection_dataset.py:40
-MAX_BATCH = 64     # scenes per batch (SUN_MAX_B)
 NUM_CLASS = 10     # model_util_sunrgbd.py:21
 MEAN_COLOR_RGB = np.array([0.5, 0.5, 0.5])  # sunrgbd_detection_dataset.py:41 (colour is in 0~1)
 VOTE_COLS = 10     # mask, three votes
-# draw indices of the hash (sunrgbd_hip.h)
-DRAW_STUDENT, DRAW_EMA, DRAW_FLIP, DRAW_ANGLE, DRAW_SCALE, DRAW_COLOR, DRAW_JITTER, DRAW_DROP = \
-    0, 1, 2, 3, 4, 5, 11, 12
+# draw indices of the hash beyond the two point samples (sunrgbd_hip.h)
+DRAW_FLIP, DRAW_ANGLE, DRAW_SCALE, DRAW_COLOR, DRAW_JITTER, DRAW_DROP = 2, 3, 4, 5, 11, 12
 
 _c_int, _c_uint, _vp = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p
 
@@ -148,11 +147,6 @@ def available_scans(data_dir):
     return sorted(set(os.path.basename(f)[0:6] for f in os.listdir(data_dir)))
 
 
-def _read_list(path):
-    with open(path) as f:
-        return [x.strip() for x in f.read().splitlines() if x.strip()]
-
-
 def labeled_split(data_dir, list_path):
     """The labeled scans of a list file such as sunrgbd_v1_train_0.05.txt
     (sunrgbd_ssl_dataset.py:37-40); listed scans without files are skipped."""
@@ -175,7 +169,7 @@ def val_split(val_dir):
 
 
 # ------------------------------------------------------------------ the resident store
-class SunRgbdScenes(object):
+class SunRgbdScenes(SceneStore):
     """Every scan of `scan_names` read once and packed into flat device arrays with a per-scene
     offset / count table: the cloud (P, C) float32, the vote rows (P, 10) float32, the box table
     (S, 64, 8) float64.  At 50k points a scene is 50k x (4 C + 40) bytes = 2.8 MB with the height
@@ -184,38 +178,13 @@ class SunRgbdScenes(object):
     the boxes.  `device=None` keeps the host copy only (the CPU path)."""
 
     def __init__(self, data_dir, scan_names, device, use_color=False, use_height=True, votes="file"):
-        if not scan_names:
-            raise SceneError("no scans to load from %s" % data_dir)
         self.votes = _votes_mode(votes)
-        self.scan_names = list(scan_names)
         self.use_color, self.use_height = use_color, use_height
-        self.scenes = [read_scene(data_dir, s, use_color, use_height, votes) for s in self.scan_names]
-        self.channels = self.scenes[0]["cloud"].shape[1]
-        self.count = np.array([s["cloud"].shape[0] for s in self.scenes], np.int32)
-        self.offset = np.concatenate([[0], np.cumsum(self.count, dtype=np.int64)[:-1]]).astype(np.int64)
-        self.nbox = np.array([s["boxes"].shape[0] for s in self.scenes], np.int32)
+        SceneStore.__init__(self, data_dir, scan_names,
+                            lambda s: read_scene(data_dir, s, use_color, use_height, votes), device, box_cols=8)
         self.floor = np.array([s["floor"] for s in self.scenes], np.float64)
-        self.boxes = np.zeros((len(self.scenes), MAX_NUM_OBJ, 8))
-        for i, s in enumerate(self.scenes):
-            self.boxes[i, :s["boxes"].shape[0]] = s["boxes"]
-        self.device = torch.device(device) if device is not None else None
-        self.dev = None
-        if self.device is not None:
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
-            self.dev = {
-                "cloud": t(np.concatenate([s["cloud"] for s in self.scenes])),
-                "offset": t(self.offset), "count": t(self.count),
-                "boxes": t(self.boxes), "nbox": t(self.nbox),
-            }
-            if self.votes == "file":
-                self.dev["votes"] = t(np.concatenate([s["votes"] for s in self.scenes]))
-
-    def __len__(self):
-        return len(self.scan_names)
-
-    def index(self, names):
-        where = {s: i for i, s in enumerate(self.scan_names)}
-        return np.array([where[s] for s in names], np.int64)
+        if self.dev is not None and self.votes == "file":
+            self.dev["votes"] = self._flat("votes")
 
     def vote_rows(self):
         """The (P, 10) float32 vote rows of the whole store on the device, in the reference's layout
@@ -358,26 +327,20 @@ def host_scene(scene, idx, u=None, votes=True, boxes="raw", mean_size=None, has_
     return out
 
 
-_BOX_KEYS = ("center_label", "heading_class_label", "heading_residual_label", "size_class_label",
-             "size_residual_label", "sem_cls_label", "box_label_mask")
-_DRAW_KEYS = ("flip_x_axis", "flip_y_axis", "rot_mat", "rot_angle", "scale")
-
-
 def uniforms(seed, counter, row):
     """The three uniforms in [0, 1) of a row: flip, angle, scale (float64, 32 bits)."""
-    return draw_key(seed, counter, row, DRAW_FLIP + np.arange(3)).astype(np.float64) * 2.0 ** -32
+    return unit_uniform(draw_key(seed, counter, row, DRAW_FLIP + np.arange(3)))
 
 
 def color_uniforms(seed, counter, row):
     """The six colour uniforms of a row: brightness rgb, shift rgb."""
-    return draw_key(seed, counter, row, DRAW_COLOR + np.arange(6)).astype(np.float64) * 2.0 ** -32
+    return unit_uniform(draw_key(seed, counter, row, DRAW_COLOR + np.arange(6)))
 
 
 def point_uniforms(seed, counter, row, n):
     """(2, n): the jitter and the drop uniform of every SOURCE point of a row's scene."""
     p = np.arange(n, dtype=np.uint32)
-    return np.stack([_element(draw_key(seed, counter, row, d), p).astype(np.float64) * 2.0 ** -32
-                     for d in (DRAW_JITTER, DRAW_DROP)])
+    return np.stack([unit_uniform(_element(draw_key(seed, counter, row, d), p)) for d in (DRAW_JITTER, DRAW_DROP)])
 
 
 # ------------------------------------------------------------------ batches
@@ -396,231 +359,68 @@ class _Args(ctypes.Structure):  # field order == include/sunrgbd_hip.h SunBatchA
                                     "flip_y_axis", "rot_angle", "rot_mat", "scale")])
 
 
-class SunRgbdLoader(object):
-    """Batches of `num_points` points per scene from `scenes`, with the semantics of the reference's
-    datasets:
+class SunRgbdLoader(SceneLoader):
+    """SceneLoader with the semantics of the reference's SUN RGB-D datasets:
 
       pretrain_batch   SunrgbdDetectionVotesDataset('train', augment=True), with its per-point colour
                        augmentation when the store has colour
       semi_batch       SunrgbdSSLLabeledDataset + SunrgbdSSLUnlabeledDataset rows (augment=True)
       eval_batch       SunrgbdDetectionVotesDataset('val', augment=False)
 
-    `labeled` / `unlabeled`: the scan names of each list (default: every scan of the store); ids
-    passed to the builders index these lists and are what scan_idx reports.  `config.mean_size_arr`
-    (sunrgbd_config(mean_size_arr=...)) gives the size residuals, in float64 as the reference.
-    Device draws are keyed by (seed, counter, batch row, draw index), per-point colour draws
-    additionally by the source point index; `draws=` replaces them with explicit ones:
-    {'idx': (B, N) ints, 'ema_idx': (B, N), 'u': (B, 3) float64 uniforms (flip, angle, scale),
-    'u_color': (B, 6), 'u_point': (B, 2, n_max) jitter and drop by source point}."""
-
-    def __init__(self, scenes, config, num_points, seed=0, labeled=None, unlabeled=None):
-        self.scenes, self.config, self.num_points, self.seed = scenes, config, int(num_points), int(seed)
-        self.mean_size = np.asarray(getattr(config, "mean_size_arr_f64", config.mean_size_arr), np.float64)
-        self.labeled = scenes.index(labeled) if labeled is not None else np.arange(len(scenes))
-        self.unlabeled = scenes.index(unlabeled) if unlabeled is not None else np.arange(len(scenes))
-        self._mean_dev = None
-        if scenes.device is not None:
-            self._mean_dev = torch.from_numpy(np.ascontiguousarray(self.mean_size)).to(scenes.device)
-
-    # ---------------------------------------------------------------- layouts
-    def _layout(self, kind, nl, nu=0, unlabeled_labels=False):
-        N, C = self.num_points, self.scenes.channels
-        B = nl + nu
-        f, i64 = torch.float32, torch.int64
-        shapes = {"point_clouds": ((B, N, C), f), "supervised_mask": ((B,), i64), "scan_idx": ((B,), i64)}
-        vote_rows = nl
-        box_rows = B if (kind == "semi" and unlabeled_labels) else nl
-        shapes.update({"vote_label": ((vote_rows, N, 9), f), "vote_label_mask": ((vote_rows, N), i64),
-                       "center_label": ((box_rows, MAX_NUM_OBJ, 3), f),
-                       "heading_class_label": ((box_rows, MAX_NUM_OBJ), i64),
-                       "heading_residual_label": ((box_rows, MAX_NUM_OBJ), f),
-                       "size_class_label": ((box_rows, MAX_NUM_OBJ), i64),
-                       "size_residual_label": ((box_rows, MAX_NUM_OBJ, 3), f),
-                       "sem_cls_label": ((box_rows, MAX_NUM_OBJ), i64),
-                       "box_label_mask": ((box_rows, MAX_NUM_OBJ), f)})
-        if kind == "semi":
-            shapes.update({"ema_point_clouds": ((B, N, C), f), "flip_x_axis": ((B,), i64),
-                           "flip_y_axis": ((B,), i64), "rot_angle": ((B,), f), "rot_mat": ((B, 3, 3), f),
-                           "scale": ((B, 1, 3), f)})
-        return shapes, vote_rows, box_rows
-
-    def allocate(self, kind, nl, nu=0, unlabeled_labels=False):
-        """One output set (batch tensors; this builder needs no scratch) on the store's device."""
-        shapes, _, _ = self._layout(kind, nl, nu, unlabeled_labels)
-        dev = self.scenes.device
-        return {k: torch.empty(s, dtype=d, device=dev) for k, (s, d) in shapes.items()}, {}
-
-    # ---------------------------------------------------------------- device builds
-    def _rows(self, kind, labeled_ids, unlabeled_ids):
-        lab = np.asarray(labeled_ids, np.int64).reshape(-1)
-        unl = np.asarray(unlabeled_ids if unlabeled_ids is not None else [], np.int64).reshape(-1)
-        if kind == "semi":
-            scene = np.concatenate([self.labeled[lab], self.unlabeled[unl]])
-        else:
-            scene = self.labeled[lab]
-        scan_idx = np.concatenate([lab, unl])
-        if not 1 <= len(scene) <= MAX_BATCH:
-            raise ValueError("a batch holds 1..%d scenes, got %d" % (MAX_BATCH, len(scene)))
-        return scene, scan_idx, len(lab), len(unl)
+    `config`: sunrgbd_config(mean_size_arr=...).  Per-point colour draws are keyed additionally by
+    the source point index.  Explicit draws: {'idx': (B, N) ints, 'ema_idx': (B, N), 'u': (B, 3)
+    float64 uniforms (flip, angle, scale), 'u_color': (B, 6), 'u_point': (B, 2, n_max) jitter and
+    drop by source point}."""
+    _Args, _ENTRY = _Args, "scene_sunrgbd_batch_build"
+    _STORE_KEYS = ("cloud", "offset", "count", "boxes", "nbox")
+    _UNIFORMS = {"u": 3, "u_color": 6}
+    _uniforms = staticmethod(uniforms)
 
     def _color_aug(self, kind):
         return kind == "pretrain" and self.scenes.use_color
 
-    def _build(self, kind, labeled_ids, unlabeled_ids=None, counter=0, unlabeled_labels=False,
-               out=None, draws=None, stream=None):
-        scene, scan_idx, nl, nu = self._rows(kind, labeled_ids, unlabeled_ids)
-        B, N, C = len(scene), self.num_points, self.scenes.channels
-        given = {}
-        n_max = int(self.scenes.count[scene].max())
-        if draws is not None:  # bounds: checked on the host before anything is launched
-            counts = self.scenes.count[scene]
-            for key in ("idx", "ema_idx"):
-                if key in draws:
-                    v = np.asarray(draws[key]).reshape(B, N)
-                    if (v < 0).any() or (v >= counts[:, None]).any():
-                        raise ValueError("explicit draws %r out of range of the scenes' point counts" % key)
-                    given[key] = np.ascontiguousarray(v, np.int32)
-            if "u" in draws:
-                given["u"] = np.ascontiguousarray(np.asarray(draws["u"], np.float64).reshape(B, 3))
-            if "u_color" in draws:
-                given["u_color"] = np.ascontiguousarray(np.asarray(draws["u_color"], np.float64).reshape(B, 6))
-            if "u_point" in draws:
-                v = np.asarray(draws["u_point"], np.float64)
-                if v.ndim != 3 or v.shape[0] != B or v.shape[1] != 2 or v.shape[2] < n_max:
-                    raise ValueError("explicit draws 'u_point' have shape %s, expected (%d, 2, >= %d)"
-                                     % (v.shape, B, n_max))
-                given["u_point"] = np.ascontiguousarray(v)
-        if self.scenes.dev is None:
-            raise RuntimeError("SunRgbdLoader: the store has no device copy (device=None); use host_batch")
-        _L = importlib.import_module("3dioumatch_amd._lib")
-        shapes, vote_rows, box_rows = self._layout(kind, nl, nu, unlabeled_labels)
-        current = torch.cuda.current_stream(self.scenes.device)
-        if stream is None:
-            stream = current
-        fresh = out is None
-        if fresh:
-            out = self.allocate(kind, nl, nu, unlabeled_labels)
-        batch = out[0]
-        for k, (s, d) in shapes.items():
-            if k not in batch or tuple(batch[k].shape) != s or batch[k].dtype != d:
-                raise ValueError("output set does not match the batch layout at %r" % k)
-        a = _Args()
-        a.B, a.N, a.C = B, N, C
-        a.has_height = int(self.scenes.use_height)
-        a.augment = int(kind != "eval")
+    def _given(self, draws, counts):
+        given = SceneLoader._given(self, draws, counts)
+        if "u_point" in draws:
+            v = np.asarray(draws["u_point"], np.float64)
+            B, n_max = len(counts), int(counts.max())
+            if v.ndim != 3 or v.shape[0] != B or v.shape[1] != 2 or v.shape[2] < n_max:
+                raise ValueError("explicit draws 'u_point' have shape %s, expected (%d, 2, >= %d)"
+                                 % (v.shape, B, n_max))
+            given["u_point"] = np.ascontiguousarray(v)
+        return given
+
+    def _fill(self, a, kind, nl, given, scratch):
         a.color_aug = int(self._color_aug(kind))
-        a.ema = int(kind == "semi")
-        a.vote_rows, a.box_rows = vote_rows, box_rows
-        a.box_aug_rows = vote_rows if kind != "eval" else 0
-        a.div256_from = nl if kind == "semi" else B
-        a.NS = self.mean_size.shape[0]
+        a.div256_from = nl if kind == "semi" else a.B
         a.num_heading_bin = int(self.config.num_heading_bin)
-        a.seed, a.counter = self.seed & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF
-        for r in range(B):
-            a.scene[r], a.scan_idx[r], a.supervised[r] = int(scene[r]), int(scan_idx[r]), int(r < nl)
         d = self.scenes.dev
-        for k in ("cloud", "offset", "count", "boxes", "nbox"):
-            setattr(a, k, d[k].data_ptr())
         a.votes = d["votes"].data_ptr() if "votes" in d else None  # NULL: computed from the boxes
-        a.mean_size = self._mean_dev.data_ptr()
-        keep = []  # device memory this call allocates on the current stream and `stream` writes or reads
-        for key, field in (("idx", "idx_in"), ("ema_idx", "ema_idx_in"), ("u", "u_in"),
-                           ("u_color", "u_color_in"), ("u_point", "u_point_in")):
-            if key in given:
-                t = torch.from_numpy(given[key]).to(self.scenes.device)
-                keep.append(t)
-                setattr(a, field, t.data_ptr())
         if "u_point" in given:
             a.u_point_stride = given["u_point"].shape[2]
-        if fresh:
-            keep += list(batch.values())
-        for k in ("point_clouds", "ema_point_clouds", "vote_label", "vote_label_mask", "center_label",
-                  "heading_class_label", "heading_residual_label", "size_class_label",
-                  "size_residual_label", "sem_cls_label", "box_label_mask", "supervised_mask",
-                  "flip_x_axis", "flip_y_axis", "rot_angle", "rot_mat", "scale"):
-            if k in batch:
-                setattr(a, k, batch[k].data_ptr())
-        a.scan_idx_out = batch["scan_idx"].data_ptr()
-        if keep and stream != current:
-            stream.wait_stream(current)  # the blocks just allocated may have been freed by queued work
-        with torch.cuda.device(self.scenes.device):
-            _L.check(_L.lib.scene_sunrgbd_batch_build(ctypes.byref(a), stream.cuda_stream),
-                     "scene_sunrgbd_batch_build")
-        for t in keep:  # not handed to another allocation before `stream` is done with them
-            t.record_stream(stream)
-        result = dict(batch)
-        result["supervised_mask_host"] = tuple([1] * nl + [0] * nu)
-        return result
 
-    def pretrain_batch(self, ids, counter=0, out=None, draws=None, stream=None):
-        return self._build("pretrain", ids, None, counter, out=out, draws=draws, stream=stream)
-
-    def semi_batch(self, labeled_ids, unlabeled_ids, counter=0, unlabeled_labels=False, out=None,
-                   draws=None, stream=None):
-        return self._build("semi", labeled_ids, unlabeled_ids, counter, unlabeled_labels, out=out,
-                           draws=draws, stream=stream)
-
-    def eval_batch(self, ids, counter=0, out=None, draws=None, stream=None):
-        return self._build("eval", ids, None, counter, out=out, draws=draws, stream=stream)
-
-    # ---------------------------------------------------------------- the host restatement
-    def host_draws(self, kind, labeled_ids, unlabeled_ids=None, counter=0):
-        """The device's own draws of a batch, on the host (exact)."""
-        scene, _, nl, nu = self._rows(kind, labeled_ids, unlabeled_ids)
-        B, N = len(scene), self.num_points
-        n = self.scenes.count[scene]
-        draws = {"idx": np.stack([sample_indices(self.seed, counter, r, DRAW_STUDENT, n[r], N) for r in range(B)])}
-        if kind == "semi":
-            draws["ema_idx"] = np.stack([sample_indices(self.seed, counter, r, DRAW_EMA, n[r], N)
-                                         for r in range(B)])
-        if kind != "eval":
-            draws["u"] = np.stack([uniforms(self.seed, counter, r) for r in range(B)])
+    def _extra_host_draws(self, draws, kind, counter, n):
         if self._color_aug(kind):
+            B = len(n)
             draws["u_color"] = np.stack([color_uniforms(self.seed, counter, r) for r in range(B)])
             up = np.zeros((B, 2, int(n.max())))
             for r in range(B):
                 up[r, :, :n[r]] = point_uniforms(self.seed, counter, r, n[r])
             draws["u_point"] = up
-        return draws
 
-    def host_batch(self, kind, labeled_ids, unlabeled_ids=None, counter=0, unlabeled_labels=False,
-                   draws=None):
-        """numpy restatement of pretrain_batch / semi_batch / eval_batch (kind = 'pretrain' | 'semi' |
-        'eval'): the same outputs for the same draws (default: the device's, host_draws)."""
-        scene, scan_idx, nl, nu = self._rows(kind, labeled_ids, unlabeled_ids)
-        if draws is None:
-            draws = self.host_draws(kind, labeled_ids, unlabeled_ids, counter)
-        hh = self.scenes.use_height
-        rows = []
-        for r, s in enumerate(scene):
-            sc = self.scenes.scenes[s]
-            u = np.asarray(draws["u"])[r] if kind != "eval" else None
-            lab = r < nl
-            box = ("aug" if kind != "eval" else "raw") if lab else ("raw" if unlabeled_labels else None)
-            color = None
-            if self._color_aug(kind):
-                up = np.asarray(draws["u_point"])[r]
-                color = (np.asarray(draws["u_color"])[r], up[0], up[1])
-            div256 = kind == "semi" and not lab
-            row = host_scene(sc, np.asarray(draws["idx"][r]), u, votes=lab, boxes=box,
-                             mean_size=self.mean_size, has_height=hh,
-                             num_heading_bin=self.config.num_heading_bin, div256=div256, color=color)
-            if kind == "semi":
-                ema = sc["cloud"][np.asarray(draws["ema_idx"][r])].astype(np.float32)
-                if div256 and self.scenes.use_color:
-                    ema[:, 3:6] = ema[:, 3:6] / 256.0
-                row["ema_point_clouds"] = ema
-            rows.append(row)
-        out = _stack(rows, ["point_clouds"])
-        out.update(_stack(rows[:nl], ("vote_label", "vote_label_mask"), self.num_points))
-        box_rows = nl + nu if (kind == "semi" and unlabeled_labels) else nl
-        out.update(_stack(rows[:box_rows], _BOX_KEYS))
-        if kind == "semi":
-            out.update(_stack(rows, ("ema_point_clouds",) + _DRAW_KEYS))
-            out["rot_angle"] = out["rot_angle"].astype(np.float32)
-        out["supervised_mask"] = np.array([1] * nl + [0] * nu, np.int64)
-        out["scan_idx"] = scan_idx.astype(np.int64)
-        return out
+    def _host_row(self, scene, kind, r, labeled, idx, u, boxes, draws):
+        color = None
+        if self._color_aug(kind):
+            up = np.asarray(draws["u_point"])[r]
+            color = (np.asarray(draws["u_color"])[r], up[0], up[1])
+        return host_scene(scene, idx, u, votes=labeled, boxes=boxes, mean_size=self.mean_size,
+                          has_height=self.scenes.use_height, num_heading_bin=self.config.num_heading_bin,
+                          div256=kind == "semi" and not labeled, color=color)
+
+    def _teacher_colour(self, ema, labeled):
+        if not labeled and self.scenes.use_color:  # the unlabeled dataset's (rgb - 0.5) / 256
+            ema[:, 3:6] = ema[:, 3:6] / 256.0
+        return ema
 
 
 # ------------------------------------------------------------------ synthetic scans

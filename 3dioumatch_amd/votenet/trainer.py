@@ -24,9 +24,9 @@ from .train_meter import tb_name  # noqa: F401  (the loop's naming of a logged k
 
 def loader_epochs(runner, loader, kind, batch_size, unlabeled_batch_size=0, seed=0, rank=0, world=1,
                   unlabeled_labels=False):
-    """epoch_batches for a ScanNetLoader or SunRgbdLoader: epoch -> the batches of scannet_data.epoch_plan,
-    built on the device and prefetched by scannet_data.feed."""
-    from .scannet_data import epoch_plan, feed
+    """epoch_batches for a ScanNetLoader or SunRgbdLoader: epoch -> the batches of scene_loader.epoch_plan,
+    built on the device and prefetched by scene_loader.feed."""
+    from .scene_loader import epoch_plan, feed
 
     def epoch_batches(epoch):
         semi = kind == "semi"

@@ -177,8 +177,13 @@ def test_batch_layout_matches_the_synthetic_batches(tmp_path):
 
 
 def test_shared_pieces_are_the_scannet_loaders():
-    for name in ("sample_indices", "epoch_plan", "feed", "eval_batches", "SceneError", "draw_key"):
+    core = importlib.import_module("3dioumatch_amd.votenet.scene_loader")
+    scan = importlib.import_module("3dioumatch_amd.votenet.scan_data")
+    for name in ("sample_indices", "epoch_plan", "feed", "eval_batches", "SceneError", "draw_key", "launch"):
         assert getattr(SD, name) is getattr(SN, name), name
+        for module in (SD, SN, scan):
+            assert getattr(module, name) is getattr(core, name), (module.__name__, name)
+    assert SD.SunRgbdLoader.build is SN.ScanNetLoader.build is core.SceneLoader.build
 
 
 def test_host_draws_are_a_pure_function_and_keyed_by_source_point(tmp_path):
