@@ -203,6 +203,7 @@ _LOADER_SIGNATURES = {
     # the label-free scan path (include/scan_hip.h)
     "scene_scan_prepare": [_vp, _vp],
     "scene_scan_batch_build": [_vp, _vp],
+    "scene_scan_semi_build": [_vp, _vp],
     "scene_detections_pack": [_vp, _vp],
 }
 

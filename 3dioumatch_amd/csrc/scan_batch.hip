@@ -12,6 +12,15 @@
 //                         draw SB_DRAW_STUDENT of csrc/scene_common.h, as the labeled loaders' eval
 //                         batches), the gathered raw row, the colour normalisation rounded once from
 //                         double and height = z - floor.
+//   scan_semi_kernel      (chunks of 2048 sample slots) x unlabeled rows x (student, teacher): the
+//                         unlabeled rows of a semi-supervised batch from raw clouds.  The slot's row
+//                         as scan_batch_kernel makes it (draws SB_DRAW_STUDENT / SB_DRAW_EMA of the
+//                         row's place in the whole batch, row0 + r), SUN RGB-D's colour / 256 in
+//                         float32, and for the student the dataset's flip / rotate / scale RESTATED
+//                         from scene_points_kernel / sun_points_kernel (float64 per stage, rounded to
+//                         float32 after each; the parity tests hold the copies equal).  All eight
+//                         gathers of a thread are issued before the first is used.  One thread per
+//                         row writes the header scene_boxes_kernel / sun_boxes_kernel write.
 //   scan_pack_kernel      one workgroup per scene: the kept proposals ranked by (objectness
 //                         probability descending, proposal ascending) with pseudo_rank::rank, then
 //                         every plane of the scene's arena rows written in row order -- rows past
@@ -20,6 +29,7 @@
 #include "scene_common.h"
 #include "pseudo_rank.h"
 #include "../../include/scan_hip.h"
+#include "../../include/sunrgbd_hip.h"  // SUN_DRAW_FLIP
 
 namespace {
 
@@ -152,6 +162,130 @@ __global__ void __launch_bounds__(kBlock) scan_batch_kernel(const ScanBatchArgs 
   }
 }
 
+struct SemiAug {
+  int fx, fy;
+  double c, s, angle, scale;
+};
+
+__device__ __forceinline__ double semi_uniform(const ScanSemiArgs &a, int r, int k) {
+  const bool sun = a.dataset == SCAN_DATASET_SUNRGBD;
+  if (a.u_in) return a.u_in[r * (sun ? 3 : 4) + k];
+  const unsigned first = sun ? (unsigned)SUN_DRAW_FLIP : (unsigned)SB_DRAW_FLIP_X;
+  return (double)draw_key(a.seed, a.counter, (unsigned)(a.row0 + r), first + k) * 0x1p-32;
+}
+
+// row_aug of scene_batch.hip and sun_row_aug of sunrgbd_batch.hip, restated
+__device__ __forceinline__ SemiAug semi_row_aug(const ScanSemiArgs &a, int r) {
+  SemiAug g;
+  g.fx = semi_uniform(a, r, 0) > 0.5;
+  if (a.dataset == SCAN_DATASET_SUNRGBD) {
+    g.fy = 0;
+    g.angle = (semi_uniform(a, r, 1) * M_PI) / 3.0 - M_PI / 6.0;  // -30 ~ +30 degree
+    g.scale = semi_uniform(a, r, 2) * 0.3 + 0.85;
+  } else {
+    g.fy = semi_uniform(a, r, 1) > 0.5;
+    g.angle = (semi_uniform(a, r, 2) * M_PI) / 18.0 - M_PI / 36.0;  // -5 ~ +5 degree
+    g.scale = semi_uniform(a, r, 3) * 0.3 + 0.85;
+  }
+  g.c = cos(g.angle);
+  g.s = sin(g.angle);
+  return g;
+}
+
+__global__ void __launch_bounds__(kBlock) scan_semi_kernel(const ScanSemiArgs a) {
+  __shared__ SemiAug s_aug;
+  const int chunk = blockIdx.x, r = blockIdx.y, teacher = blockIdx.z, t = threadIdx.x;
+  const int scene = a.scene[r];
+  const int n = a.count[scene], N = a.N, C = a.C;
+  const bool color = a.use_color != 0, height = a.use_height != 0;
+  const bool sun = a.dataset == SCAN_DATASET_SUNRGBD;
+  const int OC = 3 + (color ? 3 : 0) + (height ? 1 : 0);
+  if (t == 0 && !teacher) {
+    const SemiAug g = semi_row_aug(a, r);
+    s_aug = g;
+    if (chunk == 0) {  // the row's header, as the labeled builders' box kernels write it
+      a.supervised_mask[r] = 0;
+      a.scan_idx_out[r] = a.scan_idx[r];
+      a.flip_x_axis[r] = g.fx;
+      a.flip_y_axis[r] = g.fy;
+      a.rot_angle[r] = (float)g.angle;
+      float *m = a.rot_mat + r * 9;
+      m[0] = (float)g.c; m[1] = (float)-g.s; m[2] = 0.0f;
+      m[3] = (float)g.s; m[4] = (float)g.c;  m[5] = 0.0f;
+      m[6] = 0.0f;       m[7] = 0.0f;        m[8] = 1.0f;
+      const float sc = (float)g.scale;
+      a.scale[r * 3 + 0] = sc;
+      a.scale[r * 3 + 1] = sc;
+      a.scale[r * 3 + 2] = sc;
+    }
+  }
+  __syncthreads();
+  SemiAug g{};
+  if (!teacher) g = s_aug;
+  const float *cloud = a.cloud + a.offset[scene] * C;
+  const float floor = a.floor[scene];
+  const int *given = teacher ? a.ema_idx_in : a.idx_in;
+  const unsigned key = draw_key(a.seed, a.counter, (unsigned)(a.row0 + r),
+                                teacher ? SB_DRAW_EMA : SB_DRAW_STUDENT);
+  const int h = feistel_half_bits(n);
+  float *out = (teacher ? a.ema_point_clouds : a.point_clouds) + (size_t)r * N * OC;
+  // The kernel waits on its gathers and on little else, so a thread issues all eight before it uses
+  // the first.  A slot past N reads point 0 (every scan has one) and stores nothing.
+  int p[kPerThread];
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    const int j = chunk * kChunk + k * kBlock + t;
+    p[k] = j >= N ? 0 : (given ? given[(size_t)r * N + j] : sample_index(key, j, n, N, h));
+  }
+  float raw[kPerThread][6];  // constant indices only: registers, no scratch
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    const float *src = cloud + (size_t)p[k] * C;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) raw[k][c] = (c < 3 || color) ? src[c] : 0.0f;
+  }
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    const int j = chunk * kChunk + k * kBlock + t;
+    if (j >= N) break;
+    float x = raw[k][0], y = raw[k][1], z = raw[k][2];
+    float rgb[3] = {0.0f, 0.0f, 0.0f};
+    if (color) {
+      if (sun) {  // rgb - MEAN_COLOR_RGB, 0.5 each, then the unlabeled dataset's / 256 in float32
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rgb[c] = (float)((double)raw[k][3 + c] - 0.5) * 0.00390625f;
+      } else {  // (rgb - MEAN_COLOR_RGB) / 256.0
+        rgb[0] = (float)(((double)raw[k][3] - 109.8) / 256.0);
+        rgb[1] = (float)(((double)raw[k][4] - 97.2) / 256.0);
+        rgb[2] = (float)(((double)raw[k][5] - 83.8) / 256.0);
+      }
+    }
+    float up = __fsub_rn(z, floor);
+    if (!teacher) {
+      if (g.fx) x = -x;
+      if (g.fy) y = -y;
+      const double dx = x, dy = y, dz = z;
+      const float rx = (float)(dx * g.c + dy * -g.s + dz * 0.0);
+      const float ry = (float)(dx * g.s + dy * g.c + dz * 0.0);
+      const float rz = (float)(dx * 0.0 + dy * 0.0 + dz * 1.0);
+      x = (float)((double)rx * g.scale);
+      y = (float)((double)ry * g.scale);
+      z = (float)((double)rz * g.scale);
+      up = (float)((double)up * g.scale);
+    }
+    float *dst = out + (size_t)j * OC;
+    dst[0] = x;
+    dst[1] = y;
+    dst[2] = z;
+    if (color) {
+      dst[3] = rgb[0];
+      dst[4] = rgb[1];
+      dst[5] = rgb[2];
+    }
+    if (height) dst[OC - 1] = up;
+  }
+}
+
 __global__ void __launch_bounds__(kBlock) scan_pack_kernel(const ScanPackArgs a) {
   __shared__ float s_key[SCAN_MAX_K];
   __shared__ int s_src[SCAN_MAX_K];
@@ -217,6 +351,19 @@ PN2_API int scene_scan_batch_build(const ScanBatchArgs *args, void *stream) {
       (args->dataset != SCAN_DATASET_SCANNET && args->dataset != SCAN_DATASET_SUNRGBD))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(scan_batch_kernel, dim3(pn2_ceil_div(args->N, kChunk), args->B), dim3(kBlock), 0,
+                     (hipStream_t)stream, *args);
+  return (int)hipGetLastError();
+}
+
+PN2_API int scene_scan_semi_build(const ScanSemiArgs *args, void *stream) {
+  if (!args || args->B < 1 || args->B > SB_MAX_B || args->row0 < 0 || args->row0 + args->B > SB_MAX_B ||
+      args->N < 1 || (args->C != 3 && args->C != 6) || (args->use_color && args->C != 6) ||
+      (args->dataset != SCAN_DATASET_SCANNET && args->dataset != SCAN_DATASET_SUNRGBD) || !args->cloud ||
+      !args->offset || !args->count || !args->floor || !args->point_clouds || !args->ema_point_clouds ||
+      !args->flip_x_axis || !args->flip_y_axis || !args->rot_angle || !args->rot_mat || !args->scale ||
+      !args->supervised_mask || !args->scan_idx_out)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(scan_semi_kernel, dim3(pn2_ceil_div(args->N, kChunk), args->B, 2), dim3(kBlock), 0,
                      (hipStream_t)stream, *args);
   return (int)hipGetLastError();
 }

@@ -15,6 +15,12 @@ colour normalisation rounded once from double as read_scene does, and height = z
 The draw, the bounds check of explicit indices and the launch with its stream discipline are
 scene_loader's, the same functions the labeled loaders use.
 
+`ScanLoader.semi_rows` is one launch too (scene_scan_semi_build): the UNLABELED rows of a
+semi-supervised batch -- the student's sample through the dataset's flip / rotation / scale in the
+labeled kernels' arithmetic, the teacher's sample, the row header -- keyed by the rows' place behind
+the batch's labeled rows (`row0`), so that scene_loader.SceneLoader(unlabeled_scans=store) can put them
+behind its own labeled rows; `host_semi_rows` is the numpy restatement.
+
 One difference from the SUN RGB-D reader: float64 input is cast to float32 on the host BEFORE the
 floor and the colour normalisation, where sunrgbd_data.read_scene works in the file's dtype and
 rounds afterwards.  For float32 files (and every ScanNet `_vert.npy`, which the ScanNet reader casts
@@ -30,8 +36,9 @@ import os
 import numpy as np
 import torch
 
-from .scene_loader import (DRAW_STUDENT, MAX_BATCH, SceneError, draw_key, epoch_plan, eval_batches,  # noqa: F401
-                           explicit_indices, feed, launch, sample_indices, scene_offsets, to_device)
+from .scene_loader import (DRAW_EMA, DRAW_STUDENT, MAX_BATCH, SceneError, draw_key, epoch_plan,  # noqa: F401
+                           eval_batches, explicit_indices, feed, launch, rotz, sample_indices, scene_offsets,
+                           to_device, unit_uniform)
 
 DATASETS = ("scannet", "sunrgbd")
 MEAN_COLOR_RGB = {"scannet": np.array([109.8, 97.2, 83.8]),  # scannet_detection_dataset.py:24
@@ -71,6 +78,29 @@ class _BatchArgs(ctypes.Structure):  # field order == include/scan_hip.h ScanBat
                 [("seed", _c_uint), ("counter", _c_uint)] +
                 [(n, _c_int * MAX_BATCH) for n in ("scene", "scan_idx")] +
                 [(n, _vp) for n in ("cloud", "offset", "count", "floor", "idx_in", "point_clouds", "scan_idx_out")])
+
+
+class _SemiArgs(ctypes.Structure):  # field order == include/scan_hip.h ScanSemiArgs
+    _fields_ = ([(n, _c_int) for n in ("B", "N", "C", "use_color", "use_height", "dataset", "row0")] +
+                [("seed", _c_uint), ("counter", _c_uint)] +
+                [(n, _c_int * MAX_BATCH) for n in ("scene", "scan_idx")] +
+                [(n, _vp) for n in ("cloud", "offset", "count", "floor", "idx_in", "ema_idx_in", "u_in",
+                                    "point_clouds", "ema_point_clouds", "flip_x_axis", "flip_y_axis",
+                                    "rot_angle", "rot_mat", "scale", "supervised_mask", "scan_idx_out")])
+
+
+DRAW_UNIFORM = 2  # draw index of the first augmentation uniform of a row (scene_hip.h, sunrgbd_hip.h)
+UNIFORMS = {"scannet": 4,   # flip x, flip y, angle, scale
+            "sunrgbd": 3}   # flip, angle, scale
+
+
+def augmentation(dataset, u):
+    """A row's uniforms -> (flip_x, flip_y, angle, scale) with the formulas of the dataset's unlabeled
+    loader (scannet_ssl_dataset.py:258-280: +-5 degrees; sunrgbd_ssl_dataset.py:259-281: no y flip,
+    +-30 degrees)."""
+    if dataset == "scannet":
+        return int(u[0] > 0.5), int(u[1] > 0.5), (u[2] * np.pi / 18) - np.pi / 36, u[3] * 0.3 + 0.85
+    return int(u[0] > 0.5), 0, (u[1] * np.pi / 3) - np.pi / 6, u[2] * 0.3 + 0.85
 
 
 def _load_cloud(path):
@@ -261,20 +291,149 @@ class ScanLoader(object):
         """numpy restatement of batch(): the same outputs for the same draws (default: the device's)."""
         ids = self._ids(ids)
         idx = self._given(ids, draws) if draws is not None and "idx" in draws else self.host_draws(ids, counter)["idx"]
-        st = self.store
-        rows = []
-        for r, s in enumerate(ids):
-            raw = st.clouds[s][idx[r]]
-            cols = [raw[:, 0:3]]
-            if self.use_color:
-                rgb = raw[:, 3:6] - MEAN_COLOR_RGB[st.dataset]  # float32 - float64: double
-                if st.dataset == "scannet":
-                    rgb = rgb / 256.0
-                cols.append(rgb.astype(np.float32))
-            if self.use_height:
-                cols.append((raw[:, 2] - np.float32(st.floor[s]))[:, None])
-            rows.append(np.concatenate(cols, 1).astype(np.float32))
+        rows = [self._host_rows(s, idx[r]) for r, s in enumerate(ids)]
         return {"point_clouds": np.stack(rows), "scan_idx": ids.astype(np.int64)}
+
+    def _host_rows(self, s, idx):
+        """The points `idx` of scan s as eval rows: xyz, [normalised rgb], [z - floor]."""
+        st = self.store
+        raw = st.clouds[s][idx]
+        cols = [raw[:, 0:3]]
+        if self.use_color:
+            rgb = raw[:, 3:6] - MEAN_COLOR_RGB[st.dataset]  # float32 - float64: double
+            if st.dataset == "scannet":
+                rgb = rgb / 256.0
+            cols.append(rgb.astype(np.float32))
+        if self.use_height:
+            cols.append((raw[:, 2] - np.float32(st.floor[s]))[:, None])
+        return np.concatenate(cols, 1).astype(np.float32)
+
+    # ---------------------------------------------------------------- unlabeled rows of a semi batch
+    _SEMI_KEYS = ("point_clouds", "ema_point_clouds", "flip_x_axis", "flip_y_axis", "rot_angle", "rot_mat",
+                  "scale", "supervised_mask", "scan_idx")
+
+    def _semi_layout(self, B):
+        N, C = self.num_points, self.channels
+        f, i64 = torch.float32, torch.int64
+        return {"point_clouds": ((B, N, C), f), "ema_point_clouds": ((B, N, C), f), "flip_x_axis": ((B,), i64),
+                "flip_y_axis": ((B,), i64), "rot_angle": ((B,), f), "rot_mat": ((B, 3, 3), f),
+                "scale": ((B, 1, 3), f), "supervised_mask": ((B,), i64), "scan_idx": ((B,), i64)}
+
+    def allocate_semi(self, B):
+        dev = self.store.device
+        return {k: torch.empty(s, dtype=d, device=dev) for k, (s, d) in self._semi_layout(B).items()}
+
+    def _row0(self, row0, B):
+        row0 = int(row0)
+        if row0 < 0 or row0 + B > MAX_BATCH:
+            raise ValueError("row0 = %d: %d rows behind it pass the batch limit of %d" % (row0, B, MAX_BATCH))
+        return row0
+
+    def _given_semi(self, ids, draws):
+        """The explicit draws of semi_rows as the contiguous arrays the device reads."""
+        given = {}
+        for key in ("idx", "ema_idx"):
+            if key in draws:
+                given[key] = explicit_indices(draws[key], self.store.count[ids], self.num_points, key, "scans'")
+        if "u" in draws:
+            given["u"] = np.ascontiguousarray(
+                np.asarray(draws["u"], np.float64).reshape(len(ids), UNIFORMS[self.store.dataset]))
+        return given
+
+    def semi_rows(self, ids, counter=0, row0=0, out=None, draws=None, stream=None):
+        """The UNLABELED rows of a semi-supervised batch for the scans `ids`, one launch
+        (scene_scan_semi_build): {'point_clouds' (the student's sample, augmented), 'ema_point_clouds'
+        (the teacher's, not augmented), 'flip_x_axis', 'flip_y_axis', 'rot_angle', 'rot_mat', 'scale',
+        'supervised_mask' (zeros), 'scan_idx'}, the rows the labeled loaders' semi_batch gives behind
+        its `row0` labeled rows: the draws of row r are keyed by batch row row0 + r.  `out`: a dict of
+        these tensors with len(ids) rows (trailing-row views of a batch's tensors will do).  Explicit
+        draws: 'idx', 'ema_idx' (B, N) and 'u' (B, 4) for ScanNet, (B, 3) for SUN RGB-D."""
+        return self._semi_launch(ids, counter, row0, out, draws, stream, [])
+
+    def _semi_launch(self, ids, counter, row0, out, draws, stream, keep):
+        """semi_rows; `keep`: more memory of the caller's that scene_loader.launch is to treat as
+        allocated for this call (the rest of a freshly allocated mixed batch)."""
+        ids = self._ids(ids)
+        B, N = len(ids), self.num_points
+        row0 = self._row0(row0, B)
+        given = self._given_semi(ids, draws) if draws is not None else {}
+        st = self.store
+        if st.dev is None:
+            raise RuntimeError("ScanLoader: the store has no device copy (device=None); use host_semi_rows")
+        keep = list(keep)
+        if out is None:
+            out = self.allocate_semi(B)
+            keep += list(out.values())
+        for k, (s, d) in self._semi_layout(B).items():
+            if k not in out or tuple(out[k].shape) != s or out[k].dtype != d or not out[k].is_contiguous() or \
+                    out[k].device != st.device:
+                raise ValueError("output set does not match the rows' layout at %r" % k)
+        a = _SemiArgs()
+        a.B, a.N, a.C, a.row0 = B, N, st.columns, row0
+        a.use_color, a.use_height = int(self.use_color), int(self.use_height)
+        a.dataset = DATASETS.index(st.dataset)
+        a.seed, a.counter = self.seed & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF
+        for r in range(B):
+            a.scene[r], a.scan_idx[r] = int(ids[r]), int(ids[r])
+        for k in ("cloud", "offset", "count", "floor"):
+            setattr(a, k, st.dev[k].data_ptr())
+        for key, v in given.items():
+            keep.append(to_device(v, st.device))
+            setattr(a, key + "_in", keep[-1].data_ptr())
+        for k in self._SEMI_KEYS:
+            setattr(a, "scan_idx_out" if k == "scan_idx" else k, out[k].data_ptr())
+        launch("scene_scan_semi_build", a, keep, stream, st.device)
+        return {k: out[k] for k in self._SEMI_KEYS}
+
+    def host_semi_draws(self, ids, counter=0, row0=0):
+        """The device's own draws of semi_rows, on the host (exact)."""
+        ids = self._ids(ids)
+        row0 = self._row0(row0, len(ids))
+        n, N = self.store.count[ids], self.num_points
+        rows = range(len(ids))
+        return {"idx": np.stack([sample_indices(self.seed, counter, row0 + r, DRAW_STUDENT, n[r], N) for r in rows]),
+                "ema_idx": np.stack([sample_indices(self.seed, counter, row0 + r, DRAW_EMA, n[r], N) for r in rows]),
+                "u": np.stack([unit_uniform(draw_key(self.seed, counter, row0 + r, DRAW_UNIFORM +
+                                                     np.arange(UNIFORMS[self.store.dataset]))) for r in rows])}
+
+    def host_semi_rows(self, ids, counter=0, row0=0, draws=None):
+        """numpy restatement of semi_rows(), in the arithmetic of the reference's unlabeled datasets
+        (scannet_ssl_dataset.py:224-320, sunrgbd_ssl_dataset.py:221-312; a float32 cloud, float64
+        rotation matrix and scale): the same outputs for the same draws (default, and for every key
+        `draws` leaves out: the device's)."""
+        ids = self._ids(ids)
+        d = self.host_semi_draws(ids, counter, row0)
+        if draws is not None:
+            d.update(self._given_semi(ids, draws))
+        sun_colour = self.store.dataset == "sunrgbd" and self.use_color
+        out = {k: [] for k in self._SEMI_KEYS[:7]}
+        for r, s in enumerate(ids):
+            pc, ema = self._host_rows(s, d["idx"][r]), self._host_rows(s, d["ema_idx"][r])
+            if sun_colour:  # the unlabeled dataset's second division (sunrgbd_ssl_dataset.py:240)
+                pc[:, 3:6] = pc[:, 3:6] / 256.0
+                ema[:, 3:6] = ema[:, 3:6] / 256.0
+            fx, fy, angle, scale = augmentation(self.store.dataset, d["u"][r])
+            if fx:
+                pc[:, 0] = -1 * pc[:, 0]
+            if fy:
+                pc[:, 1] = -1 * pc[:, 1]
+            rot = rotz(angle)
+            pc[:, 0:3] = np.dot(pc[:, 0:3], np.transpose(rot))
+            scale_ratio = np.expand_dims(np.tile(scale, 3), 0)
+            pc[:, 0:3] *= scale_ratio
+            if self.use_height:
+                pc[:, -1] *= scale_ratio[0, 0]
+            for k, v in (("point_clouds", pc), ("ema_point_clouds", ema), ("flip_x_axis", fx), ("flip_y_axis", fy),
+                         ("rot_angle", np.float32(angle)), ("rot_mat", rot.astype(np.float32)),
+                         ("scale", scale_ratio.astype(np.float32))):
+                out[k].append(v)
+        out = {k: np.stack(v) for k, v in out.items()}
+        for k in ("flip_x_axis", "flip_y_axis"):
+            out[k] = out[k].astype(np.int64)
+        out["rot_angle"] = out["rot_angle"].astype(np.float32)
+        out["supervised_mask"] = np.zeros(len(ids), np.int64)
+        out["scan_idx"] = ids.astype(np.int64)
+        return out
 
 
 def synthetic_clouds(count, num_points, seed=0, dataset="scannet", color=True):

@@ -257,7 +257,7 @@ class ScanNetLoader(SceneLoader):
 
     `config`: scannet_config(mean_size_arr=...).  Explicit draws: {'idx': (B, N) ints, 'ema_idx':
     (B, N), 'u': (B, 4) float64 uniforms}."""
-    _Args, _ENTRY = _Args, "scene_batch_build"
+    _Args, _ENTRY, _DATASET = _Args, "scene_batch_build", "scannet"
     _STORE_KEYS = ("cloud", "inst", "sem", "offset", "count", "ninst", "boxes", "nbox")
     _UNIFORMS = {"u": 4}
     _uniforms = staticmethod(uniforms)

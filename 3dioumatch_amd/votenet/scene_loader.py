@@ -5,7 +5,10 @@ scan_data (scans without labels).  Nothing here knows a dataset.
             form): every random quantity of a batch is a pure function of (seed, counter, row, draw)
   stores    `SceneStore`: the per-scene offset / count table, the padded box table, the upload
   loaders   `SceneLoader`: batch layout, explicit draws, the args record, the host restatement's
-            skeleton; a dataset's loader overrides the few methods that are its own
+            skeleton; a dataset's loader overrides the few methods that are its own.  With
+            `unlabeled_scans=` (a scan_data.ScanStore) the unlabeled rows of a semi batch come from
+            scans without labels: the dataset's build for the leading rows, ScanLoader.semi_rows for
+            the trailing ones
   launch    the ONE place that decides which stream a build's memory is recorded on
   epochs    epoch_plan, feed (builds on the train step's side stream), eval_batches
 
@@ -203,6 +206,10 @@ def _stack(rows, keys, num_points=0):
 
 
 # ------------------------------------------------------------------ batches
+def _sizes(labeled_ids, unlabeled_ids):
+    return np.size(labeled_ids), 0 if unlabeled_ids is None else np.size(unlabeled_ids)
+
+
 class SceneLoader(object):
     """Batches of `num_points` points per scene from the store `scenes`:
 
@@ -220,20 +227,71 @@ class SceneLoader(object):
     (explicit per-row uniforms: key -> how many; draw `key` goes to the field `key_in`) and
     `_uniforms` (seed, counter, row -> the row's augmentation uniforms), and overrides `_host_row`
     and, where it has something to add, `_scratch`, `_given`, `_fill`, `_extra_host_draws` and
-    `_teacher_colour`."""
-    _UNIFORMS = {}
+    `_teacher_colour`.
 
-    def __init__(self, scenes, config, num_points, seed=0, labeled=None, unlabeled=None):
+    `unlabeled_scans`: a scan_data.ScanStore of the loader's `_DATASET` on the scenes' device.  The
+    unlabeled list is then that store -- scans WITHOUT label files -- and `unlabeled_ids` index it: a
+    semi batch is the dataset's own build of the labeled rows into the leading rows of the batch's
+    tensors and ScanLoader.semi_rows into the trailing ones, on one stream.  For scans stored as
+    float32 files the batch is bit-equal to the one this loader gives with the same scans in its
+    labeled store.  Such a batch has no labels for its unlabeled rows (unlabeled_labels=True raises)
+    and needs a labeled row in front."""
+    _UNIFORMS = {}
+    _DATASET = None
+
+    def __init__(self, scenes, config, num_points, seed=0, labeled=None, unlabeled=None, unlabeled_scans=None):
         self.scenes, self.config, self.num_points, self.seed = scenes, config, int(num_points), int(seed)
         self.mean_size = np.asarray(getattr(config, "mean_size_arr_f64", config.mean_size_arr), np.float64)
         self.labeled = scenes.index(labeled) if labeled is not None else np.arange(len(scenes))
-        self.unlabeled = scenes.index(unlabeled) if unlabeled is not None else np.arange(len(scenes))
+        self.unlabeled_scans = self._scan_rows = None
+        if unlabeled_scans is not None:
+            if unlabeled is not None:
+                raise ValueError("unlabeled_scans is the unlabeled list: give it or `unlabeled`, not both")
+            self._adopt(unlabeled_scans)
+            self.unlabeled = np.arange(len(unlabeled_scans))
+        else:
+            self.unlabeled = scenes.index(unlabeled) if unlabeled is not None else np.arange(len(scenes))
         self._mean_dev = None
         if scenes.device is not None:
             self._mean_dev = to_device(self.mean_size, scenes.device)
 
+    def _adopt(self, store):
+        scan_data = importlib.import_module(__package__ + ".scan_data")  # (it imports this module)
+        if store.dataset != self._DATASET:
+            raise ValueError("unlabeled_scans holds %r scans, this is a %r loader" % (store.dataset, self._DATASET))
+        if store.device != self.scenes.device:
+            raise ValueError("unlabeled_scans is on %s, the labeled scenes are on %s"
+                             % (store.device, self.scenes.device))
+        if self.scenes.use_color and store.columns != 6:
+            raise ValueError("the labeled scenes use colour, unlabeled_scans holds 3-column clouds (xyz only)")
+        self.unlabeled_scans = store
+        self._scan_rows = scan_data.ScanLoader(store, self.num_points, use_color=self.scenes.use_color,
+                                               use_height=self.scenes.use_height, seed=self.seed)
+
+    def _mixed(self, kind, nl, nu, unlabeled_labels):
+        """Does a batch take its unlabeled rows from `unlabeled_scans`?  Refuses what such a batch
+        cannot be."""
+        if kind != "semi" or self.unlabeled_scans is None:
+            return False
+        if unlabeled_labels:
+            raise ValueError("unlabeled_labels=True: the scans of unlabeled_scans have no labels to give")
+        if nl == 0:
+            raise ValueError("a semi batch over unlabeled_scans needs at least one labeled row")
+        if nl + nu > MAX_BATCH:
+            raise ValueError("a batch holds 1..%d scenes, got %d" % (MAX_BATCH, nl + nu))
+        return nu > 0
+
+    @staticmethod
+    def _split_draws(draws, nl):
+        """Explicit draws of a mixed batch -> (the labeled rows', the unlabeled rows')."""
+        if draws is None:
+            return None, None
+        lab = {k: np.asarray(v)[:nl] for k, v in draws.items()}
+        return lab, {k: np.asarray(draws[k])[nl:] for k in ("idx", "ema_idx", "u") if k in draws}
+
     # ---------------------------------------------------------------- layouts
     def _layout(self, kind, nl, nu=0, unlabeled_labels=False):
+        self._mixed(kind, nl, nu, unlabeled_labels)
         N, C = self.num_points, self.scenes.channels
         B = nl + nu
         f, i64 = torch.float32, torch.int64
@@ -294,6 +352,8 @@ class SceneLoader(object):
               out=None, draws=None, stream=None):
         """One batch of `kind` ('pretrain' | 'semi' | 'eval') on the device, into the output set `out`
         (None: freshly allocated) on `stream` (None: the current stream)."""
+        if self._mixed(kind, *_sizes(labeled_ids, unlabeled_ids), unlabeled_labels):
+            return self._build_mixed(labeled_ids, unlabeled_ids, counter, out, draws, stream)
         scene, scan_idx, nl, nu = self._rows(kind, labeled_ids, unlabeled_ids)
         B, N = len(scene), self.num_points
         given = self._given(draws, self.scenes.count[scene]) if draws is not None else {}
@@ -339,6 +399,34 @@ class SceneLoader(object):
 
     _build = build  # the loaders' GPU tests call the builder by this name
 
+    def _build_mixed(self, labeled_ids, unlabeled_ids, counter, out, draws, stream):
+        """A semi batch whose unlabeled rows come from `unlabeled_scans`: ScanLoader's launch into the
+        trailing rows, then this dataset's own launches for the leading ones, on the same stream."""
+        lab = np.asarray(labeled_ids, np.int64).reshape(-1)
+        unl = np.asarray(unlabeled_ids, np.int64).reshape(-1)
+        nl, nu = len(lab), len(unl)
+        if self.scenes.dev is None:
+            raise RuntimeError("%s: the store has no device copy (device=None); use host_batch"
+                               % type(self).__name__)
+        shapes, _, _ = self._layout("semi", nl, nu)
+        fresh = out is None
+        if fresh:
+            out = self.allocate("semi", nl, nu)
+        batch, scratch = out
+        for k, (s, d) in shapes.items():
+            if k not in batch or tuple(batch[k].shape) != s or batch[k].dtype != d:
+                raise ValueError("output set does not match the batch layout at %r" % k)
+        lab_draws, unl_draws = self._split_draws(draws, nl)
+        tail = {k: batch[k][nl:] for k in self._scan_rows._SEMI_KEYS}
+        keep = list(batch.values()) + list(scratch.values()) if fresh else []
+        self._scan_rows._semi_launch(unl, counter, nl, tail, unl_draws, stream, keep)
+        # the leading rows of every tensor: the labeled build sees a batch of nl rows, keyed by row
+        self.build("semi", lab, None, counter, out=({k: batch[k][:nl] for k in shapes}, scratch),
+                   draws=lab_draws, stream=stream)
+        result = dict(batch)
+        result["supervised_mask_host"] = tuple([1] * nl + [0] * nu)
+        return result
+
     def pretrain_batch(self, ids, counter=0, out=None, draws=None, stream=None):
         return self.build("pretrain", ids, None, counter, out=out, draws=draws, stream=stream)
 
@@ -356,6 +444,10 @@ class SceneLoader(object):
 
     def host_draws(self, kind, labeled_ids, unlabeled_ids=None, counter=0):
         """The device's own draws of a batch, on the host (exact)."""
+        if self._mixed(kind, *_sizes(labeled_ids, unlabeled_ids), False):
+            draws = self.host_draws(kind, labeled_ids, None, counter)
+            tail = self._scan_rows.host_semi_draws(unlabeled_ids, counter, np.size(labeled_ids))
+            return {k: np.concatenate([draws[k], tail[k]]) for k in ("idx", "ema_idx", "u")}
         scene, _, nl, nu = self._rows(kind, labeled_ids, unlabeled_ids)
         B, N = len(scene), self.num_points
         n = self.scenes.count[scene]
@@ -380,6 +472,13 @@ class SceneLoader(object):
                    draws=None):
         """numpy restatement of pretrain_batch / semi_batch / eval_batch (kind = 'pretrain' | 'semi' |
         'eval'): the same outputs for the same draws (default: the device's, host_draws)."""
+        if self._mixed(kind, *_sizes(labeled_ids, unlabeled_ids), unlabeled_labels):
+            lab_draws, unl_draws = self._split_draws(draws, np.size(labeled_ids))
+            out = self.host_batch(kind, labeled_ids, None, counter, draws=lab_draws)
+            tail = self._scan_rows.host_semi_rows(unlabeled_ids, counter, np.size(labeled_ids), unl_draws)
+            for k, v in tail.items():
+                out[k] = np.concatenate([out[k], v])
+            return out
         scene, scan_idx, nl, nu = self._rows(kind, labeled_ids, unlabeled_ids)
         if draws is None:
             draws = self.host_draws(kind, labeled_ids, unlabeled_ids, counter)

@@ -371,7 +371,7 @@ class SunRgbdLoader(SceneLoader):
     the source point index.  Explicit draws: {'idx': (B, N) ints, 'ema_idx': (B, N), 'u': (B, 3)
     float64 uniforms (flip, angle, scale), 'u_color': (B, 6), 'u_point': (B, 2, n_max) jitter and
     drop by source point}."""
-    _Args, _ENTRY = _Args, "scene_sunrgbd_batch_build"
+    _Args, _ENTRY, _DATASET = _Args, "scene_sunrgbd_batch_build", "sunrgbd"
     _STORE_KEYS = ("cloud", "offset", "count", "boxes", "nbox")
     _UNIFORMS = {"u": 3, "u_color": 6}
     _uniforms = staticmethod(uniforms)

@@ -66,6 +66,50 @@ typedef struct ScanBatchArgs {
  * ScanNet, rgb - 0.5 for SUN RGB-D) and height = z - floor in float32. */
 int scene_scan_batch_build(const ScanBatchArgs *args, void *stream);
 
+typedef struct ScanSemiArgs {
+  int B;              /* unlabeled rows built here, 1..SB_MAX_B */
+  int N;              /* points per row */
+  int C;              /* columns of the raw rows: 3 or 6 */
+  int use_color;      /* output channels 3..5: normalised rgb (needs C == 6) */
+  int use_height;     /* last output channel: z - floor, scaled with the student's cloud */
+  int dataset;        /* SCAN_DATASET_*: colour normalisation and augmentation */
+  int row0;           /* labeled rows in front: row r here is batch row row0 + r, which keys its draws */
+  unsigned seed, counter;
+  int scene[SB_MAX_B];    /* store row of each row */
+  int scan_idx[SB_MAX_B]; /* written to scan_idx_out */
+  const float *cloud;      /* (P, C) */
+  const long long *offset; /* (S,) */
+  const int *count;        /* (S,) */
+  const float *floor;      /* (S,) scene_scan_prepare's */
+  /* explicit draws (parity tests), indexed by r; NULL: drawn on the device */
+  const int *idx_in;       /* (B, N) student sample in [0, count) */
+  const int *ema_idx_in;   /* (B, N) teacher sample */
+  const double *u_in;      /* (B, 4) ScanNet: flip x, flip y, angle, scale; (B, 3) SUN RGB-D: flip, angle, scale */
+  /* outputs: row r of each is batch row row0 + r (the trailing rows of the batch's tensors) */
+  float *point_clouds;     /* (B, N, 3 + 3 use_color + use_height) student sample, augmented */
+  float *ema_point_clouds; /* (B, N, same) teacher sample, not augmented */
+  long long *flip_x_axis, *flip_y_axis; /* (B,) */
+  float *rot_angle;        /* (B,) */
+  float *rot_mat;          /* (B, 3, 3) */
+  float *scale;            /* (B, 1, 3) */
+  long long *supervised_mask; /* (B,) out: 0 */
+  long long *scan_idx_out; /* (B,) out */
+} ScanSemiArgs;
+
+/* One launch, (chunks of 2048 slots) x rows x (student, teacher): the UNLABELED rows of a
+ * semi-supervised batch (scannet/scannet_ssl_dataset.py:224-320, sunrgbd/sunrgbd_ssl_dataset.py:
+ * 221-312) from raw clouds.  Each slot gathers its raw row (draws SB_DRAW_STUDENT / SB_DRAW_EMA of
+ * batch row row0 + r), normalises colour as scene_scan_batch_build does -- SUN RGB-D divides by 256
+ * once more in float32, as its unlabeled dataset does -- and takes height = z - floor; the student
+ * sample then goes through the dataset's augmentation in scene_batch_build's /
+ * scene_sunrgbd_batch_build's own arithmetic (float64 per stage, rounded to float32 after each), so
+ * the rows are bit-equal to the unlabeled rows those builders give for the same scans as float32
+ * files.  One thread per row writes the row's header as their box kernels do.
+ * hipErrorInvalidValue, without a launch: NULL args, B outside 1..SB_MAX_B, row0 < 0 or row0 + B >
+ * SB_MAX_B, N < 1, C not 3 or 6, use_color with C == 3, an unknown dataset, a NULL store or output
+ * pointer. */
+int scene_scan_semi_build(const ScanSemiArgs *args, void *stream);
+
 typedef struct ScanPackArgs {
   int B;                    /* scenes of the batch */
   int K;                    /* proposals per scene, <= SCAN_MAX_K; also the rows per scene (cap) */

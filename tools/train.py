@@ -4,12 +4,15 @@
     python tools/train.py --stage pretrain --data_dir scans --meta_dir meta --log_dir log
     python tools/train.py --stage semi --synthetic 24 --max_epoch 4 --eval_interval 2 --log_dir /tmp/run
     python tools/train.py --stage semi --synthetic 24 --max_epoch 6 --resume --log_dir /tmp/run
+    python tools/train.py --stage semi --data_dir scans --meta_dir meta --unlabeled_scans captures
 
 --stage pretrain is pretrain.py (labeled scenes, no teacher), --stage semi is train.py (labeled +
 unlabeled scenes, EMA teacher).  --synthetic N trains on N seeded stand-in scans
 (scannet_data.write_synthetic_scans), so that the loop runs with no dataset at hand.  The statistics
 are summed on the device and read once per --print_interval steps; --no_guard / --clip_grad_norm
-choose what stands in front of the update (votenet/step.py)."""
+choose what stands in front of the update (votenet/step.py).  --unlabeled_scans DIR takes the
+unlabeled scans of --stage semi from a folder of bare clouds, every `.npy` / `.npz` in it (xyz or xyz +
+rgb, no label files: votenet/scan_data.py), instead of the unlabeled split of --data_dir."""
 import argparse
 import importlib
 import os
@@ -27,6 +30,9 @@ def parser():
     ap.add_argument('--data_dir', default=None, help='preprocessed scans (scannet_train_detection_data)')
     ap.add_argument('--meta_dir', default=None, help='the split lists (scannet/meta_data)')
     ap.add_argument('--labeled_sample_list', default='scannetv2_train.txt')
+    ap.add_argument('--unlabeled_scans', default=None, metavar='DIR',
+                    help="--stage semi: the unlabeled scans are the .npy / .npz clouds of DIR, which need no "
+                         "label files ('synthetic' with --synthetic N: the _vert.npy of the unlabeled half)")
     ap.add_argument('--detector_checkpoint', default='none')
     ap.add_argument('--log_dir', default='./temp', help='Dump dir to save model checkpoint')
     ap.add_argument('--num_point', type=int, default=40000, help='Point Number')
@@ -85,11 +91,20 @@ def eval_config_dict(cfg, flags):
 def main(argv=None):
     flags = parser().parse_args(argv)
     opt = settings(flags)
+    if flags.unlabeled_scans is not None:
+        if not opt['semi']:
+            raise SystemExit("--unlabeled_scans: --stage pretrain trains on labeled scans only")
+        if flags.view_stats:
+            raise SystemExit("--unlabeled_scans with --view_stats: the statistics compare the pseudo-labels with "
+                             "the unlabeled scans' own labels, which a folder of bare clouds does not have")
+        if flags.unlabeled_scans == 'synthetic' and not flags.synthetic:
+            raise SystemExit("--unlabeled_scans synthetic needs --synthetic N")
     sys.path.insert(0, ROOT)
     import torch
     importlib.import_module("3dioumatch_amd")
     V = importlib.import_module("3dioumatch_amd.votenet")
     SD = importlib.import_module("3dioumatch_amd.votenet.scannet_data")
+    SC = importlib.import_module("3dioumatch_amd.votenet.scan_data")
     T = importlib.import_module("3dioumatch_amd.votenet.trainer")
     U = importlib.import_module("3dioumatch_amd.votenet.losses_unlabeled")
     dev = torch.device(flags.device)
@@ -114,14 +129,27 @@ def main(argv=None):
             raise SystemExit("--data_dir and --meta_dir (or --synthetic N)")
         data_dir = flags.data_dir
         labeled = SD.labeled_split(data_dir, flags.meta_dir, flags.labeled_sample_list)
-        unlabeled = SD.unlabeled_split(data_dir, flags.meta_dir, flags.labeled_sample_list) if opt['semi'] else None
+        split = opt['semi'] and flags.unlabeled_scans is None
+        unlabeled = SD.unlabeled_split(data_dir, flags.meta_dir, flags.labeled_sample_list) if split else None
         val = SD.val_split(data_dir, flags.meta_dir)
         names = sorted(set(labeled) | set(unlabeled or ()) | set(val))
+    scans = None
+    if flags.unlabeled_scans == 'synthetic':
+        files = [os.path.join(data_dir, s + "_vert.npy") for s in unlabeled]
+    elif flags.unlabeled_scans is not None:
+        files = sorted(os.path.join(flags.unlabeled_scans, f) for f in os.listdir(flags.unlabeled_scans)
+                       if f.endswith((".npy", ".npz")))
+        if not files:
+            raise SystemExit("--unlabeled_scans %s: no .npy or .npz cloud in it" % flags.unlabeled_scans)
+    if flags.unlabeled_scans is not None:  # the labeled store then holds no unlabeled scan
+        scans = SC.ScanStore.from_files(files, dev, "scannet")
+        names = [s for s in names if s in set(labeled) | set(val)]
+        unlabeled = None
     scenes = SD.ScanNetScenes(data_dir, names, dev, use_color=flags.use_color, use_height=use_height)
     if tmp is not None:
-        tmp.cleanup()  # the store is resident
+        tmp.cleanup()  # the stores are resident
     loader = SD.ScanNetLoader(scenes, cfg, flags.num_point, seed=flags.seed or 0, labeled=labeled,
-                              unlabeled=unlabeled)
+                              unlabeled=unlabeled, unlabeled_scans=scans)
     val_loader = SD.ScanNetLoader(scenes, cfg, flags.num_point, seed=flags.seed or 0, labeled=val)
 
     common = dict(num_proposal=opt['num_target'], lr=opt['learning_rate'], meter=True, guard=opt['guard'],
