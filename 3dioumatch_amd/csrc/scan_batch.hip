@@ -16,11 +16,12 @@
 //                         unlabeled rows of a semi-supervised batch from raw clouds.  The slot's row
 //                         as scan_batch_kernel makes it (draws SB_DRAW_STUDENT / SB_DRAW_EMA of the
 //                         row's place in the whole batch, row0 + r), SUN RGB-D's colour / 256 in
-//                         float32, and for the student the dataset's flip / rotate / scale RESTATED
-//                         from scene_points_kernel / sun_points_kernel (float64 per stage, rounded to
-//                         float32 after each; the parity tests hold the copies equal).  All eight
+//                         float32, and for the student the dataset's flip / rotate / scale: the
+//                         functions of csrc/scene_common.h that scene_points_kernel and
+//                         sun_points_kernel call (row_aug, aug_point), not a copy of them.  All eight
 //                         gathers of a thread are issued before the first is used.  One thread per
-//                         row writes the header scene_boxes_kernel / sun_boxes_kernel write.
+//                         row writes the header with the labeled box kernels' write_row_header.
+//                         Both halves' rows are eval_row below, as scan_batch_kernel's are.
 //   scan_pack_kernel      one workgroup per scene: the kept proposals ranked by (objectness
 //                         probability descending, proposal ascending) with pseudo_rank::rank, then
 //                         every plane of the scene's arena rows written in row order -- rows past
@@ -29,7 +30,6 @@
 #include "scene_common.h"
 #include "pseudo_rank.h"
 #include "../../include/scan_hip.h"
-#include "../../include/sunrgbd_hip.h"  // SUN_DRAW_FLIP
 
 namespace {
 
@@ -38,15 +38,6 @@ constexpr int kPrepWaves = kPrepBlock / kWave;
 constexpr int kBlock = 256;
 constexpr int kPerThread = 8;
 constexpr int kChunk = kBlock * kPerThread;  // sample slots per workgroup of scan_batch_kernel
-
-__device__ __forceinline__ unsigned order_key(float f) {  // monotone: a < b <=> key(a) < key(b)
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float from_order_key(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
 
 __global__ void __launch_bounds__(kPrepBlock) scan_prepare_kernel(const ScanPrepareArgs a) {
   __shared__ unsigned s_hist[kPrepWaves * 256];  // one histogram per wave: less contention
@@ -124,11 +115,47 @@ __global__ void __launch_bounds__(kPrepBlock) scan_prepare_kernel(const ScanPrep
   a.nonfinite[scan] = (int)min(s_bad, 0x7FFFFFFFu);
 }
 
+// Raw row (x y z [r g b]) -> the eval row of the dataset's detection loader, e = x y z r g b height:
+// xyz as stored, the colour normalisation rounded once from double (without `color` no colour
+// column is read), height = z - floor.
+__device__ __forceinline__ void eval_row(bool sun, bool color, const float *raw, float floor, float (&e)[7]) {
+  e[0] = raw[0];
+  e[1] = raw[1];
+  e[2] = raw[2];
+  e[3] = e[4] = e[5] = 0.0f;
+  if (color) {
+    if (sun) {  // rgb - MEAN_COLOR_RGB, 0.5 each
+#pragma unroll
+      for (int c = 3; c < 6; ++c) e[c] = (float)((double)raw[c] - 0.5);
+    } else {  // (rgb - MEAN_COLOR_RGB) / 256.0
+      e[3] = (float)(((double)raw[3] - 109.8) / 256.0);
+      e[4] = (float)(((double)raw[4] - 97.2) / 256.0);
+      e[5] = (float)(((double)raw[5] - 83.8) / 256.0);
+    }
+  }
+  e[6] = __fsub_rn(raw[2], floor);
+}
+
+// the row's channels in output order: xyz, [rgb], [height]
+__device__ __forceinline__ void store_row(float *dst, bool color, bool height, const float (&e)[7]) {
+  dst[0] = e[0];
+  dst[1] = e[1];
+  dst[2] = e[2];
+  if (color) {
+    dst[3] = e[3];
+    dst[4] = e[4];
+    dst[5] = e[5];
+  }
+  if (height) dst[color ? 6 : 3] = e[6];
+}
+
 __global__ void __launch_bounds__(kBlock) scan_batch_kernel(const ScanBatchArgs a) {
   const int chunk = blockIdx.x, row = blockIdx.y, t = threadIdx.x;
   const int scene = a.scene[row];
   const int n = a.count[scene], N = a.N, C = a.C;
-  const int OC = 3 + (a.use_color ? 3 : 0) + (a.use_height ? 1 : 0);
+  const bool color = a.use_color != 0, height = a.use_height != 0;
+  const bool sun = a.dataset == SCAN_DATASET_SUNRGBD;
+  const int OC = 3 + (color ? 3 : 0) + (height ? 1 : 0);
   if (chunk == 0 && t == 0) a.scan_idx_out[row] = a.scan_idx[row];
   const float *cloud = a.cloud + a.offset[scene] * C;
   const float floor = a.floor[scene];
@@ -139,61 +166,14 @@ __global__ void __launch_bounds__(kBlock) scan_batch_kernel(const ScanBatchArgs 
     const int j = chunk * kChunk + k * kBlock + t;
     if (j >= N) break;
     const int p = a.idx_in ? a.idx_in[(size_t)row * N + j] : sample_index(key, j, n, N, h);
-    const float *src = cloud + (size_t)p * C;
-    float *dst = out + (size_t)j * OC;
-    const float z = src[2];
-    dst[0] = src[0];
-    dst[1] = src[1];
-    dst[2] = z;
-    int c = 3;
-    if (a.use_color) {
-      if (a.dataset == SCAN_DATASET_SCANNET) {  // (rgb - MEAN_COLOR_RGB) / 256.0
-        dst[3] = (float)(((double)src[3] - 109.8) / 256.0);
-        dst[4] = (float)(((double)src[4] - 97.2) / 256.0);
-        dst[5] = (float)(((double)src[5] - 83.8) / 256.0);
-      } else {  // rgb - MEAN_COLOR_RGB, 0.5 each
-        dst[3] = (float)((double)src[3] - 0.5);
-        dst[4] = (float)((double)src[4] - 0.5);
-        dst[5] = (float)((double)src[5] - 0.5);
-      }
-      c = 6;
-    }
-    if (a.use_height) dst[c] = __fsub_rn(z, floor);
+    float e[7];
+    eval_row(sun, color, cloud + (size_t)p * C, floor, e);
+    store_row(out + (size_t)j * OC, color, height, e);
   }
-}
-
-struct SemiAug {
-  int fx, fy;
-  double c, s, angle, scale;
-};
-
-__device__ __forceinline__ double semi_uniform(const ScanSemiArgs &a, int r, int k) {
-  const bool sun = a.dataset == SCAN_DATASET_SUNRGBD;
-  if (a.u_in) return a.u_in[r * (sun ? 3 : 4) + k];
-  const unsigned first = sun ? (unsigned)SUN_DRAW_FLIP : (unsigned)SB_DRAW_FLIP_X;
-  return (double)draw_key(a.seed, a.counter, (unsigned)(a.row0 + r), first + k) * 0x1p-32;
-}
-
-// row_aug of scene_batch.hip and sun_row_aug of sunrgbd_batch.hip, restated
-__device__ __forceinline__ SemiAug semi_row_aug(const ScanSemiArgs &a, int r) {
-  SemiAug g;
-  g.fx = semi_uniform(a, r, 0) > 0.5;
-  if (a.dataset == SCAN_DATASET_SUNRGBD) {
-    g.fy = 0;
-    g.angle = (semi_uniform(a, r, 1) * M_PI) / 3.0 - M_PI / 6.0;  // -30 ~ +30 degree
-    g.scale = semi_uniform(a, r, 2) * 0.3 + 0.85;
-  } else {
-    g.fy = semi_uniform(a, r, 1) > 0.5;
-    g.angle = (semi_uniform(a, r, 2) * M_PI) / 18.0 - M_PI / 36.0;  // -5 ~ +5 degree
-    g.scale = semi_uniform(a, r, 3) * 0.3 + 0.85;
-  }
-  g.c = cos(g.angle);
-  g.s = sin(g.angle);
-  return g;
 }
 
 __global__ void __launch_bounds__(kBlock) scan_semi_kernel(const ScanSemiArgs a) {
-  __shared__ SemiAug s_aug;
+  __shared__ RowAug s_aug;
   const int chunk = blockIdx.x, r = blockIdx.y, teacher = blockIdx.z, t = threadIdx.x;
   const int scene = a.scene[r];
   const int n = a.count[scene], N = a.N, C = a.C;
@@ -201,27 +181,16 @@ __global__ void __launch_bounds__(kBlock) scan_semi_kernel(const ScanSemiArgs a)
   const bool sun = a.dataset == SCAN_DATASET_SUNRGBD;
   const int OC = 3 + (color ? 3 : 0) + (height ? 1 : 0);
   if (t == 0 && !teacher) {
-    const SemiAug g = semi_row_aug(a, r);
+    const RowAug g = row_aug(sun, a.u_in, r, a.seed, a.counter, (unsigned)(a.row0 + r));
     s_aug = g;
-    if (chunk == 0) {  // the row's header, as the labeled builders' box kernels write it
+    if (chunk == 0) {  // the row's header, which the labeled builders' box kernels write
       a.supervised_mask[r] = 0;
       a.scan_idx_out[r] = a.scan_idx[r];
-      a.flip_x_axis[r] = g.fx;
-      a.flip_y_axis[r] = g.fy;
-      a.rot_angle[r] = (float)g.angle;
-      float *m = a.rot_mat + r * 9;
-      m[0] = (float)g.c; m[1] = (float)-g.s; m[2] = 0.0f;
-      m[3] = (float)g.s; m[4] = (float)g.c;  m[5] = 0.0f;
-      m[6] = 0.0f;       m[7] = 0.0f;        m[8] = 1.0f;
-      const float sc = (float)g.scale;
-      a.scale[r * 3 + 0] = sc;
-      a.scale[r * 3 + 1] = sc;
-      a.scale[r * 3 + 2] = sc;
+      write_row_header(a, r, g);
     }
   }
   __syncthreads();
-  SemiAug g{};
-  if (!teacher) g = s_aug;
+  const RowAug g = teacher ? row_identity() : s_aug;
   const float *cloud = a.cloud + a.offset[scene] * C;
   const float floor = a.floor[scene];
   const int *given = teacher ? a.ema_idx_in : a.idx_in;
@@ -248,41 +217,17 @@ __global__ void __launch_bounds__(kBlock) scan_semi_kernel(const ScanSemiArgs a)
   for (int k = 0; k < kPerThread; ++k) {
     const int j = chunk * kChunk + k * kBlock + t;
     if (j >= N) break;
-    float x = raw[k][0], y = raw[k][1], z = raw[k][2];
-    float rgb[3] = {0.0f, 0.0f, 0.0f};
-    if (color) {
-      if (sun) {  // rgb - MEAN_COLOR_RGB, 0.5 each, then the unlabeled dataset's / 256 in float32
+    float e[7];
+    eval_row(sun, color, raw[k], floor, e);
+    if (sun) {  // the unlabeled dataset's / 256 in float32, on both samples
 #pragma unroll
-        for (int c = 0; c < 3; ++c) rgb[c] = (float)((double)raw[k][3 + c] - 0.5) * 0.00390625f;
-      } else {  // (rgb - MEAN_COLOR_RGB) / 256.0
-        rgb[0] = (float)(((double)raw[k][3] - 109.8) / 256.0);
-        rgb[1] = (float)(((double)raw[k][4] - 97.2) / 256.0);
-        rgb[2] = (float)(((double)raw[k][5] - 83.8) / 256.0);
-      }
+      for (int c = 3; c < 6; ++c) e[c] *= 0.00390625f;
     }
-    float up = __fsub_rn(z, floor);
     if (!teacher) {
-      if (g.fx) x = -x;
-      if (g.fy) y = -y;
-      const double dx = x, dy = y, dz = z;
-      const float rx = (float)(dx * g.c + dy * -g.s + dz * 0.0);
-      const float ry = (float)(dx * g.s + dy * g.c + dz * 0.0);
-      const float rz = (float)(dx * 0.0 + dy * 0.0 + dz * 1.0);
-      x = (float)((double)rx * g.scale);
-      y = (float)((double)ry * g.scale);
-      z = (float)((double)rz * g.scale);
-      up = (float)((double)up * g.scale);
+      aug_point(g, e[0], e[1], e[2]);
+      e[6] = aug_scale(g, e[6]);
     }
-    float *dst = out + (size_t)j * OC;
-    dst[0] = x;
-    dst[1] = y;
-    dst[2] = z;
-    if (color) {
-      dst[3] = rgb[0];
-      dst[4] = rgb[1];
-      dst[5] = rgb[2];
-    }
-    if (height) dst[OC - 1] = up;
+    store_row(out + (size_t)j * OC, color, height, e);
   }
 }
 

@@ -19,6 +19,10 @@
 //                         by the semantic label at the instance's FIRST sampled position
 //                         (scannet_ssl_dataset.py:136-147).  Integer atomics make the result
 //                         independent of arrival order: bit-reproducible.
+// The draws, the row header, the point's and the box centre's flip / rotate / scale and the integer
+// keys are csrc/scene_common.h's (row_aug, write_row_header, aug_point, aug_vector, order_key), which
+// the other two builders call too; what is written out here is ScanNet's own: the extent rule of
+// rotate_aligned_boxes, the instance tables and the votes.
 #include "common.h"
 #include "scene_common.h"
 #include "../../include/scene_hip.h"
@@ -32,36 +36,6 @@ constexpr int kTableWords = 8;               // minx miny minz maxx maxy maxz fi
 
 __constant__ int kNyu40ids[18] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39};
 
-__device__ __forceinline__ double uniform_of(const SceneBatchArgs &a, int row, int k) {
-  if (a.u_in) return a.u_in[row * 4 + k];
-  return (double)draw_key(a.seed, a.counter, (unsigned)row, SB_DRAW_FLIP_X + k) * 0x1p-32;
-}
-
-struct Aug {
-  int fx, fy;
-  double c, s, angle, scale;
-};
-
-__device__ __forceinline__ Aug row_aug(const SceneBatchArgs &a, int row) {
-  Aug g;
-  g.fx = uniform_of(a, row, 0) > 0.5;
-  g.fy = uniform_of(a, row, 1) > 0.5;
-  g.angle = (uniform_of(a, row, 2) * M_PI) / 18.0 - M_PI / 36.0;  // -5 ~ +5 degree
-  g.scale = uniform_of(a, row, 3) * 0.3 + 0.85;
-  g.c = cos(g.angle);
-  g.s = sin(g.angle);
-  return g;
-}
-
-__device__ __forceinline__ unsigned order_key(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float from_order_key(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
 __device__ __forceinline__ bool is_nyu40(int id) {
   bool hit = false;
 #pragma unroll
@@ -73,25 +47,11 @@ __global__ void __launch_bounds__(kBlock) scene_boxes_kernel(const SceneBatchArg
   const int row = blockIdx.x, t = threadIdx.x;
   const int scene = a.scene[row];
   const bool train = a.augment != 0;
-  Aug g;
-  if (train) g = row_aug(a, row);
+  const RowAug g = train ? row_aug(false, a.u_in, row, a.seed, a.counter, (unsigned)row) : row_identity();
   if (t == 0) {
     if (a.supervised_mask) a.supervised_mask[row] = a.supervised[row];
     if (a.scan_idx_out) a.scan_idx_out[row] = a.scan_idx[row];
-    if (a.flip_x_axis) {
-      a.flip_x_axis[row] = train ? g.fx : 0;
-      a.flip_y_axis[row] = train ? g.fy : 0;
-      a.rot_angle[row] = train ? (float)g.angle : 0.0f;
-      const double c = train ? g.c : 1.0, s = train ? g.s : 0.0;
-      float *m = a.rot_mat + row * 9;
-      m[0] = (float)c; m[1] = (float)-s; m[2] = 0.0f;
-      m[3] = (float)s; m[4] = (float)c;  m[5] = 0.0f;
-      m[6] = 0.0f;     m[7] = 0.0f;      m[8] = 1.0f;
-      const float sc = train ? (float)g.scale : 1.0f;
-      a.scale[row * 3 + 0] = sc;
-      a.scale[row * 3 + 1] = sc;
-      a.scale[row * 3 + 2] = sc;
-    }
+    write_row_header(a, row, g);
   }
   if (row < a.vote_rows) {  // the instance table the points kernel fills
     const int words = a.ninst[scene] * kTableWords;
@@ -111,13 +71,9 @@ __global__ void __launch_bounds__(kBlock) scene_boxes_kernel(const SceneBatchArg
     cls = (int)src[6];
   }
   if (train && row < a.box_aug_rows) {
-    if (g.fx) cx = -1.0 * cx;
-    if (g.fy) cy = -1.0 * cy;
     // rotate_aligned_boxes: centres by rot_mat, x/y extent = 2 x the largest rotated half-corner
+    aug_vector(g, cx, cy, cz);
     const double c = g.c, s = g.s;
-    const double ncx = cx * c + cy * -s + cz * 0.0;
-    const double ncy = cx * s + cy * c + cz * 0.0;
-    const double ncz = cx * 0.0 + cy * 0.0 + cz * 1.0;
     const double hx = dx / 2.0, hy = dy / 2.0;
     double mx = -INFINITY, my = -INFINITY;
     const double sx[4] = {-1.0, 1.0, 1.0, -1.0}, sy[4] = {-1.0, -1.0, 1.0, 1.0};
@@ -127,7 +83,6 @@ __global__ void __launch_bounds__(kBlock) scene_boxes_kernel(const SceneBatchArg
       mx = fmax(mx, px * c + py * -s + 0.0 * 0.0);
       my = fmax(my, px * s + py * c + 0.0 * 0.0);
     }
-    cx = ncx * g.scale; cy = ncy * g.scale; cz = ncz * g.scale;
     dx = (2.0 * mx) * g.scale; dy = (2.0 * my) * g.scale; dz = dz * g.scale;
   }
   const size_t o = (size_t)row * SB_MAX_OBJ + t;
@@ -147,18 +102,17 @@ __global__ void __launch_bounds__(kBlock) scene_boxes_kernel(const SceneBatchArg
 
 __global__ void __launch_bounds__(kBlock) scene_points_kernel(const SceneBatchArgs a) {
   __shared__ unsigned s_tab[7 * SB_MAX_INST];
-  __shared__ Aug s_aug;
+  __shared__ RowAug s_aug;
   const int chunk = blockIdx.x, row = blockIdx.y, teacher = blockIdx.z, t = threadIdx.x;
   const int scene = a.scene[row];
   const int n = a.count[scene], N = a.N, C = a.C;
   const bool augment = !teacher && a.augment;
   const bool votes = !teacher && row < a.vote_rows;
   const int ninst = votes ? a.ninst[scene] : 0;
-  if (t == 0 && augment) s_aug = row_aug(a, row);
+  if (t == 0 && augment) s_aug = row_aug(false, a.u_in, row, a.seed, a.counter, (unsigned)row);
   for (int i = t; i < 7 * ninst; i += kBlock) s_tab[i] = (i < 3 * ninst || i >= 6 * ninst) ? 0xFFFFFFFFu : 0u;
   __syncthreads();
-  Aug g{};
-  if (augment) g = s_aug;
+  const RowAug g = augment ? s_aug : row_identity();
   const float *cloud = a.cloud + a.offset[scene] * C;
   const int *given = teacher ? a.ema_idx_in : a.idx_in;
   const unsigned key = draw_key(a.seed, a.counter, (unsigned)row, teacher ? SB_DRAW_EMA : SB_DRAW_STUDENT);
@@ -173,18 +127,10 @@ __global__ void __launch_bounds__(kBlock) scene_points_kernel(const SceneBatchAr
 #pragma unroll
     for (int c = 0; c < 7; ++c) v[c] = c < C ? src[c] : 0.0f;
     if (augment) {
-      if (g.fx) v[0] = -v[0];
-      if (g.fy) v[1] = -v[1];
-      const double x = v[0], y = v[1], z = v[2];
-      const float rx = (float)(x * g.c + y * -g.s + z * 0.0);
-      const float ry = (float)(x * g.s + y * g.c + z * 0.0);
-      const float rz = (float)(x * 0.0 + y * 0.0 + z * 1.0);
-      v[0] = (float)((double)rx * g.scale);
-      v[1] = (float)((double)ry * g.scale);
-      v[2] = (float)((double)rz * g.scale);
+      aug_point(g, v[0], v[1], v[2]);
 #pragma unroll
       for (int c = 3; c < 7; ++c)
-        if (a.has_height && c == C - 1) v[c] = (float)((double)v[c] * g.scale);
+        if (a.has_height && c == C - 1) v[c] = aug_scale(g, v[c]);
     }
 #pragma unroll
     for (int c = 0; c < 7; ++c)

@@ -26,6 +26,10 @@
 // is the oriented box itself) is sun_vote_row, shared by the two kernels: the scene's boxes staged
 // once per workgroup in LDS (64 x 8 doubles), every test in float64, the slot picked by selects.
 // No atomics, no scratch tables: a slot's outputs depend on its own source row alone.
+// The draws, the row header, the point's flip / rotate / scale and the float64 one of the box centres
+// and the votes are csrc/scene_common.h's (row_aug, write_row_header, aug_point, aug_vector), which
+// the other two builders call too; what is written out here is SUN RGB-D's own: heading and half
+// sizes, the colour augmentation and the vote rule.
 #include "common.h"
 #include "scene_common.h"
 #include "../../include/sunrgbd_hip.h"
@@ -35,26 +39,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kPerThread = 8;
 constexpr int kChunk = kBlock * kPerThread;  // sample slots per workgroup of sun_points_kernel
-
-__device__ __forceinline__ double sun_uniform(const SunBatchArgs &a, int row, int k) {
-  if (a.u_in) return a.u_in[row * 3 + k];
-  return (double)draw_key(a.seed, a.counter, (unsigned)row, SUN_DRAW_FLIP + k) * 0x1p-32;
-}
-
-struct SunAug {
-  int fx;
-  double c, s, angle, scale;
-};
-
-__device__ __forceinline__ SunAug sun_row_aug(const SunBatchArgs &a, int row) {
-  SunAug g;
-  g.fx = sun_uniform(a, row, 0) > 0.5;
-  g.angle = (sun_uniform(a, row, 1) * M_PI) / 3.0 - M_PI / 6.0;  // -30 ~ +30 degree
-  g.scale = sun_uniform(a, row, 2) * 0.3 + 0.85;
-  g.c = cos(g.angle);
-  g.s = sin(g.angle);
-  return g;
-}
 
 // Python's float modulo for a positive divisor: the result takes the divisor's sign
 __device__ __forceinline__ double py_mod(double x, double y) {
@@ -71,25 +55,11 @@ __global__ void __launch_bounds__(SUN_MAX_OBJ) sun_boxes_kernel(const SunBatchAr
   const int row = blockIdx.x, t = threadIdx.x;
   const int scene = a.scene[row];
   const bool train = a.augment != 0;
-  SunAug g;
-  if (train) g = sun_row_aug(a, row);
+  const RowAug g = train ? row_aug(true, a.u_in, row, a.seed, a.counter, (unsigned)row) : row_identity();
   if (t == 0) {
     if (a.supervised_mask) a.supervised_mask[row] = a.supervised[row];
     if (a.scan_idx_out) a.scan_idx_out[row] = a.scan_idx[row];
-    if (a.flip_x_axis) {
-      a.flip_x_axis[row] = train ? g.fx : 0;
-      a.flip_y_axis[row] = 0;
-      a.rot_angle[row] = train ? (float)g.angle : 0.0f;
-      const double c = train ? g.c : 1.0, s = train ? g.s : 0.0;
-      float *m = a.rot_mat + row * 9;
-      m[0] = (float)c; m[1] = (float)-s; m[2] = 0.0f;
-      m[3] = (float)s; m[4] = (float)c;  m[5] = 0.0f;
-      m[6] = 0.0f;     m[7] = 0.0f;      m[8] = 1.0f;
-      const float sc = train ? (float)g.scale : 1.0f;
-      a.scale[row * 3 + 0] = sc;
-      a.scale[row * 3 + 1] = sc;
-      a.scale[row * 3 + 2] = sc;
-    }
+    write_row_header(a, row, g);
   }
   if (row >= a.box_rows) return;
   const int nb = a.nbox[scene];
@@ -103,16 +73,9 @@ __global__ void __launch_bounds__(SUN_MAX_OBJ) sun_boxes_kernel(const SunBatchAr
     cls = (int)src[7];
   }
   if (train && row < a.box_aug_rows) {
-    if (g.fx) {
-      cx = -1.0 * cx;
-      heading = M_PI - heading;
-    }
-    const double c = g.c, s = g.s;
-    const double ncx = cx * c + cy * -s + cz * 0.0;
-    const double ncy = cx * s + cy * c + cz * 0.0;
-    const double ncz = cx * 0.0 + cy * 0.0 + cz * 1.0;
+    aug_vector(g, cx, cy, cz);
+    if (g.fx) heading = M_PI - heading;
     heading -= g.angle;
-    cx = ncx * g.scale; cy = ncy * g.scale; cz = ncz * g.scale;
     hx = hx * g.scale; hy = hy * g.scale; hz = hz * g.scale;
   }
   // angle2class (model_util_sunrgbd.py:92-108)
@@ -209,7 +172,7 @@ __device__ __forceinline__ double sun_color_uniform(const SunBatchArgs &a, int r
 // kFromBoxes: the store holds no vote rows (a.votes == NULL); they are computed from the boxes
 template <bool kFromBoxes>
 __global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a) {
-  __shared__ SunAug s_aug;
+  __shared__ RowAug s_aug;
   __shared__ SunColor s_col;
   __shared__ SunBox s_box[kFromBoxes ? SUN_MAX_OBJ : 1];
   const int chunk = blockIdx.x, row = blockIdx.y, teacher = blockIdx.z, t = threadIdx.x;
@@ -219,7 +182,7 @@ __global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a
   const bool votes = !teacher && row < a.vote_rows;
   const bool color = augment && a.color_aug && C >= 6;
   const bool div256 = row >= a.div256_from && C >= 6;
-  if (t == 0 && augment) s_aug = sun_row_aug(a, row);
+  if (t == 0 && augment) s_aug = row_aug(true, a.u_in, row, a.seed, a.counter, (unsigned)row);
   if (t < 3 && color) {
     s_col.bright[t] = 1.0 + 0.4 * sun_color_uniform(a, row, t) - 0.2;
     s_col.shift[t] = 0.1 * sun_color_uniform(a, row, 3 + t) - 0.05;
@@ -232,8 +195,7 @@ __global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a
     }
   }
   __syncthreads();
-  SunAug g{};
-  if (augment) g = s_aug;
+  const RowAug g = augment ? s_aug : row_identity();
   SunColor col{};
   if (color) col = s_col;
   const long long off = a.offset[scene];
@@ -270,12 +232,8 @@ __global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a
       v[5] *= 0.00390625f;
     }
     if (augment) {
-      if (g.fx) v[0] = -v[0];
-      const double x = v[0], y = v[1], z = v[2];
-      const float rx = (float)(x * g.c + y * -g.s + z * 0.0);
-      const float ry = (float)(x * g.s + y * g.c + z * 0.0);
-      const float rz = (float)(x * 0.0 + y * 0.0 + z * 1.0);
-      if (color) {
+      aug_point(g, v[0], v[1], v[2]);
+      if (color) {  // (touches channels 3..5 only; the height channel is scaled after it)
         const double uj = u_point ? u_point[p] : (double)element(key_jit, (unsigned)p) * 0x1p-32;
         const double ud = u_point ? u_point[a.u_point_stride + p]
                                   : (double)element(key_drop, (unsigned)p) * 0x1p-32;
@@ -292,12 +250,9 @@ __global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a
           v[3 + c] = (float)(rgb - 0.5);
         }
       }
-      v[0] = (float)((double)rx * g.scale);
-      v[1] = (float)((double)ry * g.scale);
-      v[2] = (float)((double)rz * g.scale);
 #pragma unroll
       for (int c = 3; c < 7; ++c)
-        if (a.has_height && c == C - 1) v[c] = (float)((double)v[c] * g.scale);
+        if (a.has_height && c == C - 1) v[c] = aug_scale(g, v[c]);
     }
 #pragma unroll
     for (int c = 0; c < 7; ++c)
@@ -310,15 +265,7 @@ __global__ void __launch_bounds__(kBlock) sun_points_kernel(const SunBatchArgs a
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
         double x = vx[q], y = vy[q], z = vz[q];
-        if (augment) {
-          if (g.fx) x = -1.0 * x;
-          const double rx = x * g.c + y * -g.s + z * 0.0;
-          const double ry = x * g.s + y * g.c + z * 0.0;
-          const double rz = x * 0.0 + y * 0.0 + z * 1.0;
-          x = rx * g.scale;
-          y = ry * g.scale;
-          z = rz * g.scale;
-        }
+        if (augment) aug_vector(g, x, y, z);
         dst[q * 3 + 0] = (float)x;
         dst[q * 3 + 1] = (float)y;
         dst[q * 3 + 2] = (float)z;

@@ -101,10 +101,11 @@ typedef struct ScanSemiArgs {
  * 221-312) from raw clouds.  Each slot gathers its raw row (draws SB_DRAW_STUDENT / SB_DRAW_EMA of
  * batch row row0 + r), normalises colour as scene_scan_batch_build does -- SUN RGB-D divides by 256
  * once more in float32, as its unlabeled dataset does -- and takes height = z - floor; the student
- * sample then goes through the dataset's augmentation in scene_batch_build's /
- * scene_sunrgbd_batch_build's own arithmetic (float64 per stage, rounded to float32 after each), so
- * the rows are bit-equal to the unlabeled rows those builders give for the same scans as float32
- * files.  One thread per row writes the row's header as their box kernels do.
+ * sample then goes through the dataset's augmentation by the very device functions
+ * scene_batch_build / scene_sunrgbd_batch_build call (csrc/scene_common.h: float64 per stage,
+ * rounded to float32 after each), so the rows are bit-equal to the unlabeled rows those builders
+ * give for the same scans as float32 files.  One thread per row writes the row's header with the
+ * function their box kernels write it with.
  * hipErrorInvalidValue, without a launch: NULL args, B outside 1..SB_MAX_B, row0 < 0 or row0 + B >
  * SB_MAX_B, N < 1, C not 3 or 6, use_color with C == 3, an unknown dataset, a NULL store or output
  * pointer. */
