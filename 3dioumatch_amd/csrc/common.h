@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <mutex>
+#include <set>
 
 #define PN2_API extern "C" __attribute__((visibility("default")))
 
@@ -80,4 +82,81 @@ __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & (kWave - 1
 __device__ __forceinline__ int mask_rank(unsigned long long mask) {
   return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32),
                                         __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
+// ---- wave reductions: butterflies in a FIXED order (summation order is part of the results) ------
+// sum over the 64 lanes, every lane gets it; offsets 32, 16, .., 1
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = kWave / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
+  return v;
+}
+
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __shfl_xor(lo, mask, kWave);
+  hi = __shfl_xor(hi, mask, kWave);
+  return __hiloint2double(hi, lo);
+}
+
+// the same in double; offsets 1, 2, .., 32 (the other way round from the float form)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) v += shfl_xor_f64(v, off);
+  return v;
+}
+
+// sum over the 32 lanes of each half-wave (DPP, no LDS); the total lands in lanes 16..31 / 48..63
+__device__ __forceinline__ float half_wave_sum(float v) {
+#define HW_STEP(CTRL, RM) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, RM, 0xf, false))
+  HW_STEP(0xB1, 0xf);   // quad_perm [1,0,3,2]
+  HW_STEP(0x4E, 0xf);   // quad_perm [2,3,0,1]
+  HW_STEP(0x141, 0xf);  // row_half_mirror
+  HW_STEP(0x140, 0xf);  // row_mirror        -> every lane: the total of its row of 16
+  HW_STEP(0x142, 0xa);  // row_bcast:15 into rows 1 and 3 -> the total of the half-wave
+#undef HW_STEP
+  return v;
+}
+
+// the same butterfly with max / min: lanes 16..31 (48..63) end up with the extreme of lanes
+// 0..31 (32..63); masked-out rows keep their own value (old = v)
+template <bool MAXOP>
+__device__ __forceinline__ float half_wave_extreme(float v) {
+#define HX_STEP(CTRL, RM)                                                                        \
+  {                                                                                              \
+    const float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(                      \
+        __builtin_bit_cast(int, v), __builtin_bit_cast(int, v), CTRL, RM, 0xf, false));         \
+    v = MAXOP ? fmaxf(v, o) : fminf(v, o);                                                       \
+  }
+  HX_STEP(0xB1, 0xf);
+  HX_STEP(0x4E, 0xf);
+  HX_STEP(0x141, 0xf);
+  HX_STEP(0x140, 0xf);
+  HX_STEP(0x142, 0xa);
+#undef HX_STEP
+  return v;
+}
+
+// ---- host side of the persistent / large-LDS launches ---------------------------------------------
+// compute units of the current device (256 when it cannot be asked), asked once
+static inline int pn2_cu_count() {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+  }
+  return cus;
+}
+
+// Let `kernel` be launched with up to `bytes` of dynamic LDS (above the 64 KB default): set once per
+// kernel, remembered by address (the instantiations of a template share one pointer type), safe
+// from several host threads.  The first call's `bytes` holds: pass the kernel's maximum.
+static inline void pn2_allow_dynamic_lds(const void *kernel, size_t bytes) {
+  static std::mutex mu;
+  static std::set<const void *> done;
+  std::lock_guard<std::mutex> lock(mu);
+  if (done.insert(kernel).second)
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }

@@ -18,7 +18,6 @@
 #include "common.h"
 #include "box_geom.h"
 #include "iou3d_pair.h"
-#include <mutex>
 
 namespace {
 
@@ -407,16 +406,7 @@ IOU3D_API int iou3d_nms(const float *boxes, int boxes_num, float thresh, int nor
   if (rc != 0) return rc;
   const int col_blocks = (boxes_num + 63) / 64;
   if (col_blocks <= 16) {  // the mask fits the LDS
-    static std::mutex mu;
-    static bool attr_set = false;
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(nms_scan_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 1024 * 16 * 8);
-        attr_set = true;
-      }
-    }
+    pn2_allow_dynamic_lds(reinterpret_cast<const void *>(nms_scan_kernel<true>), 1024 * 16 * 8);
     hipLaunchKernelGGL(nms_scan_kernel<true>, dim3(1), dim3(1024),
                        sizeof(unsigned long long) * (size_t)boxes_num * col_blocks, stream, mask_ws, boxes_num,
                        col_blocks, keep_dev, num_out_dev);

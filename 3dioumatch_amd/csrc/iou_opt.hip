@@ -22,12 +22,6 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 __global__ void __launch_bounds__(256)
 iou_opt_box_step_kernel(int boxes, int k, int nseed, int ch, const float *__restrict__ unit,
                         const float *__restrict__ seed_xyz, const int *__restrict__ idx,

@@ -23,12 +23,6 @@ namespace {
 
 constexpr int kBnThreads = 256;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 // sum of two values over the workgroup; result valid in thread 0
 __device__ __forceinline__ void block_sum2(float &a, float &b, float *scratch) {
   a = wave_sum(a);
@@ -99,13 +93,6 @@ __device__ __forceinline__ Moments chan_merge(const Moments &a, const Moments &b
   return o;
 }
 
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __shfl_xor(lo, mask, kWave);
-  hi = __shfl_xor(hi, mask, kWave);
-  return __hiloint2double(hi, lo);
-}
-
 struct FwdFinalize {
   int *tickets;  // one counter per channel, zero between launches (the caller's array)
   const float *gamma, *beta;
@@ -161,6 +148,7 @@ __device__ __forceinline__ void fwd_write_channel(int ch, double n, double mean,
 // reduction (~5 us).  The backward form keeps y and dz in registers between the sums and dy.
 constexpr int kChThreads = 1024, kChMax = 4 * 4 * kChThreads;  // values per channel
 __device__ __forceinline__ void channel_sum2(double &a, double &b, double (*red)[2]) {
+  // (wave_sum of each, the two butterflies interleaved)
 #pragma unroll
   for (int off = 1; off < kWave; off <<= 1) { a += shfl_xor_f64(a, off); b += shfl_xor_f64(b, off); }
   const int w = threadIdx.x / kWave;
@@ -527,7 +515,7 @@ __device__ __forceinline__ void bwd_finalize_channel(int ch, int parts, const fl
   const float *p = partial + (size_t)ch * parts * 2;
   for (int q = lane; q < parts; q += kWave) { s1 += coherent_load(p + q * 2); s2 += coherent_load(p + q * 2 + 1); }
 #pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
+  for (int off = 1; off < kWave; off <<= 1) {  // (wave_sum of each, interleaved)
     s1 += shfl_xor_f64(s1, off);
     s2 += shfl_xor_f64(s2, off);
   }

@@ -41,7 +41,7 @@
 namespace {
 
 // X6: the products run as six bf16 MFMAs on an exact three-term split of the fp32 fragments
-// (mlp_operand.h: split3 / mfma_x6): a fragment is then a lane's EIGHT consecutive reduction
+// (mlp_frag.h: split3 / mfma_x6): a fragment is then a lane's EIGHT consecutive reduction
 // indices -- eight 4-byte LDS reads from the same conflict-free tiles -- and an MFMA step covers
 // 16 of them, so a chunk is M/16 dgrad steps and TN/16 wgrad steps.
 template <int MB, int KB, int KBD, int NB, int PMODE, int QMODE, int OCC, bool STATS, bool DGRAD = true,
@@ -630,21 +630,10 @@ bool fused_shape(int m, int k, FusedShape *s) {
   return false;
 }
 
-int fused_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 // workgroups of the persistent launch: one resident round, at least 8 chunks each (the partial
 // dW every workgroup writes must stay small next to the activations it read)
 int fused_workgroups(const FusedShape &s, long long total_chunks) {
-  long long g = (long long)fused_cus() * s.occ;
+  long long g = (long long)pn2_cu_count() * s.occ;
   if (g > total_chunks / 8) g = total_chunks / 8;
   return (int)(g < 1 ? 1 : g);
 }
@@ -681,7 +670,7 @@ MLP_API int mlp_gemm_backward_fused_supported(int b, int m, int k, int r, int pm
 MLP_API int mlp_gemm_backward_fused_stats_parts(int b, int m, int k, int r) {
   FusedShape s;
   // the (128,128) layers on the bf16-split kernel: one partial per workgroup
-  const int gx = mlp_bwd_x6_workgroups(b, m, k, r, fused_cus());
+  const int gx = mlp_bwd_x6_workgroups(b, m, k, r, pn2_cu_count());
   if (gx > 0) return gx;
   // otherwise the first set-abstraction level only: there the absorbed pass over (x, dq) costs
   // ~95 us a layer; on the narrower levels the extra registers cost the fp32 GEMM more than the pass
@@ -694,7 +683,7 @@ MLP_API size_t mlp_gemm_backward_fused_workspace_floats(int b, int m, int k, int
   if (!fused_shape(m, k, &s) || r % s.tn != 0) return 0;
   // (the bf16-split kernel of the (128,128) layers writes one partial per ITS workgroup count)
   const long long g0 = fused_workgroups(s, (long long)b * (r / s.tn));
-  const long long g1 = mlp_bwd_x6_workgroups(b, m, k, r, fused_cus());
+  const long long g1 = mlp_bwd_x6_workgroups(b, m, k, r, pn2_cu_count());
   return (size_t)(g0 > g1 ? g0 : g1) * m * k;
 }
 
@@ -722,7 +711,7 @@ MLP_API int mlp_gemm_backward_fused(int b, int m, int k, int r, const float *w, 
   {  // the bf16-split kernel with its operands split at staging, where it covers the shape
     int gx = 0;
     const int rcx = mlp_bwd_x6_try(b, m, k, r, pmode, qmode, P, Q, w, dq, workspace,
-                                   qmode == OP_BNRELU ? stats_part : nullptr, fused_cus(), &gx, stream);
+                                   qmode == OP_BNRELU ? stats_part : nullptr, pn2_cu_count(), &gx, stream);
     if (rcx > 0) return rcx;
     if (rcx == 0) return mlp_reduce_weight_partials(m * k, gx, workspace, dw, stream);
   }

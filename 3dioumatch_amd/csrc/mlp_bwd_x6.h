@@ -1,6 +1,6 @@
 // 3dioumatch_amd/csrc/mlp_bwd_x6.h (included by mlp_bwd_fused.hip) -- the one-pass backward of a shared-MLP layer (see
 // mlp_bwd_fused.hip for what it computes: dQ = W^T P and dW = sum P Q^T from ONE staging of the
-// chunk) with its fp32 products on the bf16 matrix pipe (mlp_operand.h: exact three-term split,
+// chunk) with its fp32 products on the bf16 matrix pipe (mlp_frag.h: exact three-term split,
 // six of the nine partial products, v_mfma_f32_32x32x16_bf16).
 //
 // The fp32 kernel gathers a fragment as single floats from odd-pitch fp32 tiles; splitting those
@@ -43,28 +43,9 @@
 
 namespace {
 
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-
 #if defined(BWDX6_ABL) && BWDX6_ABL == 2   // (timing ablation 2: no MFMAs)
 #define mfma_x6(ACC, A, B) do { (ACC)[0] += __builtin_bit_cast(float, (int)(A).hi[0] + (int)(B).hi[0] + (int)(A).mid[1] + (int)(B).mid[1] + (int)(A).lo[2] + (int)(B).lo[2]); } while (0)
 #endif
-
-__device__ __forceinline__ bf16x4 lds_read_tr(const char *p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) bf16x4 *)(__attribute__((address_space(3))) char *)p);
-}
-
-// sum over the 32 lanes of each half-wave (DPP, no LDS); the total lands in lanes 16..31 / 48..63
-__device__ __forceinline__ float x6_half_wave_sum(float v) {
-#define HW_STEP(CTRL, RM) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, RM, 0xf, false))
-  HW_STEP(0xB1, 0xf);   // quad_perm [1,0,3,2]
-  HW_STEP(0x4E, 0xf);   // quad_perm [2,3,0,1]
-  HW_STEP(0x141, 0xf);  // row_half_mirror
-  HW_STEP(0x140, 0xf);  // row_mirror        -> every lane: the total of its row of 16
-  HW_STEP(0x142, 0xa);  // row_bcast:15 into rows 1 and 3 -> the total of the half-wave
-#undef HW_STEP
-  return v;
-}
 
 // Which waves stage which slices (a slice = 32 rows of P or Q, one float4 per lane of a role's 256):
 // bit sl set = the dgrad waves stage slice sl (P slices 0 .. PS-1, then the Q slices), clear = the
@@ -234,20 +215,6 @@ __device__ __forceinline__ void gemm_bwd_x6_role(int k_total, int r, int total_c
     }
   };
   // slice: four consecutive n of a row -> transformed, split, 8 bytes per term into the images
-  auto store4 = [&](char *img, size_t term_bytes, int row, int c0, const float (&v)[4]) {
-    float h[4], m[4], l[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      h[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v[e]) & 0xffff0000u);
-      const float r1 = v[e] - h[e];
-      m[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & 0xffff0000u);
-      l[e] = r1 - m[e];
-    }
-    char *dst = img + (size_t)row * RP + c0 * 2;
-    *reinterpret_cast<uint2 *>(dst) = make_uint2(pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]));
-    *reinterpret_cast<uint2 *>(dst + term_bytes) = make_uint2(pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]));
-    *reinterpret_cast<uint2 *>(dst + 2 * term_bytes) = make_uint2(pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]));
-  };
   auto stage_slice = [&](int sl, int buf) {
     char *base = lds + (size_t)buf * BUF;
     if (sl < PS) {
@@ -260,14 +227,14 @@ __device__ __forceinline__ void gemm_bwd_x6_role(int k_total, int r, int total_c
         const float dz = PMODE == OP_POOLDY ? (e == pwin[p] ? pdp[p] : 0.f) : dv[e];
         v[e] = transform<PMODE>(xv[e], dz, pc[p]);
       }
-      store4(base, PIMG, seg_row + p * 32, seg_c, v);
+      store_split4<RP>(base, PIMG, seg_row + p * 32, seg_c, v);
     } else {
       const int q = sl - PS;
       const float xv[4] = {qx[q].x, qx[q].y, qx[q].z, qx[q].w};
       float v[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = q_ok[q] ? transform<QMODE>(xv[e], 0.f, qc[q]) : 0.f;
-      store4(base + 3 * PIMG, QIMG, seg_row + q * 32, seg_c, v);
+      store_split4<RP>(base + 3 * PIMG, QIMG, seg_row + q * 32, seg_c, v);
       if (STATS)
         *reinterpret_cast<float4 *>(base + 3 * (PIMG + QIMG) + (size_t)(seg_row + q * 32) * RAWP + seg_c * 4) =
             qx[q];
@@ -536,12 +503,7 @@ static int mlp_bwd_x6_try(int b, int m, int k, int r, int pmode, int qmode, cons
     const size_t lds_bytes = 2 * (3 * (size_t)(m + k) * RP + (ST ? (size_t)k * 144 : 0)) +         \
                              (ST ? (size_t)k * 16 : 0);                                             \
     auto kern = gemm_bwd_x6_kernel<MB, KB, KBD, PM, QM, ST>;                                        \
-    static bool attr_set = false;                                                                   \
-    if (!attr_set) {                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                               \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);        \
-      attr_set = true;                                                                              \
-    }                                                                                               \
+    pn2_allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes);                         \
     hipLaunchKernelGGL(kern, dim3(g), dim3(512), lds_bytes, stream, k, r, total_chunks,             \
                        chunks_per_cloud, 0, P, Q, w, dq, part, stats_part);                         \
   } while (0)

@@ -20,7 +20,7 @@
 // and the y3 store from the accumulators.  Layer 2's own statistics need a pass of their own
 // (they must exist before its ReLU): the same kernel without layer 3, in T form, nothing stored.
 //
-// fp32 products as six bf16 MFMAs on the exact three-term split (mlp_operand.h).  The weights are
+// fp32 products as six bf16 MFMAs on the exact three-term split (mlp_frag.h).  The weights are
 // split ONCE per workgroup into fragment-ordered bf16 images in LDS (one ds_read_b128 per term
 // and fragment, conflict-free; 72 KB for 64x64 + 128x64), two workgroups per CU.
 //
@@ -30,8 +30,6 @@
 //         every other kernel that recomputes it (lin4).
 #include "common.h"
 #include "mlp_operand.h"
-#include <mutex>
-#include <set>
 #include <type_traits>
 
 namespace {
@@ -40,7 +38,7 @@ struct ChainArgs {
   int r;                 // columns per cloud (multiple of 64)
   int tiles_per_cloud;   // r / 32
   const float *x4;       // (b, 4, r)
-  const char *wimg;      // the weight images + layer-1 tables chain_prep_kernel left (kImgBytes)
+  const char *wimg;      // the weight images + layer-1 tables chain_prep_kernel left (kLin4ImgBytes)
   const float *sc2, *sh2;  // (64) BatchNorm of layer 2 (full pass)
   const float *gamma3;   // (M3): sign decides which extreme wins the pool
   float *y2;             // (b, 64, r) or null
@@ -51,41 +49,7 @@ struct ChainArgs {
   size_t ext_plane;
 };
 
-constexpr int kChainK = 64;  // channels entering layer 2 / layer 3 (SA1: 64 -> 64 -> 128)
-
-// byte offset of fragment (term, step t, half h, row) in a weight image of R rows
-template <int R>
-__device__ __forceinline__ int img_off(int term, int t, int h, int row) {
-  return (((term * (kChainK / 16) + t) * 2 + h) * R + row) * 16;
-}
-
-__device__ __forceinline__ Split3 lds_frag(const char *img, int term_stride) {
-  Split3 s;
-  s.hi = *reinterpret_cast<const bf16x8 *>(img);
-  s.mid = *reinterpret_cast<const bf16x8 *>(img + term_stride);
-  s.lo = *reinterpret_cast<const bf16x8 *>(img + 2 * term_stride);
-  return s;
-}
-
-// acc[i] += w[i] x s (N form: the weight is the A operand) or s x w[i] (T form), i < NB: the six
-// significant partial products, small ones first, the NB independent accumulators interleaved
-template <int NB, bool TFORM, bool FIRST = false>
-__device__ __forceinline__ void mfma6(f32x16 (&acc)[NB], const Split3 &s, const Split3 (&w)[NB]) {
-  // FIRST: the accumulators are not read -- the first product starts from a literal zero (an inline
-  // constant of the MFMA: no register is cleared; 96 v_mov per tile otherwise)
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#define CH_STEP(WT, ST, C0)                                                                        \
-  _Pragma("unroll") for (int i = 0; i < NB; ++i)                                                  \
-    acc[i] = TFORM ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(s.ST, w[i].WT, (C0) ? zero : acc[i], 0, 0, 0) \
-                   : __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[i].WT, s.ST, (C0) ? zero : acc[i], 0, 0, 0)
-  CH_STEP(lo, hi, FIRST);
-  CH_STEP(hi, lo, false);
-  CH_STEP(mid, mid, false);
-  CH_STEP(mid, hi, false);
-  CH_STEP(hi, mid, false);
-  CH_STEP(hi, hi, false);
-#undef CH_STEP
-}
+constexpr int kChainK = kLin4K;  // channels entering layer 2 / layer 3 (SA1: 64 -> 64 -> 128)
 
 // running shifted sums of one channel (a lane's 16 samples per tile)
 struct RunStat { float shift, s1, s2; };
@@ -100,10 +64,8 @@ struct RunStat { float shift, s1, s2; };
 // resident ran after all others and the launch took twice as long (measured); a single-word work
 // queue costs ~10 k serialized atomics per launch (90 per microsecond: slower than no chaining).
 constexpr int kTilesPerWave = 2;
-constexpr int kW2Bytes = 3 * (kChainK / 16) * 2 * 64 * 16;    // 24 576
-constexpr int kW3Bytes = 3 * (kChainK / 16) * 2 * 128 * 16;   // 49 152
-constexpr int kTabBytes = 64 * 16 + 64 * 8;                   // w1 rows (float4) + (sc1, sh1)
-constexpr int kImgBytes = kW2Bytes + kW3Bytes + kTabBytes;    // global image: [W2][W3T][tables]
+// the global image [W2][W3T][w1 rows (float4)][(sc1, sh1)]: mlp_frag.h (kLin4*)
+constexpr int kW2Bytes = kLin4ImgA, kW3Bytes = kLin4ImgB;
 
 // One launch per forward: the weights as fragment-ordered bf16 images (exact three-term split)
 // and the first layer's tables, in the order the passes hold them in LDS.
@@ -118,10 +80,7 @@ chain_prep_kernel(const float *__restrict__ w1, const float *__restrict__ sc1, c
     const int row = g / (T * 2), th = g % (T * 2), t = th >> 1, hh = th & 1;
     const float *src = w2 + (size_t)row * kChainK + 16 * t + 8 * hh;
     const Split3 s = split3(*reinterpret_cast<const float4 *>(src), *reinterpret_cast<const float4 *>(src + 4));
-    char *dst = img + img_off<64>(0, t, hh, row);
-    *reinterpret_cast<bf16x8 *>(dst) = s.hi;
-    *reinterpret_cast<bf16x8 *>(dst + kW2Bytes / 3) = s.mid;
-    *reinterpret_cast<bf16x8 *>(dst + 2 * (kW2Bytes / 3)) = s.lo;
+    store_frag(img + img_off<kChainK, 64>(0, t, hh, row), kW2Bytes / 3, s);
   } else if (g < (64 + 128) * T * 2) {
     // W3 as the B operand of the T form: row = output channel, k slot (t, h, e) <-> input channel
     // 16 t + 8 (e >> 2) + 4 h + (e & 3) -- the order layer 2's accumulators hold them in
@@ -129,14 +88,11 @@ chain_prep_kernel(const float *__restrict__ w1, const float *__restrict__ sc1, c
     const int row = q / (T * 2), th = q % (T * 2), t = th >> 1, hh = th & 1;
     const float *src = w3 + (size_t)row * kChainK + 16 * t + 4 * hh;
     const Split3 s = split3(*reinterpret_cast<const float4 *>(src), *reinterpret_cast<const float4 *>(src + 8));
-    char *dst = img + kW2Bytes + img_off<128>(0, t, hh, row);
-    *reinterpret_cast<bf16x8 *>(dst) = s.hi;
-    *reinterpret_cast<bf16x8 *>(dst + kW3Bytes / 3) = s.mid;
-    *reinterpret_cast<bf16x8 *>(dst + 2 * (kW3Bytes / 3)) = s.lo;
+    store_frag(img + kW2Bytes + img_off<kChainK, 128>(0, t, hh, row), kW3Bytes / 3, s);
   } else if (g < (64 + 128) * T * 2 + 64) {
     const int ch = g - (64 + 128) * T * 2;
-    reinterpret_cast<float4 *>(img + kW2Bytes + kW3Bytes)[ch] = *reinterpret_cast<const float4 *>(w1 + (size_t)ch * 4);
-    reinterpret_cast<float2 *>(img + kW2Bytes + kW3Bytes + 1024)[ch] = make_float2(sc1[ch], sh1[ch]);
+    reinterpret_cast<float4 *>(img + kLin4TabW)[ch] = *reinterpret_cast<const float4 *>(w1 + (size_t)ch * 4);
+    reinterpret_cast<float2 *>(img + kLin4TabC)[ch] = make_float2(sc1[ch], sh1[ch]);
   }
 }
 
@@ -149,8 +105,8 @@ __global__ void __launch_bounds__(256, FULL ? 2 : 4) chain_lin4_kernel(const Cha
   extern __shared__ __attribute__((aligned(16))) char lds[];
   char *w2img = lds, *w3img = lds + W2_BYTES;
   float4 *w1tab = reinterpret_cast<float4 *>(lds + W2_BYTES + W3_BYTES);          // [64]
-  float2 *c1tab = reinterpret_cast<float2 *>(lds + W2_BYTES + W3_BYTES + 1024);   // [64] sc1, sh1
-  float2 *c2tab = reinterpret_cast<float2 *>(lds + W2_BYTES + W3_BYTES + 1536);   // [64] sc2, sh2
+  float2 *c1tab = reinterpret_cast<float2 *>(lds + W2_BYTES + W3_BYTES + (kLin4TabC - kLin4TabW));  // [64] sc1, sh1
+  float2 *c2tab = reinterpret_cast<float2 *>(lds + W2_BYTES + W3_BYTES + kLin4TabBytes);            // [64] sc2, sh2
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
@@ -159,9 +115,9 @@ __global__ void __launch_bounds__(256, FULL ? 2 : 4) chain_lin4_kernel(const Cha
   {
     const uint4 *src = reinterpret_cast<const uint4 *>(a.wimg);
     uint4 *dst = reinterpret_cast<uint4 *>(lds);
-    constexpr int HEAD = (kW2Bytes + (FULL ? kW3Bytes : 0)) / 16, TAB = kTabBytes / 16;
+    constexpr int HEAD = (kW2Bytes + (FULL ? kW3Bytes : 0)) / 16, TAB = kLin4TabBytes / 16;
     for (int i = tid; i < HEAD; i += 256) dst[i] = src[i];
-    if (tid < TAB) dst[HEAD + tid] = src[(kW2Bytes + kW3Bytes) / 16 + tid];
+    if (tid < TAB) dst[HEAD + tid] = src[kLin4TabW / 16 + tid];
     if constexpr (FULL) {
       if (tid >= 64 && tid < 128) c2tab[tid - 64] = make_float2(a.sc2[tid - 64], a.sh2[tid - 64]);
     }
@@ -226,7 +182,7 @@ __global__ void __launch_bounds__(256, FULL ? 2 : 4) chain_lin4_kernel(const Cha
     };
     auto load_w2 = [&](int t, Split3 (&w)[2]) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i) w[i] = lds_frag(w2lane + img_off<M2>(0, t, 0, 32 * i), W2_TERM);
+      for (int i = 0; i < 2; ++i) w[i] = lds_frag(w2lane + img_off<kChainK, M2>(0, t, 0, 32 * i), W2_TERM);
     };
     {
       Split3 sc = prep_a1(0), wc[2];
@@ -306,7 +262,7 @@ __global__ void __launch_bounds__(256, FULL ? 2 : 4) chain_lin4_kernel(const Cha
       };
       auto load_w3 = [&](int t, int j0, Split3 (&w)[2]) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) w[i] = lds_frag(w3lane + img_off<M3>(0, t, 0, 32 * (j0 + i)), W3_TERM);
+        for (int i = 0; i < 2; ++i) w[i] = lds_frag(w3lane + img_off<kChainK, M3>(0, t, 0, 32 * (j0 + i)), W3_TERM);
       };
       {
         f32x16 lo2[2], hi2[2];
@@ -434,17 +390,6 @@ __global__ void __launch_bounds__(256, FULL ? 2 : 4) chain_lin4_kernel(const Cha
   }
 }
 
-int chain_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 bool chain_shape_ok(int b, int r, int ns) {
   return b > 0 && r > 0 && r % (32 * 4 * kTilesPerWave) == 0 && (ns == 16 || ns == 32 || ns == 64) &&
          r % ns == 0 && (long long)b * (r / 32) < (1LL << 30);
@@ -455,32 +400,13 @@ int chain_workgroups(int b, int r) { return (int)((long long)b * (r / 32) / (4 *
 
 template <typename Kern>
 void chain_launch(Kern kern, int wgs, size_t lds_bytes, hipStream_t stream, const ChainArgs &args) {
-  // (every instantiation has the same pointer TYPE: remember the kernels by address)
-  static std::mutex mu;
-  static std::set<const void *> done;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (done.insert(reinterpret_cast<const void *>(kern)).second)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  }
+  pn2_allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes);
   hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), lds_bytes, stream, args);
 }
 
 // ---- BatchNorm coefficients from the workgroups' equal-count (mean, M2) pairs (part, channel, 2):
 // one wave per channel, sums in double around the first part's mean (no cancellation):
 // mean = ref + s1 / P, M2 = sum M2_i + n_part * (s2 - s1^2 / P)
-__device__ __forceinline__ double chain_wave_sum(double v) {
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, off, kWave);
-    hi = __shfl_xor(hi, off, kWave);
-    v += __hiloint2double(hi, lo);
-  }
-  return v;
-}
-
 __global__ void __launch_bounds__(256)
 chain_finalize_kernel(int c, int parts, int n_part, const float *__restrict__ pairs,
                       const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
@@ -508,7 +434,7 @@ chain_finalize_kernel(int c, int parts, int n_part, const float *__restrict__ pa
     const double d = (double)v.x - ref;
     s1 += d; s2 += d * d; sm2 += (double)v.y;
   }
-  s1 = chain_wave_sum(s1); s2 = chain_wave_sum(s2); sm2 = chain_wave_sum(sm2);
+  s1 = wave_sum(s1); s2 = wave_sum(s2); sm2 = wave_sum(sm2);
   if (lane == 0) { red[wave][0] = s1; red[wave][1] = s2; red[wave][2] = sm2; }
   __syncthreads();
   if (tid != 0) return;
@@ -548,7 +474,7 @@ MLP_API int mlp_chain_lin4_parts(int b, int r, int m3, int ns, int *cols_per_par
 }
 
 // bytes of the weight-image scratch mlp_chain_lin4_prepare fills
-MLP_API size_t mlp_chain_lin4_image_bytes(void) { return (size_t)kImgBytes; }
+MLP_API size_t mlp_chain_lin4_image_bytes(void) { return (size_t)kLin4ImgBytes; }
 
 // The weights of the module as fragment-ordered bf16 images (exact three-term split) + the first
 // layer's tables -> img (mlp_chain_lin4_image_bytes(), 16-byte aligned); once per forward, before
@@ -573,7 +499,7 @@ MLP_API int mlp_chain_lin4_stats(int b, int r, int ns, const float *x4, const vo
   ChainArgs a = {};
   a.r = r; a.tiles_per_cloud = r / 32;
   a.x4 = x4; a.wimg = (const char *)img; a.pairs = pairs2;
-  const size_t lds_bytes = kW2Bytes + kTabBytes + 512;
+  const size_t lds_bytes = kW2Bytes + kLin4TabBytes + 512;  // + (sc2, sh2)
   chain_launch(chain_lin4_kernel<4, 32, false>, chain_workgroups(b, r), lds_bytes, (hipStream_t)stream_, a);
   return pn2_launch_status();
 }
@@ -592,7 +518,7 @@ MLP_API int mlp_chain_lin4_forward(int b, int r, int ns, const float *x4, const 
   a.x4 = x4; a.wimg = (const char *)img; a.sc2 = sc2; a.sh2 = sh2;
   a.gamma3 = gamma3; a.y2 = y2; a.y3 = y3; a.pairs = pairs3; a.ext = ext;
   a.ext_plane = (size_t)b * 128 * (r / ns);
-  const size_t lds_bytes = kImgBytes + 512;
+  const size_t lds_bytes = kLin4ImgBytes + 512;  // + (sc2, sh2)
   hipStream_t stream = (hipStream_t)stream_;
   const int wgs = chain_workgroups(b, r);
   if (ns == 16) chain_launch(chain_lin4_kernel<4, 16, true>, wgs, lds_bytes, stream, a);

@@ -10,7 +10,7 @@
 // The MFMA forms are those of mlp_chain.hip (its header comment): a layer in N form leaves its
 // activation in registers as the next layer's operand, the last layer runs in T form so that
 // BatchNorm + ReLU + the max over nsample are in-lane.  Every fp32 product is six bf16 MFMAs on
-// the exact three-term split (mlp_operand.h).
+// the exact three-term split (mlp_frag.h).
 //
 // Two input forms:
 //   LIN4 (SA1, 4 -> 64 -> 64 -> 128): layer 0 recomputed per element from the 4-channel grouped
@@ -26,42 +26,8 @@
 //        both images in LDS exists at 256 outputs.
 #include "common.h"
 #include "mlp_operand.h"
-#include <mutex>
-#include <set>
 
 namespace {
-
-// fragment (term, step t, half h, row) of a K-deep weight image of R rows, bytes
-template <int K, int R>
-__device__ __forceinline__ int ev_off(int term, int t, int h, int row) {
-  return (((term * (K / 16) + t) * 2 + h) * R + row) * 16;
-}
-
-__device__ __forceinline__ Split3 ev_frag(const char *p, int term_stride) {
-  Split3 s;
-  s.hi = *reinterpret_cast<const bf16x8 *>(p);
-  s.mid = *reinterpret_cast<const bf16x8 *>(p + term_stride);
-  s.lo = *reinterpret_cast<const bf16x8 *>(p + 2 * term_stride);
-  return s;
-}
-
-// acc[i] += w[i] x s (N form) or s x w[i] (T form): the six significant partial products, small
-// ones first (mlp_chain.hip mfma6)
-template <int NB, bool TFORM, bool FIRST = false>
-__device__ __forceinline__ void ev_mfma6(f32x16 (&acc)[NB], const Split3 &s, const Split3 (&w)[NB]) {
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#define EV_STEP(WT, ST, C0)                                                                        \
-  _Pragma("unroll") for (int i = 0; i < NB; ++i)                                                  \
-    acc[i] = TFORM ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(s.ST, w[i].WT, (C0) ? zero : acc[i], 0, 0, 0) \
-                   : __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[i].WT, s.ST, (C0) ? zero : acc[i], 0, 0, 0)
-  EV_STEP(lo, hi, FIRST);
-  EV_STEP(hi, lo, false);
-  EV_STEP(mid, mid, false);
-  EV_STEP(mid, hi, false);
-  EV_STEP(hi, mid, false);
-  EV_STEP(hi, hi, false);
-#undef EV_STEP
-}
 
 // relu(bn(.)) of eight N-form accumulator registers (block t >> 1, registers 8 (t & 1) + e), the
 // k slots of step t of the next (T-form) layer: channel 16 t + 8 (e >> 2) + 4 h + (e & 3)
@@ -109,12 +75,8 @@ __device__ __forceinline__ void ev_pool_store(float (&best)[NB][2], float *out, 
 }
 
 // ================================ LIN4 form (SA1) ===============================================
-constexpr int kL4K = 64;                                   // channels entering layers 1 and 2
-constexpr int kL4W1Bytes = 3 * (kL4K / 16) * 2 * 64 * 16;  // 24 576  (mlp_chain.hip kW2Bytes)
-constexpr int kL4W2Bytes = 3 * (kL4K / 16) * 2 * 128 * 16; // 49 152  (kW3Bytes)
-constexpr int kL4TabBytes = 64 * 16 + 64 * 8;              // w0 rows (float4) + (sc0, sh0)
-constexpr int kL4ImgBytes = kL4W1Bytes + kL4W2Bytes + kL4TabBytes;
-constexpr int kL4Lds = kL4ImgBytes + 64 * 8 + 128 * 8;     // + (sc1, sh1) + (sc2, sh2)
+// the image [W1][W2T][w0 rows (float4)][(sc0, sh0)]: mlp_frag.h (kLin4*)
+constexpr int kL4Lds = kLin4ImgBytes + 64 * 8 + 128 * 8;   // + (sc1, sh1) + (sc2, sh2)
 constexpr int kL4TilesPerWave = 2;
 
 struct Lin4Args {
@@ -128,21 +90,21 @@ struct Lin4Args {
 
 template <int NS>
 __global__ void __launch_bounds__(256, 2) eval_lin4_kernel(const Lin4Args a) {
-  constexpr int M1 = 64, M2 = 128, M2B = 4, T = kL4K / 16;
-  constexpr int W1_TERM = kL4W1Bytes / 3, W2_TERM = kL4W2Bytes / 3;
+  constexpr int M1 = 64, M2 = 128, M2B = 4, T = kLin4K / 16;
+  constexpr int W1_TERM = kLin4ImgA / 3, W2_TERM = kLin4ImgB / 3;
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  char *w1img = lds, *w2img = lds + kL4W1Bytes;
-  float4 *w0tab = reinterpret_cast<float4 *>(lds + kL4W1Bytes + kL4W2Bytes);
-  float2 *c0tab = reinterpret_cast<float2 *>(lds + kL4W1Bytes + kL4W2Bytes + 1024);
-  float2 *c1tab = reinterpret_cast<float2 *>(lds + kL4ImgBytes);
-  float2 *c2tab = reinterpret_cast<float2 *>(lds + kL4ImgBytes + 64 * 8);
+  char *w1img = lds, *w2img = lds + kLin4ImgA;
+  float4 *w0tab = reinterpret_cast<float4 *>(lds + kLin4TabW);
+  float2 *c0tab = reinterpret_cast<float2 *>(lds + kLin4TabC);
+  float2 *c1tab = reinterpret_cast<float2 *>(lds + kLin4ImgBytes);
+  float2 *c2tab = reinterpret_cast<float2 *>(lds + kLin4ImgBytes + 64 * 8);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, h = lane >> 5;
   {
     const uint4 *src = reinterpret_cast<const uint4 *>(a.wimg);
     uint4 *dst = reinterpret_cast<uint4 *>(lds);
-    for (int i = tid; i < kL4ImgBytes / 16; i += 256) dst[i] = src[i];
+    for (int i = tid; i < kLin4ImgBytes / 16; i += 256) dst[i] = src[i];
     if (tid < 64) c1tab[tid] = make_float2(a.sc1[tid], a.sh1[tid]);
     if (tid < 128) c2tab[tid] = make_float2(a.sc2[tid], a.sh2[tid]);
   }
@@ -186,7 +148,7 @@ __global__ void __launch_bounds__(256, 2) eval_lin4_kernel(const Lin4Args a) {
     };
     auto load_w1 = [&](int t, Split3 (&w)[2]) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i) w[i] = ev_frag(w1lane + ev_off<kL4K, M1>(0, t, 0, 32 * i), W1_TERM);
+      for (int i = 0; i < 2; ++i) w[i] = lds_frag(w1lane + img_off<kLin4K, M1>(0, t, 0, 32 * i), W1_TERM);
     };
     {
       Split3 sc = prep0(0), wc[2];
@@ -199,8 +161,8 @@ __global__ void __launch_bounds__(256, 2) eval_lin4_kernel(const Lin4Args a) {
           sn = prep0(t + 1);
           load_w1(t + 1, wn);
         }
-        if (t == 0) ev_mfma6<2, false, true>(acc1, sc, wc);
-        else ev_mfma6<2, false>(acc1, sc, wc);
+        if (t == 0) mfma6<2, false, true>(acc1, sc, wc);
+        else mfma6<2, false>(acc1, sc, wc);
         sc = sn; wc[0] = wn[0]; wc[1] = wn[1];
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -209,7 +171,7 @@ __global__ void __launch_bounds__(256, 2) eval_lin4_kernel(const Lin4Args a) {
     f32x16 acc2[M2B];
     auto load_w2 = [&](int t, int j0, Split3 (&w)[2]) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i) w[i] = ev_frag(w2lane + ev_off<kL4K, M2>(0, t, 0, 32 * (j0 + i)), W2_TERM);
+      for (int i = 0; i < 2; ++i) w[i] = lds_frag(w2lane + img_off<kLin4K, M2>(0, t, 0, 32 * (j0 + i)), W2_TERM);
     };
     {
       f32x16 lo2[2], hi2[2];
@@ -221,12 +183,12 @@ __global__ void __launch_bounds__(256, 2) eval_lin4_kernel(const Lin4Args a) {
         load_w2(t, 2, wb);
         Split3 sn = sc;
         if (t + 1 < T) sn = ev_act_of_acc(acc1, t + 1, c1h);
-        if (t == 0) ev_mfma6<2, true, true>(lo2, sc, wa);
-        else ev_mfma6<2, true>(lo2, sc, wa);
+        if (t == 0) mfma6<2, true, true>(lo2, sc, wa);
+        else mfma6<2, true>(lo2, sc, wa);
         __builtin_amdgcn_sched_barrier(0);
         if (t + 1 < T) load_w2(t + 1, 0, wa);
-        if (t == 0) ev_mfma6<2, true, true>(hi2, sc, wb);
-        else ev_mfma6<2, true>(hi2, sc, wb);
+        if (t == 0) mfma6<2, true, true>(hi2, sc, wb);
+        else mfma6<2, true>(hi2, sc, wb);
         sc = sn;
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -279,20 +241,14 @@ eval_stored_prep_kernel(const float *__restrict__ w1, const float *__restrict__ 
     const int row = g / (T * 2), th = g % (T * 2), t = th >> 1, hh = th & 1;
     const float *src = w1 + (size_t)row * kStK + 16 * t + 8 * hh;
     const Split3 s = split3(*reinterpret_cast<const float4 *>(src), *reinterpret_cast<const float4 *>(src + 4));
-    char *dst = img + ((t * 2 + hh) * 128 + row) * 16;
-    *reinterpret_cast<bf16x8 *>(dst) = s.hi;
-    *reinterpret_cast<bf16x8 *>(dst + kStW1Bytes / 3) = s.mid;
-    *reinterpret_cast<bf16x8 *>(dst + 2 * (kStW1Bytes / 3)) = s.lo;
+    store_frag(img + ((t * 2 + hh) * 128 + row) * 16, kStW1Bytes / 3, s);
   } else if (g < (128 + c_out) * T * 2) {
     const int q = g - 128 * T * 2;
     const int row = q / (T * 2), th = q % (T * 2), t = th >> 1, hh = th & 1;
     const float *src = w2 + (size_t)row * kStK + 16 * t + 4 * hh;
     const Split3 s = split3(*reinterpret_cast<const float4 *>(src), *reinterpret_cast<const float4 *>(src + 8));
     const int term = st_w2_bytes(c_out) / 3;
-    char *dst = img + kStW1Bytes + ((t * 2 + hh) * c_out + row) * 16;
-    *reinterpret_cast<bf16x8 *>(dst) = s.hi;
-    *reinterpret_cast<bf16x8 *>(dst + term) = s.mid;
-    *reinterpret_cast<bf16x8 *>(dst + 2 * term) = s.lo;
+    store_frag(img + kStW1Bytes + ((t * 2 + hh) * c_out + row) * 16, term, s);
   }
 }
 
@@ -358,7 +314,7 @@ __global__ void __launch_bounds__(256, 1) eval_stored_kernel(const StoredArgs a)
     };
     auto load_w1 = [&](int t, Split3 (&w)[4]) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) w[i] = ev_frag(w1lane + ev_off<kStK, M1>(0, t, 0, 32 * i), W1_TERM);
+      for (int i = 0; i < 4; ++i) w[i] = lds_frag(w1lane + img_off<kStK, M1>(0, t, 0, 32 * i), W1_TERM);
     };
     {
       Split3 sc = prep0(0), wc[4];
@@ -370,8 +326,8 @@ __global__ void __launch_bounds__(256, 1) eval_stored_kernel(const StoredArgs a)
           sn = prep0(t + 1);
           load_w1(t + 1, wn);
         }
-        if (t == 0) ev_mfma6<4, false, true>(acc1, sc, wc);
-        else ev_mfma6<4, false>(acc1, sc, wc);
+        if (t == 0) mfma6<4, false, true>(acc1, sc, wc);
+        else mfma6<4, false>(acc1, sc, wc);
         sc = sn;
 #pragma unroll
         for (int i = 0; i < 4; ++i) wc[i] = wn[i];
@@ -395,7 +351,7 @@ __global__ void __launch_bounds__(256, 1) eval_stored_kernel(const StoredArgs a)
       const char *w2h = w2lane + hf * (HB * 32 * 16);
       auto load_w2 = [&](int t, Split3 (&w)[HB]) {
 #pragma unroll
-        for (int i = 0; i < HB; ++i) w[i] = ev_frag(w2h + ev_off<kStK, M2>(0, t, 0, 32 * i), W2_TERM);
+        for (int i = 0; i < HB; ++i) w[i] = lds_frag(w2h + img_off<kStK, M2>(0, t, 0, 32 * i), W2_TERM);
       };
       Split3 wc[HB];
       load_w2(0, wc);
@@ -403,8 +359,8 @@ __global__ void __launch_bounds__(256, 1) eval_stored_kernel(const StoredArgs a)
       for (int t = 0; t < T; ++t) {
         Split3 wn[HB];
         if (t + 1 < T) load_w2(t + 1, wn);
-        if (t == 0) ev_mfma6<HB, true, true>(acc2, a2[t], wc);
-        else ev_mfma6<HB, true>(acc2, a2[t], wc);
+        if (t == 0) mfma6<HB, true, true>(acc2, a2[t], wc);
+        else mfma6<HB, true>(acc2, a2[t], wc);
         if (t + 1 < T) {
 #pragma unroll
           for (int i = 0; i < HB; ++i) wc[i] = wn[i];
@@ -435,36 +391,18 @@ bool stored_shape_ok(int b, int c_in, int c_mid, int c_out, int m, int ns) {
   return r % 32 == 0 && (long long)b * r * 128 < (1LL << 31) * 4LL && (long long)b * r < (1LL << 31);
 }
 
-int eval_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 // tiles per wave of the STORED launch: two where the chip is covered anyway (fewer LDS image loads;
 // NS == 64 always, a group is two tiles), one otherwise
 int stored_tiles_per_wave(int b, int m, int ns) {
   const long long total_tiles = (long long)b * m * ns / 32;
-  return (ns == 64 || total_tiles >= 4 * 2 * 2 * eval_cus()) ? 2 : 1;
+  return (ns == 64 || total_tiles >= 4 * 2 * 2 * pn2_cu_count()) ? 2 : 1;
 }
 
 template <typename Kern, typename Args>
 void eval_launch(Kern kern, int wgs, size_t lds_bytes, hipStream_t stream, const Args &args) {
   // once per kernel (by address: the instantiations share one pointer type); the engine runs its
   // eager warm-up before it captures, so this happens outside any capture
-  static std::mutex mu;
-  static std::set<const void *> done;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (done.insert(reinterpret_cast<const void *>(kern)).second)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  }
+  pn2_allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds_bytes);
   hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), lds_bytes, stream, args);
 }
 

@@ -19,13 +19,6 @@ namespace {
 
 constexpr int kF4Rows = 64;
 
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __shfl_xor(lo, mask, kWave);
-  hi = __shfl_xor(hi, mask, kWave);
-  return __hiloint2double(hi, lo);
-}
-
 // G partials: 8 waves, wave w owns rows 8w .. 8w+7, a lane owns 4 consecutive columns per step
 constexpr int kF4Rpw = 8;  // rows per wave
 __global__ void __launch_bounds__(512, 2)

@@ -156,37 +156,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, unsig
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
 }
 
-// sum over the 32 lanes of each half-wave; the total lands in lanes 16..31 / 48..63
-__device__ __forceinline__ float half_wave_sum(float v) {
-#define HW_STEP(CTRL, RM) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, RM, 0xf, false))
-  HW_STEP(0xB1, 0xf);   // quad_perm [1,0,3,2]
-  HW_STEP(0x4E, 0xf);   // quad_perm [2,3,0,1]
-  HW_STEP(0x141, 0xf);  // row_half_mirror
-  HW_STEP(0x140, 0xf);  // row_mirror        -> every lane: the total of its row of 16
-  HW_STEP(0x142, 0xa);  // row_bcast:15 into rows 1 and 3 -> the total of the half-wave
-#undef HW_STEP
-  return v;
-}
-
-// the same butterfly with max / min: lanes 16..31 (48..63) end up with the extreme of lanes
-// 0..31 (32..63); masked-out rows keep their own value (old = v)
-template <bool MAXOP>
-__device__ __forceinline__ float half_wave_extreme(float v) {
-#define HX_STEP(CTRL, RM)                                                                        \
-  {                                                                                              \
-    const float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(                      \
-        __builtin_bit_cast(int, v), __builtin_bit_cast(int, v), CTRL, RM, 0xf, false));         \
-    v = MAXOP ? fmaxf(v, o) : fminf(v, o);                                                       \
-  }
-  HX_STEP(0xB1, 0xf);
-  HX_STEP(0x4E, 0xf);
-  HX_STEP(0x141, 0xf);
-  HX_STEP(0x140, 0xf);
-  HX_STEP(0x142, 0xa);
-#undef HX_STEP
-  return v;
-}
-
 // A_VEC: the rows of A are 16-byte aligned (lda % 4 == 0 and an aligned base)
 // STATS: the epilogue also reduces every output row over the tile's columns to a
 //        (mean, M2) pair for the BatchNorm that follows (one per row, cloud and column tile, all
@@ -579,7 +548,7 @@ gemm_nn2_kernel(int m_total, int k_total, int r, const float *__restrict__ a, in
 constexpr int KS = 64;  // K chunk of the small variant
 
 // X6: the chunk's 16 k-rows of a wave are ONE bf16 MFMA step; fragments gathered as eight 4-byte
-// reads per row block and split in registers (mlp_operand.h)
+// reads per row block and split in registers (mlp_frag.h)
 // A operand as a ready bf16 image (X6 only; mlp_weight_images_build): the three planes of the exact
 // split of A as [plane][row][reduction index], rows and reduction padded with zeros to multiples
 // of 64 -- for the forward the weight itself, for the data gradient its transpose.  A lane's MFMA
@@ -1271,7 +1240,7 @@ int launch_nn(int b, int m, int k, int r, const float *a, int lda, const Operand
 
 // ---- bf16 images of the weights (AImage) ---------------------------------------------------------
 // One launch for every weight of the table: workgroup = one 64 x 64 tile of one weight; the exact
-// three-term split of mlp_operand.h per element (bit for bit what split3 produces in the kernels
+// three-term split of mlp_frag.h per element (bit for bit what split3 produces in the kernels
 // that split on the fly), written in BOTH orders: [plane][m][k] for the forward, [plane][k][m] for
 // the data gradient.
 constexpr int kImageBatch = 24;
@@ -1299,10 +1268,8 @@ __global__ void __launch_bounds__(256) weight_images_kernel(const ImageBatch t) 
   for (int i = tid; i < 64 * 64; i += 256) {
     const int rr = i >> 6, cc = i & 63;
     const float x = (r0 + rr < m && c0 + cc < k) ? w[(size_t)(r0 + rr) * k + c0 + cc] : 0.f;
-    const float h = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u);
-    const float r1 = x - h;                                   // exact
-    const float md = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & 0xffff0000u);
-    const float lo = r1 - md;                                 // exact, at most 8 significant bits
+    float h, md, lo;
+    split_terms(x, h, md, lo);
     tile[0][rr][cc] = (unsigned short)(__builtin_bit_cast(unsigned, h) >> 16);
     tile[1][rr][cc] = (unsigned short)(__builtin_bit_cast(unsigned, md) >> 16);
     tile[2][rr][cc] = (unsigned short)(__builtin_bit_cast(unsigned, lo) >> 16);

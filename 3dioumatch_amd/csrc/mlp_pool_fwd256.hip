@@ -37,17 +37,9 @@
 #include "common.h"
 #include "mlp_operand.h"
 #include <stdlib.h>
-#include <mutex>
 #include <type_traits>
 
 namespace {
-
-typedef short f_bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f_bf16x4 f_lds_read_tr(const char *p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) f_bf16x4 *)(__attribute__((address_space(3))) char *)p);
-}
 
 constexpr int kFM = 256, kFK = 128, kFTN = 32;
 constexpr int kFRP = kFTN * 2;        // image row pitch (bytes): 64 -- see the note on bank conflicts below
@@ -122,17 +114,8 @@ __global__ void __launch_bounds__(512) pool_fwd256_kernel(const PoolFwdArgs a) {
     const float xv[4] = {x.x, x.y, x.z, x.w};
     float h[4], m[4], l[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float v = transform<OP_BNRELU>(xv[e], 0.f, rc);
-      h[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & 0xffff0000u);
-      const float r1 = v - h[e];
-      m[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & 0xffff0000u);
-      l[e] = r1 - m[e];
-    }
-    char *dst = base + (size_t)row * RP + seg_c * 2;
-    *reinterpret_cast<uint2 *>(dst) = make_uint2(pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]));
-    *reinterpret_cast<uint2 *>(dst + IMG) = make_uint2(pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]));
-    *reinterpret_cast<uint2 *>(dst + 2 * IMG) = make_uint2(pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]));
+    for (int e = 0; e < 4; ++e) split_terms(transform<OP_BNRELU>(xv[e], 0.f, rc), h[e], m[e], l[e]);
+    store_terms4<RP>(base, IMG, row, seg_c, h, m, l);
   };
   auto stage = [&](char *base) {
     stage_slice(base, seg_row, qx0, rc0);
@@ -142,16 +125,16 @@ __global__ void __launch_bounds__(512) pool_fwd256_kernel(const PoolFwdArgs a) {
 
   // transposing reads: the lane's fragment = column l31 of the chunk, k = 16 s + 8 lhi + 0..7
   const int tr_off = (8 * lhi + ((lane & 15) >> 2)) * RP + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
-  f_bf16x4 pf[2][3][2];  // ring of two k-steps' fragments
-  auto frag = [&](const char *Q, int s, f_bf16x4 (&dst)[3][2]) {
+  bf16x4 pf[2][3][2];  // ring of two k-steps' fragments
+  auto frag = [&](const char *Q, int s, bf16x4 (&dst)[3][2]) {
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       const char *p0 = Q + (size_t)t * IMG + (size_t)(16 * s) * RP + tr_off;
-      dst[t][0] = f_lds_read_tr(p0);
-      dst[t][1] = f_lds_read_tr(p0 + 4 * RP);
+      dst[t][0] = lds_read_tr(p0);
+      dst[t][1] = lds_read_tr(p0 + 4 * RP);
     }
   };
-  auto operand = [&](const f_bf16x4 (&src)[3][2]) {
+  auto operand = [&](const bf16x4 (&src)[3][2]) {
     Split3 sb;
     sb.hi = __builtin_shufflevector(src[0][0], src[0][1], 0, 1, 2, 3, 4, 5, 6, 7);
     sb.mid = __builtin_shufflevector(src[1][0], src[1][1], 0, 1, 2, 3, 4, 5, 6, 7);
@@ -207,21 +190,12 @@ __global__ void __launch_bounds__(512) pool_fwd256_kernel(const PoolFwdArgs a) {
       for (int e = 0; e < 4; ++e) sv[e] = transform<OP_BNRELU>(xv[e], 0.f, rc);
     } else if constexpr (n == 1 || n == 5) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        shh[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, sv[e]) & 0xffff0000u);
-        sv[e] = sv[e] - shh[e];
-      }
+      for (int e = 0; e < 4; ++e) split_top(sv[e], shh[e], sv[e]);
     } else if constexpr (n == 2 || n == 6) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        sm[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, sv[e]) & 0xffff0000u);
-        sl[e] = sv[e] - sm[e];
-      }
+      for (int e = 0; e < 4; ++e) split_top(sv[e], sm[e], sl[e]);
     } else if constexpr (n == 3 || n == 7) {
-      char *dst = Qn + (size_t)(seg_row + (n == 7 ? 64 : 0)) * RP + seg_c * 2;
-      *reinterpret_cast<uint2 *>(dst) = make_uint2(pack_hi16(shh[0], shh[1]), pack_hi16(shh[2], shh[3]));
-      *reinterpret_cast<uint2 *>(dst + IMG) = make_uint2(pack_hi16(sm[0], sm[1]), pack_hi16(sm[2], sm[3]));
-      *reinterpret_cast<uint2 *>(dst + 2 * IMG) = make_uint2(pack_hi16(sl[0], sl[1]), pack_hi16(sl[2], sl[3]));
+      store_terms4<RP>(Qn, IMG, seg_row + (n == 7 ? 64 : 0), seg_c, shh, sm, sl);
     } else if constexpr (n == 8) {
       qx0 = qf0; qx1 = qf1;
       fetch(clampc(ce + 4));
@@ -388,17 +362,6 @@ __global__ void __launch_bounds__(512) pool_fwd256_kernel(const PoolFwdArgs a) {
 #undef PF_PIECE
 }
 
-int pool_fwd256_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 }  // namespace
 
 // 1 when mlp_gemm_forward_stats_pool runs here: (m, k) = (256, 128), nsample 16 / 32, whole
@@ -421,26 +384,16 @@ int mlp_pool_fwd256_launch(int b, int r, int ns, const float *w, const MlpOperan
   a.r = r; a.chunks_per_cloud = r / kFTN; a.total_tiles = b * (r / 64); a.groups = r / ns;
   a.w = w; a.x = x.x; a.sc = x.scale; a.sh = x.shift; a.gamma = gamma; a.pairs = pairs; a.ext = ext; a.y = y;
   a.ext_plane = (size_t)b * kFM * (size_t)(r / ns);
-  int grid = pool_fwd256_cus();
+  int grid = pn2_cu_count();
   if (grid > a.total_tiles / 2) grid = a.total_tiles / 2;
   const size_t kLds = 3 * (size_t)kFBUF + (y != nullptr ? 8 * (size_t)kFTP : 0);
   constexpr size_t kLdsMax = 3 * (size_t)kFBUF + 8 * (size_t)kFTP;
-  static std::mutex mu;
-  static bool attr_set = false;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pool_fwd256_kernel<16, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pool_fwd256_kernel<32, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pool_fwd256_kernel<16, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pool_fwd256_kernel<32, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
-      attr_set = true;
-    }
-  }
+  // (all four forms, each allowed the STORE form's size)
+  for (const void *kern : {reinterpret_cast<const void *>(pool_fwd256_kernel<16, false>),
+                           reinterpret_cast<const void *>(pool_fwd256_kernel<32, false>),
+                           reinterpret_cast<const void *>(pool_fwd256_kernel<16, true>),
+                           reinterpret_cast<const void *>(pool_fwd256_kernel<32, true>)})
+    pn2_allow_dynamic_lds(kern, kLdsMax);
   if (y != nullptr) {
     if (ns == 16) hipLaunchKernelGGL((pool_fwd256_kernel<16, true>), dim3(grid), dim3(512), kLds, stream, a);
     else hipLaunchKernelGGL((pool_fwd256_kernel<32, true>), dim3(grid), dim3(512), kLds, stream, a);

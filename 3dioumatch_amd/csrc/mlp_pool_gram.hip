@@ -25,17 +25,9 @@
 // chunk); 32-column chunks; roles of equal matrix time, see the kernel.
 #include "common.h"
 #include "mlp_operand.h"
-#include <mutex>
 #include <type_traits>
 
 namespace {
-
-typedef short g_bf16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ g_bf16x4 g_lds_read_tr(const char *p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) g_bf16x4 *)(__attribute__((address_space(3))) char *)p);
-}
 
 constexpr int kGM = 128, kGK = 64;  // the layer: kGM outputs, kGK inputs
 
@@ -188,10 +180,8 @@ __global__ void __launch_bounds__(256, 1) pool_gram_bwd_kernel(const GramArgs a)
     const int s = hit ? sl : TN;
     s_written[buf] = s;
     const float adp = l_a3 * l_dp;
-    const float hf = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, adp) & 0xffff0000u);
-    const float r1 = adp - hf;
-    const float mf = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & 0xffff0000u);
-    const float lf = r1 - mf;
+    float hf, mf, lf;
+    split_terms(adp, hf, mf, lf);
     unsigned short *dst = reinterpret_cast<unsigned short *>(lds + (size_t)buf * BUF + (size_t)lc3 * RP) + s;
     dst[0] = (unsigned short)(__builtin_bit_cast(unsigned, hf) >> 16);
     dst[SIMG / 2] = (unsigned short)(__builtin_bit_cast(unsigned, mf) >> 16);
@@ -207,16 +197,10 @@ __global__ void __launch_bounds__(256, 1) pool_gram_bwd_kernel(const GramArgs a)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         v[e] = transform<OP_BNRELU>(xv[e], 0.f, qc[item]);
-        h[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v[e]) & 0xffff0000u);
-        const float r1 = v[e] - h[e];
-        m[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & 0xffff0000u);
-        l[e] = r1 - m[e];
+        split_terms(v[e], h[e], m[e], l[e]);
       }
       if (real) s2acc[item] += (v[0] + v[1]) + (v[2] + v[3]);
-      char *dst = base + 3 * SIMG + (size_t)row * RP + seg_c * 2;
-      *reinterpret_cast<uint2 *>(dst) = make_uint2(pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]));
-      *reinterpret_cast<uint2 *>(dst + QIMG) = make_uint2(pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]));
-      *reinterpret_cast<uint2 *>(dst + 2 * QIMG) = make_uint2(pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]));
+      store_terms4<RP>(base + 3 * SIMG, QIMG, row, seg_c, h, m, l);
       *reinterpret_cast<float4 *>(base + 3 * (SIMG + QIMG) + (size_t)row * RAWP + seg_c * 4) = qx[item];
     } else {
       stage_sparse(buf, real);
@@ -272,21 +256,12 @@ __global__ void __launch_bounds__(256, 1) pool_gram_bwd_kernel(const GramArgs a)
           if (next_real) s2acc[item] += (pv[0] + pv[1]) + (pv[2] + pv[3]);
         } else if (ph == 1) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            ph_[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, pv[e]) & 0xffff0000u);
-            pv[e] = pv[e] - ph_[e];
-          }
+          for (int e = 0; e < 4; ++e) split_top(pv[e], ph_[e], pv[e]);
         } else if (ph == 2) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            pm[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, pv[e]) & 0xffff0000u);
-            pl[e] = pv[e] - pm[e];
-          }
+          for (int e = 0; e < 4; ++e) split_top(pv[e], pm[e], pl[e]);
         } else if (ph == 3) {
-          char *dst = base + 3 * SIMG + (size_t)row * RP + seg_c * 2;
-          *reinterpret_cast<uint2 *>(dst) = make_uint2(pack_hi16(ph_[0], ph_[1]), pack_hi16(ph_[2], ph_[3]));
-          *reinterpret_cast<uint2 *>(dst + QIMG) = make_uint2(pack_hi16(pm[0], pm[1]), pack_hi16(pm[2], pm[3]));
-          *reinterpret_cast<uint2 *>(dst + 2 * QIMG) = make_uint2(pack_hi16(pl[0], pl[1]), pack_hi16(pl[2], pl[3]));
+          store_terms4<RP>(base + 3 * SIMG, QIMG, row, seg_c, ph_, pm, pl);
         } else {
           *reinterpret_cast<float4 *>(base + 3 * (SIMG + QIMG) + (size_t)row * RAWP + seg_c * 4) = qx[item];
           fetch_item(item, ahead);
@@ -307,17 +282,17 @@ __global__ void __launch_bounds__(256, 1) pool_gram_bwd_kernel(const GramArgs a)
       f32x16 accD;
 #pragma unroll
       for (int q = 0; q < 16; ++q) accD[q] = 0.f;
-      g_bf16x4 pf[2][3][2];
+      bf16x4 pf[2][3][2];
       // transposing reads of an image: for this lane's column, eight consecutive rows from 16 s on
-      auto frag = [&](const char *img, int term_bytes, int s, g_bf16x4 (&dst)[3][2]) {
+      auto frag = [&](const char *img, int term_bytes, int s, bf16x4 (&dst)[3][2]) {
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
           const char *p0 = img + (size_t)t * term_bytes + (size_t)(16 * s) * RP + tr_off;
-          dst[t][0] = g_lds_read_tr(p0);
-          dst[t][1] = g_lds_read_tr(p0 + 4 * RP);
+          dst[t][0] = lds_read_tr(p0);
+          dst[t][1] = lds_read_tr(p0 + 4 * RP);
         }
       };
-      auto operand = [&](const g_bf16x4 (&src)[3][2]) {
+      auto operand = [&](const bf16x4 (&src)[3][2]) {
         Split3 sb;
         sb.hi = __builtin_shufflevector(src[0][0], src[0][1], 0, 1, 2, 3, 4, 5, 6, 7);
         sb.mid = __builtin_shufflevector(src[1][0], src[1][1], 0, 1, 2, 3, 4, 5, 6, 7);
@@ -331,11 +306,11 @@ __global__ void __launch_bounds__(256, 1) pool_gram_bwd_kernel(const GramArgs a)
 #pragma unroll
       for (int q = 0; q < 16; ++q) accE[q] = 0.f;
       auto step_operand = [&](int g) -> const Split3 & { return g < K / 16 ? msp[g] : wsp[g - K / 16]; };
-      auto step_frag = [&](int g, g_bf16x4 (&dst)[3][2]) {
+      auto step_frag = [&](int g, bf16x4 (&dst)[3][2]) {
         if (g < K / 16) frag(Qc, QIMG, g, dst);
         else frag(Sc, SIMG, g - K / 16, dst);
       };
-      g_bf16x4 pg[2][3][2];
+      bf16x4 pg[2][3][2];
       step_frag(0, pf[0]);
       step_frag(1, pg[0]);
 #pragma unroll
@@ -525,20 +500,9 @@ pool_gram_dw_kernel(const float *__restrict__ w3, const float *__restrict__ qp,
   dw[e] = (float)((double)qp[c * 2] * acc + (double)qp[c * 2 + 1] * s2[k] + rr[e]);
 }
 
-int gram_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 int gram_workgroups(int b, int r) {
   const long long total = (long long)b * (r / 32);
-  long long g = gram_cus();
+  long long g = pn2_cu_count();
   if (g > total / 8) g = total / 8;
   return (int)(g < 1 ? 1 : g);
 }
@@ -606,16 +570,7 @@ MLP_API int mlp_pool_gram_backward(int b, int m, int k, int r, const float *w, c
   double *sums = reinterpret_cast<double *>(tail + ((reinterpret_cast<size_t>(tail) & 7) ? 1 : 0));
   hipLaunchKernelGGL(pool_gram_prep_kernel, dim3(16), dim3(256), 0, stream, w, P.coef, P.mean, P.invstd, qp,
                      m3, v);
-  static std::mutex mu;
-  static bool attr_set = false;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pool_gram_bwd_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGramLds);
-      attr_set = true;
-    }
-  }
+  pn2_allow_dynamic_lds(reinterpret_cast<const void *>(pool_gram_bwd_kernel), kGramLds);
   GramArgs a = {};
   a.r = r; a.total_chunks = b * (r / 32); a.chunks_per_cloud = r / 32; a.ns = P.ns; a.groups = P.groups;
   a.y2 = Q.x; a.sc2 = Q.scale; a.sh2 = Q.shift; a.mean2 = Q.mean; a.invstd2 = Q.invstd;

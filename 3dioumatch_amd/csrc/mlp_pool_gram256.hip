@@ -25,18 +25,11 @@
 #include "common.h"
 #include "mlp_operand.h"
 #include <stdlib.h>
-#include <mutex>
 #include <type_traits>
 
 namespace {
 
-typedef short h_bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned h_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ h_bf16x4 h_lds_read_tr(const char *p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) h_bf16x4 *)(__attribute__((address_space(3))) char *)p);
-}
 
 constexpr int kHM = 256, kHK = 128, kHTN = 32;
 constexpr int kHRP = kHTN * 2 + 16;          // image row pitch (bytes): 80
@@ -98,12 +91,10 @@ struct Gram256Args {
   float *part_c2, *part_s2, *part_r;     // per workgroup: 16384, 128, 32768 floats
 };
 
-// three bf16 terms of an fp32 value (truncation split, exact), as the upper halves of three words
-__device__ __forceinline__ void split_terms(float x, unsigned &h, unsigned &m, unsigned &l) {
-  const float hf = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & 0xffff0000u);
-  const float r1 = x - hf;
-  const float mf = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & 0xffff0000u);
-  const float lf = r1 - mf;
+// three bf16 terms of an fp32 value (split_terms), as the low halves of three words
+__device__ __forceinline__ void split_terms16(float x, unsigned &h, unsigned &m, unsigned &l) {
+  float hf, mf, lf;
+  split_terms(x, hf, mf, lf);
   h = __builtin_bit_cast(unsigned, hf) >> 16;
   m = __builtin_bit_cast(unsigned, mf) >> 16;
   l = __builtin_bit_cast(unsigned, lf) >> 16;
@@ -130,7 +121,7 @@ pool_gram256_pack_kernel(int groups, const int *__restrict__ argmax, const float
       const int am = argmax[at];
       const float dp = dpooled[at], ym = ymax[at];
       unsigned h, m, l;
-      split_terms(coef3[c * 3] * dp, h, m, l);
+      split_terms16(coef3[c * 3] * dp, h, m, l);
       const bool open = __fmaf_rn(ym, sc3[c], sh3[c]) > 0.f && (unsigned)am < 0xffffu;
       rec = make_uint2((open ? (unsigned)am : 0xffffu) | (h << 16), m | (l << 16));
     }
@@ -153,15 +144,9 @@ __device__ __forceinline__ float stage_a2_slice(char *base, int row, int seg_c, 
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     v[e] = transform<OP_BNRELU>(xv[e], 0.f, rc);
-    h[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v[e]) & 0xffff0000u);
-    const float r1 = v[e] - h[e];
-    m[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, r1) & 0xffff0000u);
-    l[e] = r1 - m[e];
+    split_terms(v[e], h[e], m[e], l[e]);
   }
-  char *dst = base + (size_t)row * kHRP + seg_c * 2;
-  *reinterpret_cast<uint2 *>(dst) = make_uint2(pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]));
-  *reinterpret_cast<uint2 *>(dst + kHQIMG) = make_uint2(pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]));
-  *reinterpret_cast<uint2 *>(dst + 2 * kHQIMG) = make_uint2(pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]));
+  store_terms4<kHRP>(base, kHQIMG, row, seg_c, h, m, l);
   if (RAWCOPY) *reinterpret_cast<float4 *>(base + 3 * kHQIMG + (size_t)row * kHRAWP + seg_c * 4) = x;
   return (v[0] + v[1]) + (v[2] + v[3]);
 }
@@ -276,21 +261,12 @@ __global__ void __launch_bounds__(256, 1) pool_gram256_dgrad_kernel(const Gram25
       for (int e = 0; e < 4; ++e) sv[e] = fmaxf(__fmaf_rn(xv[e], c2.x, c2.y), 0.f);
     } else if (ph == 1) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        sh[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, sv[e]) & 0xffff0000u);
-        sv[e] = sv[e] - sh[e];
-      }
+      for (int e = 0; e < 4; ++e) split_top(sv[e], sh[e], sv[e]);
     } else if (ph == 2) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        sm[e] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, sv[e]) & 0xffff0000u);
-        sl[e] = sv[e] - sm[e];
-      }
+      for (int e = 0; e < 4; ++e) split_top(sv[e], sm[e], sl[e]);
     } else if (ph == 3) {
-      char *dst = base + (size_t)row * RP + seg_c * 2;
-      *reinterpret_cast<uint2 *>(dst) = make_uint2(pack_hi16(sh[0], sh[1]), pack_hi16(sh[2], sh[3]));
-      *reinterpret_cast<uint2 *>(dst + QIMG) = make_uint2(pack_hi16(sm[0], sm[1]), pack_hi16(sm[2], sm[3]));
-      *reinterpret_cast<uint2 *>(dst + 2 * QIMG) = make_uint2(pack_hi16(sl[0], sl[1]), pack_hi16(sl[2], sl[3]));
+      store_terms4<RP>(base, QIMG, row, seg_c, sh, sm, sl);
     } else {
       *reinterpret_cast<float4 *>(base + 3 * QIMG + (size_t)row * RAWP + seg_c * 4) = qx[it];
     }
@@ -392,13 +368,13 @@ __global__ void __launch_bounds__(256, 1) pool_gram256_dgrad_kernel(const Gram25
       }
     }
     // the first fragments of the dense part (the a2 images of this chunk: nobody writes them now)
-    h_bf16x4 pf[2][2][3][2];
-    auto frag = [&](int s, h_bf16x4 (&dst)[3][2]) {
+    bf16x4 pf[2][2][3][2];
+    auto frag = [&](int s, bf16x4 (&dst)[3][2]) {
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
         const char *p0 = Qc + (size_t)t * QIMG + (size_t)(16 * s) * RP + tr_off;
-        dst[t][0] = h_lds_read_tr(p0);
-        dst[t][1] = h_lds_read_tr(p0 + 4 * RP);
+        dst[t][0] = lds_read_tr(p0);
+        dst[t][1] = lds_read_tr(p0 + 4 * RP);
       }
     };
     frag(0, pf[0][0]);
@@ -408,7 +384,7 @@ __global__ void __launch_bounds__(256, 1) pool_gram256_dgrad_kernel(const Gram25
     // ---- dense part: M3 (registers) * a2 (transposing reads of the images); behind its first MFMAs
     // the entries of S^T are cleared, the next chunk's written, the one after's requested
     {
-      auto operand = [&](const h_bf16x4 (&src)[3][2]) {
+      auto operand = [&](const bf16x4 (&src)[3][2]) {
         Split3 sb;
         sb.hi = __builtin_shufflevector(src[0][0], src[0][1], 0, 1, 2, 3, 4, 5, 6, 7);
         sb.mid = __builtin_shufflevector(src[1][0], src[1][1], 0, 1, 2, 3, 4, 5, 6, 7);
@@ -763,22 +739,11 @@ pool_gram256_dw_kernel(const float *__restrict__ w3, const float *__restrict__ q
     dw[c * kHK + k] = (float)((double)qp[c * 2] * (acc + part[k]) + (double)qp[c * 2 + 1] * s2[k] + rr[c * kHK + k]);
 }
 
-int gram256_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 // workgroups of the two passes: one per CU, at least `least` chunks each (the weight pass writes
 // 197 KB of partials per workgroup: it takes fewer, longer ranges)
 int gram256_workgroups(int b, int r, int least) {
   const long long total = (long long)b * (r / 32);
-  long long g = gram256_cus();
+  long long g = pn2_cu_count();
   if (g > total / least) g = total / least;
   return (int)(g < 1 ? 1 : g);
 }
@@ -837,22 +802,10 @@ int mlp_pool_gram256_launch(int b, int r, const float *w3, const MlpOperand &dy,
                      dy.invstd, qp, m3, v);
   hipLaunchKernelGGL(pool_gram256_pack_kernel, dim3((groups + 31) / 32, kHM / 32, b), dim3(256), 0, stream, groups,
                      dy.argmax, dy.dz, ymax, dy.coef, dy.scale, dy.shift, recs);
-  static std::mutex mu;
-  static bool attr_set = false;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pool_gram256_dgrad_kernel<16>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDgradLds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pool_gram256_dgrad_kernel<32>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDgradLds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pool_gram256_wgrad_kernel<16>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgradLds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pool_gram256_wgrad_kernel<32>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgradLds);
-      attr_set = true;
-    }
-  }
+  pn2_allow_dynamic_lds(reinterpret_cast<const void *>(pool_gram256_dgrad_kernel<16>), kDgradLds);
+  pn2_allow_dynamic_lds(reinterpret_cast<const void *>(pool_gram256_dgrad_kernel<32>), kDgradLds);
+  pn2_allow_dynamic_lds(reinterpret_cast<const void *>(pool_gram256_wgrad_kernel<16>), kWgradLds);
+  pn2_allow_dynamic_lds(reinterpret_cast<const void *>(pool_gram256_wgrad_kernel<32>), kWgradLds);
   Gram256Args a = {};
   a.r = r; a.total_chunks = b * (r / 32); a.chunks_per_cloud = r / 32; a.groups = groups;
   a.y2 = x.x; a.sc2 = x.scale; a.sh2 = x.shift; a.mean2 = x.mean; a.invstd2 = x.invstd;

@@ -57,6 +57,7 @@ pregather_unpack_kernel(int n, int m, int c, const float *__restrict__ dsrc, flo
 
 __device__ __forceinline__ float block_sum(float v, float *scratch) {  // all threads get the sum
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+  // (wave_sum, written out: as a call the kernels' instruction schedule changes)
 #pragma unroll
   for (int o = kWave / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
   __syncthreads();

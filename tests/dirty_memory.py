@@ -28,7 +28,7 @@ What is filled
 
 Every byte workspace of the bindings:
   mlp_chain_lin4_image_bytes           LISTED  [W2][W3T] bf16 images + float tables (w1 rows, sc1,
-                                               sh1): csrc/mlp_chain.hip kImgBytes, include/mlp_hip.h
+                                               sh1): csrc/mlp_frag.h kLin4ImgBytes, include/mlp_hip.h
                                                "fragment-ordered bf16 images"
   mlp_eval_stored_image_bytes          LISTED  "fragment-ordered bf16 images (exact three-term
                                                split)" of w1 and w2, nothing else

@@ -154,6 +154,23 @@ def test_host_side_shape_gates_of_the_round4_entry_points():
         assert need >= b * m * k and need % (m * k) == 0  # whole partial blocks, one per cloud at least
 
 
+def test_weight_image_sizes_follow_from_the_layout():
+    """A fragment-ordered weight image is 3 terms x rows x K x 2 bytes (csrc/mlp_frag.h).  The LIN4
+    image, written by mlp_chain.hip and read by mlp_eval_pool.hip too, adds the first layer's 64
+    float4 rows and 64 (scale, shift) pairs; the stored image is W1 (128 x 128) + W2 (c_out x 128).
+    Host functions: no device needed."""
+    pkg = load_pkg()
+    lib = ctypes.CDLL(os.path.join(os.path.dirname(pkg.__file__), "lib3dioumatch_hip.so"))
+    lin4 = lib.mlp_chain_lin4_image_bytes
+    lin4.restype = ctypes.c_size_t
+    assert lin4() == 3 * 64 * 64 * 2 + 3 * 128 * 64 * 2 + 64 * 16 + 64 * 8 == 75264
+    stored = lib.mlp_eval_stored_image_bytes
+    stored.restype = ctypes.c_size_t
+    assert stored(128) == 3 * 128 * 128 * 2 + 3 * 128 * 128 * 2 == 196608
+    assert stored(256) == 3 * 128 * 128 * 2 + 3 * 256 * 128 * 2 == 294912
+    assert stored(64) == 0
+
+
 def test_weight_reduction_queue_host_logic():
     """The queue behind mlp_defer_weight_reductions is host state: with nothing queued, switching it
     on and off launches nothing and returns 0 (no device needed), and the Python context restores
