@@ -205,6 +205,8 @@ _LOADER_SIGNATURES = {
     "scene_scan_batch_build": [_vp, _vp],
     "scene_scan_semi_build": [_vp, _vp],
     "scene_detections_pack": [_vp, _vp],
+    # raw ScanNet scans -> the preprocessed layout (include/scannet_raw_hip.h)
+    "scannet_raw_export": [_vp, _vp],
 }
 
 

@@ -36,6 +36,7 @@ import os
 import numpy as np
 import torch
 
+from .scannet_raw import read_ply_vertices
 from .scene_loader import (DRAW_EMA, DRAW_STUDENT, MAX_BATCH, SceneError, draw_key, epoch_plan,  # noqa: F401
                            eval_batches, explicit_indices, feed, launch, rotz, sample_indices, scene_offsets,
                            to_device, unit_uniform)
@@ -105,7 +106,7 @@ def augmentation(dataset, u):
 
 def _load_cloud(path):
     name = os.path.basename(path)
-    for suffix in ("_vert.npy", "_pc.npz", ".npy", ".npz"):
+    for suffix in ("_vert.npy", "_pc.npz", ".npy", ".npz", ".ply"):
         if name.endswith(suffix):
             name = name[:-len(suffix)]
             break
@@ -118,7 +119,9 @@ def _load_cloud(path):
             return name, f["pc"]
     if path.endswith(".npy"):
         return name, np.load(path)
-    raise SceneError("scan %s: %s is neither .npy nor .npz" % (name, path))
+    if path.endswith(".ply"):  # xyz or xyz rgb as the file has them: aligning a mesh is the caller's job
+        return name, read_ply_vertices(path)
+    raise SceneError("scan %s: %s is neither .npy, .npz nor .ply" % (name, path))
 
 
 def scan_prepare_gpu(cloud, offset, count):
@@ -195,8 +198,10 @@ class ScanStore(object):
 
     @classmethod
     def from_files(cls, paths, device, dataset="scannet", names=None):
-        """`.npy` files, and `.npz` files with a `pc` member; the default names are the file names
-        without `_vert.npy` / `_pc.npz` / the extension."""
+        """`.npy` files, `.npz` files with a `pc` member and `.ply` files (the vertices' x y z, with red
+        green blue when the file has them, through scannet_raw.read_ply_vertices; the coordinates are
+        used as they are); the default names are the file names without `_vert.npy` / `_pc.npz` / the
+        extension."""
         loaded = [_load_cloud(p) for p in paths]
         if names is None:
             names = [n for n, _ in loaded]

@@ -26,6 +26,7 @@ import os
 import numpy as np
 import torch
 
+from . import scannet_raw as raw
 from .scene_loader import (DRAW_EMA, DRAW_STUDENT, MAX_BATCH, MAX_NUM_OBJ, SceneError, SceneLoader,  # noqa: F401
                            SceneStore, _read_list, draw_key, epoch_plan, eval_batches, feed, launch,
                            rotz, sample_indices, unit_uniform)
@@ -76,10 +77,14 @@ def read_scene(data_dir, name, use_color=False, use_height=True):
     for k, p in paths.items():
         if not os.path.exists(p):
             raise SceneError("scan %s: missing %s" % (name, p))
-    vert = np.load(paths["vert"])
-    ins = np.load(paths["ins_label"]).reshape(-1)
-    sem = np.load(paths["sem_label"]).reshape(-1)
-    bbox = np.load(paths["bbox"])
+    return scene_from_arrays(name, np.load(paths["vert"]), np.load(paths["ins_label"]),
+                             np.load(paths["sem_label"]), np.load(paths["bbox"]), use_color, use_height)
+
+
+def scene_from_arrays(name, vert, ins, sem, bbox, use_color=False, use_height=True):
+    """read_scene's scene from the four arrays themselves, as the files hold them or as
+    scannet_raw.export_raw_scans returns them."""
+    ins, sem = np.asarray(ins).reshape(-1), np.asarray(sem).reshape(-1)
     n = vert.shape[0] if vert.ndim else 0
     if vert.ndim != 2 or vert.shape[1] < (6 if use_color else 3):
         raise SceneError("scan %s: _vert.npy has shape %s, expected (n, %s)"
@@ -158,13 +163,51 @@ class ScanNetScenes(SceneStore):
     `device=None` keeps the host copy only (the CPU path)."""
 
     def __init__(self, data_dir, scan_names, device, use_color=False, use_height=True):
+        self._pack(data_dir, scan_names, lambda s: read_scene(data_dir, s, use_color, use_height), device,
+                   use_color, use_height)
+
+    def _pack(self, data_dir, scan_names, read, device, use_color, use_height):
         self.use_color, self.use_height = use_color, use_height
-        SceneStore.__init__(self, data_dir, scan_names,
-                            lambda s: read_scene(data_dir, s, use_color, use_height), device, box_cols=7)
+        self.raw_export = None
+        SceneStore.__init__(self, data_dir, scan_names, read, device, box_cols=7)
         self.ninst = np.array([s["ninst"] for s in self.scenes], np.int32)
         self.floor = np.array([s["floor"] for s in self.scenes], np.float32)
         if self.dev is not None:
             self.dev.update(inst=self._flat("inst"), sem=self._flat("sem"), ninst=self._upload(self.ninst))
+
+    @classmethod
+    def from_raw(cls, raw_dir, scan_names, label_map, device, use_color=False, use_height=True,
+                 max_points=50000, seed=0):
+        """The store of ScanNetScenes(exported_dir, ...) straight from raw scan folders
+        (`raw_dir/<scan>/<scan>_vh_clean_2.ply`, `.aggregation.json`, `_vh_clean_2.0.010000.segs.json`,
+        `.txt`): scannet_raw.export_raw_scans on `device` (None: its numpy restatement), a chunk of raw
+        scans in host memory at a time.  `label_map`: scannetv2-labels.combined.tsv's path, or the dict
+        of scannet_raw.read_label_map.  The exported arrays stay on the host for `export`."""
+        scan_names = list(scan_names)
+        if not scan_names:
+            raise SceneError("no scans to load from %s" % raw_dir)
+        if not isinstance(label_map, dict):
+            label_map = raw.read_label_map(label_map)
+        records = (raw.read_raw_scan(raw_dir, s, label_map) for s in scan_names)
+        exported = dict(zip(scan_names, raw.export_raw_scans(records, device, max_points, seed)))
+
+        def read(s):
+            e = exported[s]
+            return scene_from_arrays(s, e["vert"], e["ins_label"], e["sem_label"], e["bbox"], use_color, use_height)
+
+        self = cls.__new__(cls)
+        self._pack(raw_dir, scan_names, read, device, use_color, use_height)
+        self.raw_export = exported
+        return self
+
+    def export(self, out_dir):
+        """Write `<scan>_vert.npy`, `_ins_label.npy`, `_sem_label.npy` and `_bbox.npy` of every scan of
+        a from_raw store: the folder ScanNetScenes(out_dir, ...) reads."""
+        if self.raw_export is None:
+            raise RuntimeError("ScanNetScenes.export: only a from_raw store holds the arrays to write")
+        os.makedirs(out_dir, exist_ok=True)
+        for s in self.scan_names:
+            raw.save_export(out_dir, s, self.raw_export[s])
 
 
 # ------------------------------------------------------------------ host restatement

@@ -12,7 +12,10 @@ unlabeled scenes, EMA teacher).  --synthetic N trains on N seeded stand-in scans
 are summed on the device and read once per --print_interval steps; --no_guard / --clip_grad_norm
 choose what stands in front of the update (votenet/step.py).  --unlabeled_scans DIR takes the
 unlabeled scans of --stage semi from a folder of bare clouds, every `.npy` / `.npz` in it (xyz or xyz +
-rgb, no label files: votenet/scan_data.py), instead of the unlabeled split of --data_dir."""
+rgb, no label files: votenet/scan_data.py), instead of the unlabeled split of --data_dir.
+--raw_scans DIR --label_map TSV stand in place of --data_dir: DIR holds raw ScanNet scan folders
+(`<scan>/<scan>_vh_clean_2.ply`, ...), whose labels and boxes are built on the device at start-up
+(votenet/scannet_raw.py), so no preprocessing step comes before training."""
 import argparse
 import importlib
 import os
@@ -28,6 +31,9 @@ def parser():
     ap.add_argument('--synthetic', type=int, default=0, metavar='N', help='train on N synthetic scans')
     ap.add_argument('--dataset', default='scannet', choices=('scannet',), help='Dataset name.')
     ap.add_argument('--data_dir', default=None, help='preprocessed scans (scannet_train_detection_data)')
+    ap.add_argument('--raw_scans', default=None, metavar='DIR',
+                    help='raw ScanNet scan folders in place of --data_dir (needs --label_map)')
+    ap.add_argument('--label_map', default=None, metavar='TSV', help='scannetv2-labels.combined.tsv')
     ap.add_argument('--meta_dir', default=None, help='the split lists (scannet/meta_data)')
     ap.add_argument('--labeled_sample_list', default='scannetv2_train.txt')
     ap.add_argument('--unlabeled_scans', default=None, metavar='DIR',
@@ -125,9 +131,11 @@ def main(argv=None):
         unlabeled = train[len(train) // 2:] if opt['semi'] else None
         data_dir = tmp.name
     else:
-        if not flags.data_dir or not flags.meta_dir:
-            raise SystemExit("--data_dir and --meta_dir (or --synthetic N)")
-        data_dir = flags.data_dir
+        if flags.raw_scans and (flags.data_dir or not flags.label_map):
+            raise SystemExit("--raw_scans DIR --label_map TSV stand in place of --data_dir")
+        if not (flags.data_dir or flags.raw_scans) or not flags.meta_dir:
+            raise SystemExit("--data_dir (or --raw_scans and --label_map) and --meta_dir (or --synthetic N)")
+        data_dir = flags.data_dir or flags.raw_scans  # the splits need the scans' names only
         labeled = SD.labeled_split(data_dir, flags.meta_dir, flags.labeled_sample_list)
         split = opt['semi'] and flags.unlabeled_scans is None
         unlabeled = SD.unlabeled_split(data_dir, flags.meta_dir, flags.labeled_sample_list) if split else None
@@ -145,7 +153,11 @@ def main(argv=None):
         scans = SC.ScanStore.from_files(files, dev, "scannet")
         names = [s for s in names if s in set(labeled) | set(val)]
         unlabeled = None
-    scenes = SD.ScanNetScenes(data_dir, names, dev, use_color=flags.use_color, use_height=use_height)
+    if flags.raw_scans and not flags.synthetic:
+        scenes = SD.ScanNetScenes.from_raw(data_dir, names, flags.label_map, dev, use_color=flags.use_color,
+                                           use_height=use_height)
+    else:
+        scenes = SD.ScanNetScenes(data_dir, names, dev, use_color=flags.use_color, use_height=use_height)
     if tmp is not None:
         tmp.cleanup()  # the stores are resident
     loader = SD.ScanNetLoader(scenes, cfg, flags.num_point, seed=flags.seed or 0, labeled=labeled,
