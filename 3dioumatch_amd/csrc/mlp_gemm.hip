@@ -562,16 +562,89 @@ struct AImage {
   size_t plane;              // elements per plane
 };
 
+// ---- the cross-wave sum of the small kernels' epilogues ------------------------------------------
+// Each of the four waves holds the whole 64 x 64 tile -- 2 x 2 MFMA tiles of 32 x 32, tile t = 2 i + j in
+// acc[i][j] -- summed over its share of the reduction.  Wave w OWNS tile w: the three others write their
+// copy of it to LDS (a wave's 16 registers as four 16-byte pieces per lane; the copy of source wave s is
+// slot s < w ? s : s - 1 of the tile's three), the owner adds the four terms a0..a3 of the waves 0..3,
+// its own registers standing in their place, in ONE fixed association per kernel family (fp32 addition
+// commutes bit for bit, so the association alone decides the bits):
+//   TAIL_CHAIN  ((a0 + a1) + a2) + a3   the forward / data-gradient body
+//   TAIL_TREE   a0 + ((a1 + a2) + a3)   the direct weight gradient
+// and returns the sum of ITS tile; the caller then stores that tile's 16 rows x 32 columns per lane half.
+// Two phases (tiles 0, 1, then 2, 3) of 2 x 3 x 4 KB keep the buffer inside the staging buffers' 33 024 B;
+// one phase of 48 KB measured the same within 0.1 us per launch (profiles/small_tail.json).
+// Every wave passes every barrier.  The caller puts a barrier between its last LDS read and this.
+enum { TAIL_CHAIN = 0, TAIL_TREE = 1 };
+constexpr int kTailPhases = 2;
+constexpr int kTailFloats = (4 / kTailPhases) * 3 * 16 * 64;
+
+template <int FORM>
+__device__ __forceinline__ f32x16 tile_owner_sum(float *__restrict__ buf, const f32x16 (&acc)[2][2], int wave,
+                                                 int lane) {
+  float4 *b4 = reinterpret_cast<float4 *>(buf);
+  constexpr int TPP = 4 / kTailPhases;  // tiles per phase
+  f32x16 sum;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) sum[q] = 0.f;
+#pragma unroll
+  for (int ph = 0; ph < kTailPhases; ++ph) {
+    if (ph > 0) __syncthreads();  // the previous phase's copies are read
+#pragma unroll
+    for (int tt = 0; tt < TPP; ++tt) {
+      const int t = ph * TPP + tt;  // (t, not the wave, indexes the registers)
+      if (wave != t) {
+        const int slot = tt * 3 + (wave < t ? wave : wave - 1);
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          b4[(slot * 4 + g) * 64 + lane] =
+              make_float4(acc[t >> 1][t & 1][4 * g], acc[t >> 1][t & 1][4 * g + 1],
+                          acc[t >> 1][t & 1][4 * g + 2], acc[t >> 1][t & 1][4 * g + 3]);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int tt = 0; tt < TPP; ++tt) {
+      const int t = ph * TPP + tt;
+      if (wave == t) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          float v[4][4];  // [source wave][element]
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            if (s == t) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[s][e] = acc[t >> 1][t & 1][4 * g + e];
+            } else {
+              const float4 f = b4[((tt * 3 + (s < t ? s : s - 1)) * 4 + g) * 64 + lane];
+              v[s][0] = f.x; v[s][1] = f.y; v[s][2] = f.z; v[s][3] = f.w;
+            }
+          }
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            sum[4 * g + e] = FORM == TAIL_CHAIN ? ((v[0][e] + v[1][e]) + v[2][e]) + v[3][e]
+                                                : v[0][e] + ((v[1][e] + v[2][e]) + v[3][e]);
+        }
+      }
+    }
+  }
+  return sum;
+}
+
+constexpr int kSmallStageFloats = KS * (64 + 1) + KS * 64;  // the staged A (padded rows) and B chunk
+constexpr int kSmallLdsFloats = kSmallStageFloats > kTailFloats ? kSmallStageFloats : kTailFloats;
+
+// lds: kSmallLdsFloats floats of the workgroup, 16-byte aligned (staging, then the cross-wave sum)
 template <int MODE, bool A_TRANS, bool X6, bool AIMG = false>
-__device__ __forceinline__ void gemm_nn_small_body(int blk_x, int blk_y, int blk_z, int m_total, int k_total,
+__device__ __forceinline__ void gemm_nn_small_body(float *__restrict__ lds, int blk_x, int blk_y, int blk_z,
+                                                   int m_total, int k_total,
                                                    int r, const float *__restrict__ a, int lda,
                                                    OperandB opb, float *__restrict__ c,
                                                    size_t b_stride_in, size_t b_stride_out,
                                                    const AImage img = AImage{nullptr, 0, 0},
                                                    const float *__restrict__ bias = nullptr) {
   constexpr int TM = 64, TN = 64, LDA = TM + 1;
-  constexpr int STAGE = KS * LDA + KS * TN, REDUCE = 4 * 16 * 64;
-  __shared__ __attribute__((aligned(16))) float lds[STAGE > REDUCE ? STAGE : REDUCE];
+  static_assert(KS * LDA + KS * TN == kSmallStageFloats, "staging size");
   float *As = lds + KS * TN, *Bs = lds;  // Bs first: 16-byte aligned for the float4 stores
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r0 = blk_x * TN, m0 = blk_y * TM, b = blk_z;
@@ -686,54 +759,38 @@ __device__ __forceinline__ void gemm_nn_small_body(int blk_x, int blk_y, int blk
     }
     }
   }
-  // (bias: wave 0's 32 rows of it, requested here so that they arrive behind the cross-wave sum)
-  float bv[2][16];
-  if (bias != nullptr && wave == 0) {
+  // (forward forms: the MFMA loop keeps the tile in accumulation registers; pinned there, the epilogue
+  //  moves 16 of them at a time instead of all 64 at the loop's exit -- a wave per SIMD of occupancy)
+  if constexpr (!A_TRANS) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int row = m0 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-        bv[i][q] = bias[row < m_total ? row : m_total - 1];
-      }
+      for (int j = 0; j < 2; ++j) asm volatile("" : "+a"(acc[i][j]));
   }
-  for (int s = 1; s < 4; ++s) {  // waves 1..3 hand their accumulators to wave 0
-    __syncthreads();
-    if (wave == s) {
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);  // (scalar: the epilogue branches on it)
+  // (bias: the 16 rows of it that this wave stores, requested here so that they arrive behind the
+  //  cross-wave sum)
+  float bv[16];
+  if (bias != nullptr) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) lds[((i * 2 + j) * 16 + q) * 64 + lane] = acc[i][j][q];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) acc[i][j][q] += lds[((i * 2 + j) * 16 + q) * 64 + lane];
+    for (int q = 0; q < 16; ++q) {
+      const int row = m0 + (wave_s >> 1) * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+      bv[q] = bias[row < m_total ? row : m_total - 1];
     }
   }
-  if (wave != 0) return;
+  __syncthreads();  // the last chunk's MFMAs are done with the staging buffers
+  const f32x16 sum = tile_owner_sum<TAIL_CHAIN>(lds, acc, wave_s, lane);
   float *cb = c + (size_t)b * b_stride_out;
+  const int col = r0 + (wave_s & 1) * 32 + (lane & 31);
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = r0 + j * 32 + (lane & 31);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int row = m0 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-        if (row < m_total && col < r) {
-          // (bias: a convolution's, added to the finished sum as the separate pass over y did)
-          const float v = bias != nullptr ? acc[i][j][q] + bv[i][q] : acc[i][j][q];
-          __builtin_nontemporal_store(v, &cb[(size_t)row * r + col]);
-        }
-      }
+  for (int q = 0; q < 16; ++q) {
+    const int row = m0 + (wave_s >> 1) * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+    if (row < m_total && col < r) {
+      // (bias: a convolution's, added to the finished sum as the separate pass over y did)
+      const float v = bias != nullptr ? sum[q] + bv[q] : sum[q];
+      __builtin_nontemporal_store(v, &cb[(size_t)row * r + col]);
     }
+  }
 }
 
 template <int MODE, bool A_TRANS, bool X6 = false, bool AIMG = false>
@@ -741,7 +798,8 @@ __global__ void __launch_bounds__(256, (X6 && A_TRANS) ? 2 : 1)
 gemm_nn_small_kernel(int m_total, int k_total, int r, const float *__restrict__ a, int lda,
                      OperandB opb, float *__restrict__ c, size_t b_stride_in,
                      size_t b_stride_out, AImage img) {
-  gemm_nn_small_body<MODE, A_TRANS, X6, AIMG>((int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, m_total,
+  __shared__ __attribute__((aligned(16))) float lds[kSmallLdsFloats];
+  gemm_nn_small_body<MODE, A_TRANS, X6, AIMG>(lds, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, m_total,
                                               k_total, r, a, lda, opb, c, b_stride_in, b_stride_out, img);
 }
 
@@ -752,7 +810,8 @@ __global__ void __launch_bounds__(256, 1)
 gemm_nn_small_bias_kernel(int m_total, int k_total, int r, const float *__restrict__ a, int lda,
                           OperandB opb, float *__restrict__ c, size_t b_stride_in,
                           size_t b_stride_out, AImage img, const float *__restrict__ bias) {
-  gemm_nn_small_body<MODE, false, true, AIMG>((int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, m_total,
+  __shared__ __attribute__((aligned(16))) float lds[kSmallLdsFloats];
+  gemm_nn_small_body<MODE, false, true, AIMG>(lds, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, m_total,
                                               k_total, r, a, lda, opb, c, b_stride_in, b_stride_out, img,
                                               bias);
 }
@@ -904,15 +963,17 @@ gemm_wgrad_kernel(int m_total, int k_begin, int k_end, int k_total, int r, int r
 // (the first over its columns 0..7, the second over 8..15 -- any 16 columns form a k-step as long
 // as both operands agree).  A wave owns a 64 x 64 block of dW over its share of the workgroup's
 // column range (32-column chunks dealt round-robin to the four waves, the next chunk's loads in
-// flight during the MFMAs), the shares are added through LDS, one partial block per workgroup.
+// flight during the MFMAs), the shares are added through LDS (tile_owner_sum: every wave finishes and
+// stores one 32 x 32 tile), one partial block per workgroup.
 // For the small layers (FP modules, heads, the pre-gather first layers: a few thousand columns per
 // cloud, operands resident in L2) this replaces the LDS-staged kernel above at 0.4-0.6 of its time.
-template <int PMODE, int QMODE>
-__device__ __forceinline__ void wgrad_direct_body(const BlockId blk, int m_total, int k_total, int r,
+// lds: kTailFloats floats of the workgroup, 16-byte aligned
+template <int PMODE, int QMODE, bool SCALAR_WAVE>
+__device__ __forceinline__ void wgrad_direct_body(float *__restrict__ lds, const BlockId blk, int m_total,
+                                                  int k_total, int r,
                                                   int r_per_slice, int slices, OperandB opp,
                                                   OperandB opq, float *__restrict__ part,
                                                   size_t p_stride, size_t q_stride) {
-  __shared__ float red[4 * 16 * 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, half = lane >> 5;
   const int k0 = blk.x * 64, m0 = blk.y * 64;
@@ -976,43 +1037,27 @@ __device__ __forceinline__ void wgrad_direct_body(const BlockId blk, int m_total
         for (int j = 0; j < 2; ++j) mfma_x6(acc[i][j], sp[i], sq[j]);
     }
   }
-  // add the four waves' blocks: waves 1..3 -> LDS -> wave 0, one 32 x 32 tile at a time
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      __syncthreads();
-      if (wave != 0) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) red[((wave * 16) + q) * 64 + lane] = acc[i][j][q];
-      }
-      __syncthreads();
-      if (wave == 0) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          acc[i][j][q] += (red[(16 + q) * 64 + lane] + red[(32 + q) * 64 + lane]) + red[(48 + q) * 64 + lane];
-      }
-    }
-  if (wave != 0) return;
+  // add the four waves' blocks (no LDS traffic before this: no barrier ahead of the first write)
+  // (the epilogue's wave index: a scalar register in the pair kernel, the vector value in the kernel of
+  //  its own -- at the 256-register cap of the on-the-fly gradient operand each keeps the compiler's
+  //  spills at or below what they were with the other form: 12 / 28 and 12 / 36 bytes per lane)
+  const int wave_s = SCALAR_WAVE ? __builtin_amdgcn_readfirstlane(wave) : wave;
+  const f32x16 sum = tile_owner_sum<TAIL_TREE>(lds, acc, wave_s, lane);
   float *out = part + (size_t)blk.z * m_total * k_total;
+  const int col = k0 + (wave_s & 1) * 32 + l31;
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = k0 + j * 32 + l31;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int row = m0 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
-        if (row < m_total && col < k_total) out[(size_t)row * k_total + col] = acc[i][j][q];
-      }
-    }
+  for (int q = 0; q < 16; ++q) {
+    const int row = m0 + (wave_s >> 1) * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
+    if (row < m_total && col < k_total) out[(size_t)row * k_total + col] = sum[q];
+  }
 }
 
 template <int PMODE, int QMODE>
 __global__ void __launch_bounds__(256, 2)
 gemm_wgrad_direct_kernel(int m_total, int k_total, int r, int r_per_slice, int slices, OperandB opp,
                          OperandB opq, float *__restrict__ part, size_t p_stride, size_t q_stride) {
-  wgrad_direct_body<PMODE, QMODE>(xcd_block_id(), m_total, k_total, r, r_per_slice, slices, opp, opq,
+  __shared__ __attribute__((aligned(16))) float lds[kTailFloats];
+  wgrad_direct_body<PMODE, QMODE, false>(lds, xcd_block_id(), m_total, k_total, r, r_per_slice, slices, opp, opq,
                                   part, p_stride, q_stride);
 }
 
@@ -1032,12 +1077,13 @@ struct SmallPairArgs {
 template <int PMODE, int QMODE, bool X6D, bool AIMG = false>
 __global__ void __launch_bounds__(256, 2)
 gemm_small_backward_pair_kernel(SmallPairArgs t, OperandB opp, OperandB opq) {
+  __shared__ __attribute__((aligned(16))) float lds[kSmallLdsFloats];  // one buffer for either role
   const int id = (int)blockIdx.x;
   if (id < t.nd) {
     const int bx = id % t.dgx, by = (id / t.dgx) % t.dgy, bz = id / (t.dgx * t.dgy);
     // dQ (k rows) = W^T (k x m, read transposed) . P (m rows): the small kernel's (m_total, k_total)
     // are (k, m) here
-    gemm_nn_small_body<PMODE, true, X6D, AIMG>(bx, by, bz, t.k, t.m, t.r, t.w, t.k, opp, t.dq,
+    gemm_nn_small_body<PMODE, true, X6D, AIMG>(lds, bx, by, bz, t.k, t.m, t.r, t.w, t.k, opp, t.dq,
                                                (size_t)t.m * t.r, (size_t)t.k * t.r, t.wt_img);
   } else {
     const int wid = id - t.nd;
@@ -1045,7 +1091,7 @@ gemm_small_backward_pair_kernel(SmallPairArgs t, OperandB opp, OperandB opq) {
     blk.x = wid % t.wkx;
     blk.y = (wid / t.wkx) % t.wmy;
     blk.z = wid / (t.wkx * t.wmy);
-    wgrad_direct_body<PMODE, QMODE>(blk, t.m, t.k, t.r, t.per, t.slices, opp, opq, t.part,
+    wgrad_direct_body<PMODE, QMODE, true>(lds, blk, t.m, t.k, t.r, t.per, t.slices, opp, opq, t.part,
                                     (size_t)t.m * t.r, (size_t)t.k * t.r);
   }
 }
