@@ -207,6 +207,8 @@ _LOADER_SIGNATURES = {
     "scene_detections_pack": [_vp, _vp],
     # raw ScanNet scans -> the preprocessed layout (include/scannet_raw_hip.h)
     "scannet_raw_export": [_vp, _vp],
+    # raw SUN RGB-D depth clouds -> kept rows, floors, store rows (include/sunrgbd_raw_hip.h)
+    "scene_sunrgbd_raw_export": [_vp, _vp],
 }
 
 

@@ -2,7 +2,8 @@
 
 Both labeled stores (scannet_data.ScanNetScenes, sunrgbd_data.SunRgbdScenes) refuse a scan without
 its label files.  `ScanStore` takes bare (n, 3) xyz or (n, 6) xyz + rgb clouds -- arrays, `.npy`
-files or `.npz` files with a `pc` member (the SUN RGB-D `_pc.npz` layout) -- keeps the RAW float32
+files, `.npz` files with a `pc` member (the SUN RGB-D `_pc.npz` layout), `.ply` meshes' vertices or
+`.mat` depth clouds (the raw SUN RGB-D `depth/` layout) -- keeps the RAW float32
 rows in one flat device array with an offset / count table, and does in ONE launch at construction
 (scene_scan_prepare, include/scan_hip.h) everything that needs a pass over the points: the floor
 height np.percentile(z, 0.99) of every scan and its count of non-finite values.  The constructor reads
@@ -37,6 +38,7 @@ import numpy as np
 import torch
 
 from .scannet_raw import read_ply_vertices
+from .sunrgbd_raw import read_mat_points
 from .scene_loader import (DRAW_EMA, DRAW_STUDENT, MAX_BATCH, SceneError, draw_key, epoch_plan,  # noqa: F401
                            eval_batches, explicit_indices, feed, launch, rotz, sample_indices, scene_offsets,
                            to_device, unit_uniform)
@@ -106,7 +108,7 @@ def augmentation(dataset, u):
 
 def _load_cloud(path):
     name = os.path.basename(path)
-    for suffix in ("_vert.npy", "_pc.npz", ".npy", ".npz", ".ply"):
+    for suffix in ("_vert.npy", "_pc.npz", ".npy", ".npz", ".ply", ".mat"):
         if name.endswith(suffix):
             name = name[:-len(suffix)]
             break
@@ -121,7 +123,9 @@ def _load_cloud(path):
         return name, np.load(path)
     if path.endswith(".ply"):  # xyz or xyz rgb as the file has them: aligning a mesh is the caller's job
         return name, read_ply_vertices(path)
-    raise SceneError("scan %s: %s is neither .npy, .npz nor .ply" % (name, path))
+    if path.endswith(".mat"):  # a SUN RGB-D depth cloud: the variable `instance`, xyz or xyz rgb
+        return name, read_mat_points(path, columns=(3, 6))
+    raise SceneError("scan %s: %s is neither .npy, .npz, .ply nor .mat" % (name, path))
 
 
 def scan_prepare_gpu(cloud, offset, count):
@@ -198,10 +202,11 @@ class ScanStore(object):
 
     @classmethod
     def from_files(cls, paths, device, dataset="scannet", names=None):
-        """`.npy` files, `.npz` files with a `pc` member and `.ply` files (the vertices' x y z, with red
+        """`.npy` files, `.npz` files with a `pc` member, `.ply` files (the vertices' x y z, with red
         green blue when the file has them, through scannet_raw.read_ply_vertices; the coordinates are
-        used as they are); the default names are the file names without `_vert.npy` / `_pc.npz` / the
-        extension."""
+        used as they are) and `.mat` files (SUN RGB-D depth clouds: the variable `instance`, through
+        sunrgbd_raw.read_mat_points); the default names are the file names without `_vert.npy` /
+        `_pc.npz` / the extension."""
         loaded = [_load_cloud(p) for p in paths]
         if names is None:
             names = [n for n, _ in loaded]

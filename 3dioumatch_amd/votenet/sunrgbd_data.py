@@ -12,6 +12,8 @@ extraction, sunrgbd/sunrgbd_data.py:232-257).  `votes="boxes"` loads a folder th
 `_pc.npz` and `_bbox.npy`: the store then keeps no vote rows and the batch builder computes them per
 sampled point (`compute_votes` is the numpy restatement; `SunRgbdScenes.vote_rows` and
 `export_votes` give the whole store's rows, the latter in the reference's file layout).
+`SunRgbdScenes.from_raw` builds such a store straight from a raw `sunrgbd_trainval/` folder
+(votenet/sunrgbd_raw.py) and `export` writes its `_pc.npz` / `_bbox.npy`.
 
 What differs from the ScanNet loader: boxes are oriented (heading class / residual of 12 bins, size
 residuals from 2 x the stored half sizes), the vote labels are carried through the augmentation
@@ -31,6 +33,7 @@ import os
 import numpy as np
 import torch
 
+from . import sunrgbd_raw as raw
 from .scene_loader import (DRAW_EMA, DRAW_STUDENT, MAX_BATCH, MAX_NUM_OBJ, SceneError, SceneLoader,  # noqa: F401
                            SceneStore, _element, _read_list, draw_key, epoch_plan, eval_batches, feed,
                            launch, rotz, sample_indices, unit_uniform)
@@ -185,6 +188,45 @@ class SunRgbdScenes(SceneStore):
         self.floor = np.array([s["floor"] for s in self.scenes], np.float64)
         if self.dev is not None and self.votes == "file":
             self.dev["votes"] = self._flat("votes")
+        self.raw_export = None
+
+    @classmethod
+    def from_raw(cls, trainval_dir, scenes, device, use_color=False, use_height=True, use_v1=True,
+                 num_point=raw.NUM_POINT, seed=0, choices=None):
+        """The votes="boxes" store of SunRgbdScenes(exported_dir, ...) straight from a raw
+        `sunrgbd_trainval/` folder (`depth/%06d.mat`, `label_v1/%06d.txt` or, without use_v1,
+        `label/%06d.txt`): sunrgbd_raw.export_trainval on `device` (None: its numpy restatement), a
+        chunk of raw clouds in host memory at a time; nothing is written.  `scenes`: data indices or
+        their six-digit names, or the path of an index list such as train_data_idx.txt.  Scene number
+        i keeps `choices[name]` or the draw (seed, 0, i).  The kept rows and the box tables stay on
+        the host for `export`."""
+        names = raw.read_idx_list(scenes) if isinstance(scenes, str) else [raw.scene_name(s) for s in scenes]
+        if not names:
+            raise SceneError("no scans to load from %s" % trainval_dir)
+        records = (raw.read_trainval_scene(trainval_dir, s, use_v1) for s in names)
+        exported = dict(zip(names, raw.export_trainval(records, device, num_point, seed, choices)))
+        cols = [0, 1, 2] + ([3, 4, 5] if use_color else []) + ([6] if use_height else [])
+
+        def read(s):
+            e = exported[s]
+            return {"name": s, "cloud": np.ascontiguousarray(e["rows"][:, cols]), "floor": float(e["floor"]),
+                    "votes": None, "boxes": e["bbox"], "dtype": str(e["pc"].dtype)}
+
+        self = cls.__new__(cls)
+        self.votes, self.use_color, self.use_height = "boxes", use_color, use_height
+        SceneStore.__init__(self, trainval_dir, names, read, device, box_cols=8)
+        self.floor = np.array([s["floor"] for s in self.scenes], np.float64)
+        self.raw_export = {s: {"pc": e["pc"], "bbox": e["bbox"]} for s, e in exported.items()}
+        return self
+
+    def export(self, out_dir):
+        """Write `<name>_pc.npz` and `<name>_bbox.npy` of every scene of a from_raw store; with
+        export_votes(out_dir) the folder loads in the reference and as a "file" store."""
+        if self.raw_export is None:
+            raise RuntimeError("SunRgbdScenes.export: only a from_raw store holds the arrays to write")
+        os.makedirs(out_dir, exist_ok=True)
+        for s in self.scan_names:
+            raw.save_export(out_dir, s, self.raw_export[s])
 
     def vote_rows(self):
         """The (P, 10) float32 vote rows of the whole store on the device, in the reference's layout

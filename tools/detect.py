@@ -1,11 +1,11 @@
 """Boxes for scans without labels: the front end of votenet/detect.py.
 
-    python tools/detect.py --checkpoint log/checkpoint.tar --out boxes scans/          # every .npy / .npz / .ply
+    python tools/detect.py --checkpoint log/checkpoint.tar --out boxes scans/          # every .npy / .npz / .ply / .mat
     python tools/detect.py --checkpoint log/checkpoint.tar --out boxes a.npy b_pc.npz --dataset sunrgbd
     python tools/detect.py --synthetic 16 --out /tmp/boxes                             # no data, seeded weights
 
 Inputs are (n, 3) xyz or (n, 6) xyz + rgb clouds: `.npy` files, `.npz` files with a `pc` member, `.ply`
-files (their vertices, as they are), or a directory of them.  --num_point / --use_color / --no_height /
+files (their vertices, as they are), `.mat` depth clouds (SUN RGB-D's `instance`), or a directory of them.  --num_point / --use_color / --no_height /
 --num_target must be those the checkpoint was trained with (tools/train.py); the eval flags are train.py's eval_config_dict keys.
 --out gets one <name>.npz per scan (votenet/detect.py: Detections.save)."""
 import argparse
@@ -19,7 +19,7 @@ FIRST_WEIGHT = 'backbone_net.sa1.mlp_module.layer0.conv.weight'
 
 def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('inputs', nargs='*', help='cloud files (.npy, .npz with pc, .ply) or directories of them')
+    ap.add_argument('inputs', nargs='*', help='cloud files (.npy, .npz with pc, .ply, .mat) or directories of them')
     ap.add_argument('--checkpoint', default=None, help="a tools/train.py checkpoint ('model_state_dict')")
     ap.add_argument('--dataset', default='scannet', choices=('scannet', 'sunrgbd'))
     ap.add_argument('--num_point', type=int, default=None, help='Point Number [40000 scannet / 20000 sunrgbd]')
@@ -69,7 +69,7 @@ def cloud_files(inputs):
     paths = []
     for p in inputs:
         if os.path.isdir(p):
-            paths += sorted(os.path.join(p, f) for f in os.listdir(p) if f.endswith(('.npy', '.npz', '.ply')))
+            paths += sorted(os.path.join(p, f) for f in os.listdir(p) if f.endswith(('.npy', '.npz', '.ply', '.mat')))
         else:
             paths.append(p)
     return paths

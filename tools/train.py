@@ -15,7 +15,23 @@ unlabeled scans of --stage semi from a folder of bare clouds, every `.npy` / `.n
 rgb, no label files: votenet/scan_data.py), instead of the unlabeled split of --data_dir.
 --raw_scans DIR --label_map TSV stand in place of --data_dir: DIR holds raw ScanNet scan folders
 (`<scan>/<scan>_vh_clean_2.ply`, ...), whose labels and boxes are built on the device at start-up
-(votenet/scannet_raw.py), so no preprocessing step comes before training."""
+(votenet/scannet_raw.py), so no preprocessing step comes before training.
+
+--dataset sunrgbd trains on SUN RGB-D with the same stage defaults (the reference's run scripts pass
+no dataset-specific flag):
+
+    python tools/train.py --dataset sunrgbd --stage pretrain --data_dir sunrgbd_pc_bbox_votes_50k_v1_train \
+        --val_dir sunrgbd_pc_bbox_votes_50k_v1_val --log_dir log
+    python tools/train.py --dataset sunrgbd --stage semi --raw_trainval sunrgbd_trainval \
+        --labeled_sample_list sunrgbd_v1_train_0.05.txt --log_dir log
+
+--data_dir / --val_dir are the two prepared folders; --votes boxes reads no `_votes.npz` and computes
+the vote labels from the boxes.  --raw_trainval DIR stands in place of both: DIR is the
+`sunrgbd_trainval/` folder the reference's MATLAB step leaves (depth/, label_v1/ or, with
+--use_sunrgbd_v2, label/, train_data_idx.txt, val_data_idx.txt), subsampled and turned into store rows
+on the device at start-up (votenet/sunrgbd_raw.py).  --meta_dir holds --labeled_sample_list (default:
+--raw_trainval's folder, where the reference keeps its lists); without a list every train scene is
+labeled.  --unlabeled_scans DIR then also takes `.mat` depth clouds."""
 import argparse
 import importlib
 import os
@@ -29,8 +45,15 @@ def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--stage', choices=('pretrain', 'semi'), default='semi')
     ap.add_argument('--synthetic', type=int, default=0, metavar='N', help='train on N synthetic scans')
-    ap.add_argument('--dataset', default='scannet', choices=('scannet',), help='Dataset name.')
-    ap.add_argument('--data_dir', default=None, help='preprocessed scans (scannet_train_detection_data)')
+    ap.add_argument('--dataset', default='scannet', choices=('scannet', 'sunrgbd'), help='Dataset name.')
+    ap.add_argument('--data_dir', default=None, help='preprocessed scans (scannet_train_detection_data; '
+                    'sunrgbd: sunrgbd_pc_bbox_votes_50k_v1_train)')
+    ap.add_argument('--val_dir', default=None, help='sunrgbd: sunrgbd_pc_bbox_votes_50k_v1_val')
+    ap.add_argument('--votes', default='file', choices=('file', 'boxes'),
+                    help="sunrgbd: read _votes.npz, or compute the vote labels from the boxes")
+    ap.add_argument('--raw_trainval', default=None, metavar='DIR',
+                    help='sunrgbd: a raw sunrgbd_trainval folder in place of --data_dir and --val_dir')
+    ap.add_argument('--use_sunrgbd_v2', action='store_true', help='Use V2 box labels for SUN RGB-D dataset')
     ap.add_argument('--raw_scans', default=None, metavar='DIR',
                     help='raw ScanNet scan folders in place of --data_dir (needs --label_map)')
     ap.add_argument('--label_map', default=None, metavar='TSV', help='scannetv2-labels.combined.tsv')
@@ -94,28 +117,92 @@ def eval_config_dict(cfg, flags):
             'per_class_proposal': True, 'conf_thresh': flags.conf_thresh}
 
 
-def main(argv=None):
-    flags = parser().parse_args(argv)
-    opt = settings(flags)
-    if flags.unlabeled_scans is not None:
-        if not opt['semi']:
-            raise SystemExit("--unlabeled_scans: --stage pretrain trains on labeled scans only")
-        if flags.view_stats:
-            raise SystemExit("--unlabeled_scans with --view_stats: the statistics compare the pseudo-labels with "
-                             "the unlabeled scans' own labels, which a folder of bare clouds does not have")
-        if flags.unlabeled_scans == 'synthetic' and not flags.synthetic:
-            raise SystemExit("--unlabeled_scans synthetic needs --synthetic N")
-    sys.path.insert(0, ROOT)
-    import torch
-    importlib.import_module("3dioumatch_amd")
-    V = importlib.import_module("3dioumatch_amd.votenet")
+def check_dataset_flags(flags, opt):
+    """Refuse the flags of the other dataset and --dataset sunrgbd's own contradictions."""
+    if flags.dataset == 'scannet':
+        for name in ('val_dir', 'raw_trainval', 'use_sunrgbd_v2'):
+            if getattr(flags, name):
+                raise SystemExit("--%s belongs to --dataset sunrgbd" % name)
+        if flags.votes != 'file':
+            raise SystemExit("--votes belongs to --dataset sunrgbd")
+        return
+    if flags.raw_scans or flags.label_map:
+        raise SystemExit("--raw_scans and --label_map belong to --dataset scannet")
+    if flags.synthetic:
+        return
+    if flags.raw_trainval and (flags.data_dir or flags.val_dir):
+        raise SystemExit("--raw_trainval DIR stands in place of --data_dir and --val_dir")
+    if not flags.raw_trainval and not (flags.data_dir and flags.val_dir):
+        raise SystemExit("--dataset sunrgbd: --data_dir and --val_dir, or --raw_trainval DIR, or --synthetic N")
+    if flags.use_sunrgbd_v2 and not flags.raw_trainval:
+        raise SystemExit("--use_sunrgbd_v2 chooses the label folder of --raw_trainval")
+    if flags.labeled_sample_list != 'scannetv2_train.txt' and not (flags.meta_dir or flags.raw_trainval):
+        raise SystemExit("--labeled_sample_list needs --meta_dir, the folder that holds it")
+    if opt['semi'] and flags.unlabeled_scans is None and flags.labeled_sample_list == 'scannetv2_train.txt':
+        raise SystemExit("--dataset sunrgbd --stage semi: --labeled_sample_list (e.g. sunrgbd_v1_train_0.05.txt) "
+                         "or --unlabeled_scans DIR")
+
+
+def sunrgbd_loaders(flags, opt, dev, V, SC):
+    """-> (config, the train loader, the val loader) of --dataset sunrgbd."""
+    SUN = importlib.import_module("3dioumatch_amd.votenet.sunrgbd_data")
+    RAW = importlib.import_module("3dioumatch_amd.votenet.sunrgbd_raw")
+    cfg = V.sunrgbd_config()
+    color, height, seed = flags.use_color, not flags.no_height, flags.seed or 0
+    tmp, list_path = None, None
+    if flags.synthetic:
+        tmp = tempfile.TemporaryDirectory()
+        names = ["%06d" % i for i in range(1, flags.synthetic + 1)]
+        SUN.write_synthetic_scans(tmp.name, names, num_points=max(flags.num_point, 2000) * 5 // 4, seed=0)
+        # a quarter for evaluation, the rest halved into labeled and unlabeled scans
+        n_val = max(1, flags.synthetic // 4)
+        val, train = names[:n_val], names[n_val:]
+        labeled = train[:len(train) // 2] if opt['semi'] else train
+        unlabeled = train[len(train) // 2:] if opt['semi'] else None
+        data_dir = val_dir = tmp.name
+    else:
+        if flags.labeled_sample_list != 'scannetv2_train.txt':
+            list_path = os.path.join(flags.meta_dir or flags.raw_trainval, flags.labeled_sample_list)
+        if flags.raw_trainval:
+            train = RAW.read_idx_list(os.path.join(flags.raw_trainval, "train_data_idx.txt"))
+            val = RAW.read_idx_list(os.path.join(flags.raw_trainval, "val_data_idx.txt"))
+        else:
+            data_dir, val_dir = flags.data_dir, flags.val_dir
+            train, val = SUN.available_scans(data_dir), SUN.val_split(val_dir)
+        listed = SUN._read_list(list_path) if list_path else list(train)
+        labeled = [s for s in listed if s in set(train)]  # listed scans without files are skipped
+        unlabeled = None
+        if opt['semi'] and flags.unlabeled_scans is None:  # sunrgbd_ssl_dataset.py:193-203
+            unlabeled = sorted(train if len(train) == len(listed) else set(train) - set(listed))
+    scans = None
+    if flags.unlabeled_scans == 'synthetic':
+        files = [os.path.join(data_dir, s + "_pc.npz") for s in unlabeled]
+    elif flags.unlabeled_scans is not None:
+        files = sorted(os.path.join(flags.unlabeled_scans, f) for f in os.listdir(flags.unlabeled_scans)
+                       if f.endswith((".npy", ".npz", ".mat")))
+        if not files:
+            raise SystemExit("--unlabeled_scans %s: no .npy, .npz or .mat cloud in it" % flags.unlabeled_scans)
+    if flags.unlabeled_scans is not None:  # the labeled store then holds no unlabeled scan
+        scans = SC.ScanStore.from_files(files, dev, "sunrgbd")
+        unlabeled = None
+    names = sorted(set(labeled) | set(unlabeled or ()))
+    if flags.raw_trainval and not flags.synthetic:
+        v1 = not flags.use_sunrgbd_v2
+        scenes = SUN.SunRgbdScenes.from_raw(flags.raw_trainval, names, dev, color, height, use_v1=v1, seed=seed)
+        val_scenes = SUN.SunRgbdScenes.from_raw(flags.raw_trainval, val, dev, color, height, use_v1=v1, seed=seed)
+    else:
+        scenes = SUN.SunRgbdScenes(data_dir, names, dev, color, height, votes=flags.votes)
+        val_scenes = SUN.SunRgbdScenes(val_dir, val, dev, color, height, votes=flags.votes)
+    if tmp is not None:
+        tmp.cleanup()  # the stores are resident
+    loader = SUN.SunRgbdLoader(scenes, cfg, flags.num_point, seed=seed, labeled=labeled, unlabeled=unlabeled,
+                               unlabeled_scans=scans)
+    return cfg, loader, SUN.SunRgbdLoader(val_scenes, cfg, flags.num_point, seed=seed, labeled=val)
+
+
+def scannet_loaders(flags, opt, dev, V, SC):
+    """-> (config, the train loader, the val loader) of --dataset scannet."""
     SD = importlib.import_module("3dioumatch_amd.votenet.scannet_data")
-    SC = importlib.import_module("3dioumatch_amd.votenet.scan_data")
-    T = importlib.import_module("3dioumatch_amd.votenet.trainer")
-    U = importlib.import_module("3dioumatch_amd.votenet.losses_unlabeled")
-    dev = torch.device(flags.device)
-    if dev.type != "cuda":
-        raise SystemExit("tools/train.py builds its batches on the GPU (--device cuda:N)")
     cfg = V.scannet_config()
     use_height = not flags.no_height
 
@@ -162,7 +249,34 @@ def main(argv=None):
         tmp.cleanup()  # the stores are resident
     loader = SD.ScanNetLoader(scenes, cfg, flags.num_point, seed=flags.seed or 0, labeled=labeled,
                               unlabeled=unlabeled, unlabeled_scans=scans)
-    val_loader = SD.ScanNetLoader(scenes, cfg, flags.num_point, seed=flags.seed or 0, labeled=val)
+    return cfg, loader, SD.ScanNetLoader(scenes, cfg, flags.num_point, seed=flags.seed or 0, labeled=val)
+
+
+def main(argv=None):
+    flags = parser().parse_args(argv)
+    opt = settings(flags)
+    check_dataset_flags(flags, opt)
+    if flags.unlabeled_scans is not None:
+        if not opt['semi']:
+            raise SystemExit("--unlabeled_scans: --stage pretrain trains on labeled scans only")
+        if flags.view_stats:
+            raise SystemExit("--unlabeled_scans with --view_stats: the statistics compare the pseudo-labels with "
+                             "the unlabeled scans' own labels, which a folder of bare clouds does not have")
+        if flags.unlabeled_scans == 'synthetic' and not flags.synthetic:
+            raise SystemExit("--unlabeled_scans synthetic needs --synthetic N")
+    sys.path.insert(0, ROOT)
+    import torch
+    importlib.import_module("3dioumatch_amd")
+    V = importlib.import_module("3dioumatch_amd.votenet")
+    SD = importlib.import_module("3dioumatch_amd.votenet.scene_loader")  # eval_batches
+    SC = importlib.import_module("3dioumatch_amd.votenet.scan_data")
+    T = importlib.import_module("3dioumatch_amd.votenet.trainer")
+    U = importlib.import_module("3dioumatch_amd.votenet.losses_unlabeled")
+    dev = torch.device(flags.device)
+    if dev.type != "cuda":
+        raise SystemExit("tools/train.py builds its batches on the GPU (--device cuda:N)")
+    loaders = sunrgbd_loaders if flags.dataset == 'sunrgbd' else scannet_loaders
+    cfg, loader, val_loader = loaders(flags, opt, dev, V, SC)
 
     common = dict(num_proposal=opt['num_target'], lr=opt['learning_rate'], meter=True, guard=opt['guard'],
                   clip_grad_norm=opt['clip_grad_norm'])
