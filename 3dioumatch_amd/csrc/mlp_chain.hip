@@ -495,7 +495,9 @@ MLP_API int mlp_chain_lin4_prepare(const float *w1, const float *sc1, const floa
 // is written.  img: what mlp_chain_lin4_prepare left.
 MLP_API int mlp_chain_lin4_stats(int b, int r, int ns, const float *x4, const void *img, float *pairs2,
                                  void *stream_) {
-  if (!chain_shape_ok(b, r, ns) || !x4 || !img || !pairs2) return (int)hipErrorInvalidValue;
+  // (the image is fetched in 16-byte pieces)
+  if (!chain_shape_ok(b, r, ns) || !x4 || !img || !pairs2 || (reinterpret_cast<size_t>(img) & 15))
+    return (int)hipErrorInvalidValue;
   ChainArgs a = {};
   a.r = r; a.tiles_per_cloud = r / 32;
   a.x4 = x4; a.wimg = (const char *)img; a.pairs = pairs2;
@@ -511,7 +513,7 @@ MLP_API int mlp_chain_lin4_forward(int b, int r, int ns, const float *x4, const 
                                    const float *sh2, const float *gamma3, float *y2, float *y3,
                                    float *pairs3, float *ext, void *stream_) {
   if (!chain_shape_ok(b, r, ns) || !x4 || !img || !sc2 || !sh2 || !gamma3 || !pairs3 || !ext ||
-      (y3 && (reinterpret_cast<size_t>(y3) & 15)))
+      (reinterpret_cast<size_t>(img) & 15) || (y3 && (reinterpret_cast<size_t>(y3) & 15)))
     return (int)hipErrorInvalidValue;
   ChainArgs a = {};
   a.r = r; a.tiles_per_cloud = r / 32;

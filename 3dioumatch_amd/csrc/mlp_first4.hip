@@ -220,7 +220,7 @@ MLP_API int mlp_first4_moments_doubles(void) { return kF4MomentParts * 14; }
 // the 14 moments of x (b,4,r) -- 4 sums, 10 products -- as 256 partial rows of doubles
 MLP_API int mlp_first4_moments(int b, int r, const float *x, double *moments, void *stream_) {
   if (b <= 0 || r <= 0) return 0;
-  if (!moments) return (int)hipErrorInvalidValue;
+  if (!x || !moments) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(first4_moments_kernel, dim3(kF4MomentParts), dim3(256), 0, (hipStream_t)stream_, r,
                      (long long)b * r, x, moments);
   return pn2_launch_status();
@@ -232,7 +232,9 @@ MLP_API int mlp_first4_bn(const double *moments, double count, const float *w, c
                           const float *beta, float eps, float momentum, float *running_mean,
                           float *running_var, float *mean, float *invstd, float *scale,
                           float *shift, void *stream_) {
-  if (!moments || count <= 0) return (int)hipErrorInvalidValue;
+  if (!moments || count <= 0 || !w || !gamma || !beta || !mean || !invstd || !scale || !shift ||
+      (running_mean != nullptr) != (running_var != nullptr))
+    return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(first4_bn_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream_, moments, count, w,
                      gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift);
   return pn2_launch_status();
@@ -254,7 +256,8 @@ MLP_API int mlp_wgrad_first4(int b, int r, const float *w, const float *x, const
                              const float *invstd, const float *coef, const double *moments,
                              float *dw, void *workspace, void *stream_) {
   if (b <= 0 || r <= 0) return 0;
-  if (r % 4 != 0 || !workspace) return (int)hipErrorInvalidValue;
+  if (r % 4 != 0 || !workspace || !w || !x || !dz || !scale || !shift || !mean || !invstd || !coef || !dw)
+    return (int)hipErrorInvalidValue;
   hipStream_t stream = (hipStream_t)stream_;
   const int slices = first4_slices(b, r);
   const long long per = (((long long)r + slices - 1) / slices + 255) / 256 * 256;

@@ -211,7 +211,9 @@ size_t mlp_chain_lin4_image_bytes(void);
 int mlp_chain_lin4_prepare(const float *w1, const float *sc1, const float *sh1, const float *w2,
                            const float *w3, void *img, void *stream);
 /* statistics pass: pairs2 (parts, 64, 2) of y2 = w2 . relu(bn1(w1 . x4)), x4 (b,4,r); nothing else
- * is written (the BatchNorm of pytorch_utils.py:42-67 needs them before layer 2's ReLU) */
+ * is written (the BatchNorm of pytorch_utils.py:42-67 needs them before layer 2's ReLU).  Both passes
+ * refuse (hipErrorInvalidValue, nothing launched) a shape outside mlp_chain_lin4_parts, a NULL
+ * among the required pointers and an img (or, in the full pass, a y3) that is not 16-byte aligned. */
 int mlp_chain_lin4_stats(int b, int r, int ns, const float *x4, const void *img, float *pairs2,
                          void *stream);
 /* full pass: y2 (b,64,r) and y3 (b,128,r) (either may be NULL), pairs3 (parts,128,2), ext = 2 planes
@@ -387,7 +389,9 @@ size_t mlp_wgrad_first4_workspace_bytes(int b, int r);
 /* dw (64,4) from x (b,4,r), dz (b,64,r) = gradient w.r.t. relu(bn(y)), and the layer's scale,
  * shift, mean, invstd, coef (64,3) as mlp_bn_relu_backward_stats leaves them; y is not read;
  * moments = those of x (mlp_first4_moments) or NULL to compute them here
- * (replaces conv2d backward-weight behind BatchNorm2d + ReLU, pytorch_utils.py:70-124) */
+ * (replaces conv2d backward-weight behind BatchNorm2d + ReLU, pytorch_utils.py:70-124).
+ * r % 4 != 0 or a NULL among the other pointers: hipErrorInvalidValue, nothing launched (the
+ * three entry points above refuse NULL the same way; running_mean / running_var: both or none) */
 int mlp_wgrad_first4(int b, int r, const float *w, const float *x, const float *dz,
                      const float *scale, const float *shift, const float *mean, const float *invstd,
                      const float *coef, const double *moments, float *dw, void *workspace,

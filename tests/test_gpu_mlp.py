@@ -502,7 +502,8 @@ def test_pool_from_gemm_epilogue_extrema(b, m, k, groups, ns):
 @pytest.mark.parametrize("b,groups,ns,training", [(8, 256, 64, True), (2, 33, 4, True), (3, 100, 8, False)])
 def test_first_layer_weight_gradient_from_moments(b, groups, ns, training):
     """mlp_wgrad_first4 (4 -> 64 first layer: gated sums over dz and x, the rest from the second
-    moments of x; the layer's output is never read) == the general on-the-fly wgrad over (y, dz)."""
+    moments of x; the layer's output is never read) == the general on-the-fly wgrad over (y, dz).
+    (Against the float64 autograd, on inputs no kernel prepares: tests/test_sa1_train_gpu.py.)"""
     load_pkg()
     K = importlib.import_module("pointnet2._mlp_ext")
     g = torch.Generator().manual_seed(groups + ns)
@@ -588,7 +589,8 @@ def test_chained_forward_vs_layerwise(b, m, ns):
     statistics and pooled extrema as in-lane reductions) == the layer-by-layer kernels: both raw
     outputs, both layers' BatchNorm coefficients and running statistics, the pooled tensor, the
     arg-max (pytorch_utils.py:14-39,70-124, pointnet2_modules.py:256-262).  Negative gammas and
-    duplicated columns (pool ties: the first index wins) included."""
+    duplicated columns (pool ties: the first index wins) included.  (The chain against float64, per
+    channel and edge by edge: tests/test_sa1_train_gpu.py.)"""
     load_pkg()
     K = importlib.import_module("pointnet2._mlp_ext")
     g = torch.Generator().manual_seed(b * 100 + ns)
@@ -908,7 +910,9 @@ def test_sa1_chain_and_gram_vs_float64_torch(b, m, ns):
     registers, last raw output not stored) and csrc/mlp_pool_gram.hip's backward (from the Gram
     matrix of the layer's input) against a float64 torch evaluation of the reference's module --
     Conv2d 1x1 (no bias) + BatchNorm2d (batch statistics) + ReLU, three times, then the max over
-    nsample (pytorch_utils.py:14-39,70-124, pointnet2_modules.py:256-262) -- and its autograd."""
+    nsample (pytorch_utils.py:14-39,70-124, pointnet2_modules.py:256-262) -- and its autograd.
+    (The forward alone at small shapes, every nsample, stored outputs and per-channel measures:
+    tests/test_sa1_train_gpu.py.)"""
     load_pkg()
     K = importlib.import_module("pointnet2._mlp_ext")
     g = torch.Generator().manual_seed(7 * b + m + ns)
