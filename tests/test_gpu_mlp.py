@@ -821,7 +821,8 @@ def test_pooled_backward_from_the_gram_matrix(b, m, ns, kin, mout, monkeypatch):
     y3 (dy3 = q y3 + p + S: da2 = (W3^T diag(q) W3) a2 + W3^T p + W3^T S, dW3 = diag(q) W3 (a2 a2^T) +
     p (sum a2)^T + S a2^T) == the one-pass kernel that rebuilds dy3 from the stored y3: gradient
     w.r.t. the layer's input, weight gradient, BatchNorm-backward sums of the layer below
-    (autograd of pytorch_utils.py:14-39,70-124 + pointnet2_modules.py:256-262)."""
+    (autograd of pytorch_utils.py:14-39,70-124 + pointnet2_modules.py:256-262).
+    (The (128, 64) pass against float64 at every kind of chunk range: tests/test_pool_gram128_gpu.py.)"""
     load_pkg()
     K = importlib.import_module("pointnet2._mlp_ext")
     monkeypatch.setenv("MLP_POOL_GRAM256_MIN_CHUNKS", "64")  # (the product takes this path from 4096 chunks on)
@@ -912,7 +913,8 @@ def test_sa1_chain_and_gram_vs_float64_torch(b, m, ns):
     Conv2d 1x1 (no bias) + BatchNorm2d (batch statistics) + ReLU, three times, then the max over
     nsample (pytorch_utils.py:14-39,70-124, pointnet2_modules.py:256-262) -- and its autograd.
     (The forward alone at small shapes, every nsample, stored outputs and per-channel measures:
-    tests/test_sa1_train_gpu.py.)"""
+    tests/test_sa1_train_gpu.py; the backward alone, on inputs no kernel prepares and under a measured
+    bound: tests/test_pool_gram128_gpu.py.)"""
     load_pkg()
     K = importlib.import_module("pointnet2._mlp_ext")
     g = torch.Generator().manual_seed(7 * b + m + ns)
