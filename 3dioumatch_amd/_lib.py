@@ -205,6 +205,11 @@ _LOADER_SIGNATURES = {
     "scene_scan_batch_build": [_vp, _vp],
     "scene_scan_semi_build": [_vp, _vp],
     "scene_detections_pack": [_vp, _vp],
+    # scans larger than a room: device tiling and merged detections (include/scan_tile_hip.h)
+    "scene_scan_bounds": [_vp, _vp],
+    "scene_scan_tile_count": [_vp, _vp],
+    "scene_scan_tile_gather": [_vp, _vp],
+    "scene_detections_merge": [_vp, _vp],
     # raw ScanNet scans -> the preprocessed layout (include/scannet_raw_hip.h)
     "scannet_raw_export": [_vp, _vp],
     # raw SUN RGB-D depth clouds -> kept rows, floors, store rows (include/sunrgbd_raw_hip.h)

@@ -15,4 +15,5 @@ from .eval_det import eval_det, eval_det_cls, voc_ap  # noqa: F401
 from .train_meter import TrainMeter, tb_name  # noqa: F401
 from .trainer import Trainer, engine_evaluator, loader_epochs  # noqa: F401
 from .scan_data import ScanLoader, ScanStore  # noqa: F401
-from .detect import Detections, detect  # noqa: F401
+from .detect import Detections, TiledDetections, detect, detect_tiled  # noqa: F401
+from .scan_tiles import TileStore, tile_grid  # noqa: F401

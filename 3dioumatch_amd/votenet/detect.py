@@ -23,6 +23,9 @@ rows per scan; the integer planes are stored as their bit patterns):
     box       (S, K, 7)   f32   centre, size (l, w, h), heading in the network's frame
     corners   (S, K, 8, 3) f32  upright camera frame, as parse_predictions returns them
 Rows past `count` are zero.  `host_pack` restates the rule in numpy.
+
+detect_tiled() is the same loop over the tiles of a scan_tiles.TileStore and one merge launch into a
+second arena, one set of boxes per parent scan (see the section at the end; `host_merge` restates it).
 """
 import ctypes
 import importlib
@@ -147,6 +150,7 @@ def pack_gpu(arena, S, scene0, keep, obj_prob, cls, score, center, size64, headi
 class Detections(object):
     """The packed detections of a run.  Reading (indexing, by_name, as_map_cls, save) makes the one
     device -> host copy of the arena; `arena` itself stays on the device."""
+    INT_PLANES = ("count", "proposal", "cls")  # stored as their bit patterns
 
     def __init__(self, arena, names, K, NC, num_class):
         self.arena, self.names, self.K, self.NC, self.num_class = arena, list(names), int(K), int(NC), int(num_class)
@@ -164,7 +168,7 @@ class Detections(object):
             self._planes = {}
             for name, (at, shape) in self.layout.items():
                 flat = host[at:at + int(np.prod(shape))]
-                if name in ("count", "proposal", "cls"):
+                if name in self.INT_PLANES:
                     flat = flat.view(np.int32)
                 self._planes[name] = flat.reshape(shape)
         return self._planes
@@ -192,28 +196,25 @@ class Detections(object):
                      **{k: v[:c] for k, v in rows.items() if k != "count"})
 
 
-@torch.no_grad()
-def detect(engine, store_or_loader, config_dict, batch_size=8, opt_step=0, opt_rate=5e-4, counter=0):
-    """Detections of every scan of a ScanLoader (or of a ScanStore, through ScanLoader(store, 40000
-    points for ScanNet / 20000 for SUN RGB-D, height only)), batch_size scans at a time, batch i drawn
-    with counter + i.  `engine`: an InferenceEngine; `config_dict`: parse_predictions' keys."""
+def _pack_run(who, engine, store_or_loader, config_dict, batch_size, opt_step, opt_rate, counter):
+    """The loop of detect() and detect_tiled(): every scan of the loader's store through the engine
+    and the pack launch -> (store, arena, K, NC).  Nothing in it copies to the host or synchronises."""
     from .iou_opt import _check_detector, optimize_boxes
     loader = store_or_loader
     if isinstance(loader, ScanStore):
         loader = ScanLoader(loader, 40000 if loader.dataset == "scannet" else 20000)
     if not isinstance(loader, ScanLoader):
-        raise ValueError("detect: a ScanStore or a ScanLoader")
+        raise ValueError("%s: a ScanStore or a ScanLoader" % who)
     store = loader.store
     if store.device is None or store.device != engine.device:
-        raise ValueError("detect: the store lives on %s, the engine on %s" % (store.device, engine.device))
+        raise ValueError("%s: the store lives on %s, the engine on %s" % (who, store.device, engine.device))
     if not 1 <= batch_size <= 64:
-        raise ValueError("detect: batch_size 1..64")
+        raise ValueError("%s: batch_size 1..64" % who)
     detector = engine.detector
     if detector.training:
-        raise ValueError("detect: the detector must be in eval mode")
+        raise ValueError("%s: the detector must be in eval mode" % who)
     if opt_step > 0:
         _check_detector(detector)
-    config = config_dict['dataset_config']
     S = len(store)
     clouds = []  # the batches engine.run has drawn and not yet returned
 
@@ -231,4 +232,175 @@ def detect(engine, store_or_loader, config_dict, batch_size=8, opt_step=0, opt_r
             end_points.setdefault('point_clouds', point_clouds)
             arena, K, NC, B = pack_end_points(arena, S, scene0, end_points, config_dict)
             scene0 += B
-    return Detections(arena, store.names, K, NC, config.num_class)
+    return store, arena, K, NC
+
+
+@torch.no_grad()
+def detect(engine, store_or_loader, config_dict, batch_size=8, opt_step=0, opt_rate=5e-4, counter=0):
+    """Detections of every scan of a ScanLoader (or of a ScanStore, through ScanLoader(store, 40000
+    points for ScanNet / 20000 for SUN RGB-D, height only)), batch_size scans at a time, batch i drawn
+    with counter + i.  `engine`: an InferenceEngine; `config_dict`: parse_predictions' keys."""
+    store, arena, K, NC = _pack_run("detect", engine, store_or_loader, config_dict, batch_size, opt_step, opt_rate,
+                                    counter)
+    return Detections(arena, store.names, K, NC, config_dict['dataset_config'].num_class)
+
+
+# ------------------------------------------------------------------ scans larger than a room
+# The tiles of a scan_tiles.TileStore go through the loop above like any scans; ONE more launch,
+# scene_detections_merge (include/scan_tile_hip.h), then writes for every parent scan the rows its
+# tiles OWN -- those whose box centre (x, y) lies in the tile's core, float32 compares, lower bound
+# inclusive -- compacted into a second arena: the scan's tiles in store order, each tile's rows in
+# their packed order.  Its planes, indexed by parent scan (cap = (most tiles any scan has) * K rows per
+# scan):
+#     count (S,), tile (S, cap) i32: the row's tile (its row in the tile store), proposal, cls (S, cap),
+#     score (S, cap) or (S, cap, NC), box (S, cap, 7), corners (S, cap, 8, 3)
+# Rows past `count` are zero.  There is no cross-tile NMS: a box whose centre two neighbouring tiles
+# estimate on opposite sides of a cut may be kept twice or not at all.
+MERGED_PLANES = ("count", "tile", "proposal", "cls", "score", "box", "corners")
+
+
+class _MergeArgs(ctypes.Structure):  # field order == include/scan_tile_hip.h ScanMergeArgs
+    _fields_ = ([(n, _c_int) for n in ("S", "K", "NC", "cap", "max_tiles")] +
+                [(n, _vp) for n in ("first", "tiles", "core", "count_in", "proposal_in", "cls_in", "score_in",
+                                    "box_in", "corners_in", "count", "tile", "proposal", "cls", "score", "box",
+                                    "corners")])
+
+
+def merged_layout(S, cap, NC):
+    """arena_layout for the merged arena: {plane: (first word, shape)} and its size in words."""
+    shapes = {"count": (S,), "tile": (S, cap), "proposal": (S, cap), "cls": (S, cap),
+              "score": (S, cap, NC) if NC else (S, cap), "box": (S, cap, 7), "corners": (S, cap, 8, 3)}
+    layout, at = {}, 0
+    for name in MERGED_PLANES:
+        layout[name] = (at, shapes[name])
+        at += int(np.prod(shapes[name]))
+    return layout, at
+
+
+def host_merge(planes, first, tiles, core, cap=None):
+    """The merge rule in numpy: `planes` = the tile arena's {plane: array} with the tiles leading
+    (Detections.planes()), first / tiles (S,) each scan's run of tiles, core (T, 4) = clo_x, chi_x,
+    clo_y, chi_y -> the merged {plane: array} with the scans leading."""
+    first, tiles = np.asarray(first, np.int64), np.asarray(tiles, np.int64)
+    core = np.asarray(core, np.float32)
+    S, K = len(first), planes["proposal"].shape[1]
+    if cap is None:
+        cap = int(tiles.max()) * K
+    out = {"count": np.zeros(S, np.int32), "tile": np.zeros((S, cap), np.int32)}
+    for name in ("proposal", "cls", "score", "box", "corners"):
+        out[name] = np.zeros((S, cap) + planes[name].shape[2:], planes[name].dtype)
+    for s in range(S):
+        at = 0
+        for t in range(first[s], first[s] + tiles[s]):
+            c = int(planes["count"][t])
+            xy = np.asarray(planes["box"][t, :c, 0:2], np.float32)
+            lo_x, hi_x, lo_y, hi_y = core[t]
+            owned = np.nonzero((lo_x <= xy[:, 0]) & (xy[:, 0] < hi_x) & (lo_y <= xy[:, 1]) & (xy[:, 1] < hi_y))[0]
+            n = len(owned)
+            out["tile"][s, at:at + n] = t
+            for name in ("proposal", "cls", "score", "box", "corners"):
+                out[name][s, at:at + n] = planes[name][t, owned]
+            at += n
+        out["count"][s] = at
+    return out
+
+
+def new_merged_arena(S, cap, NC, device):
+    """The merged arena of S scans, uninitialised: the merge launch writes every word."""
+    return torch.empty(merged_layout(S, cap, NC)[1], dtype=torch.float32, device=device)
+
+
+def merge_gpu(merged, tile_arena, first, tiles, core, S, T, K, NC, cap, max_tiles):
+    """Launch scene_detections_merge: the tile arena (T tiles, K rows each) -> `merged` (S scans, cap
+    rows each); first, tiles (S,) int32 and core (T, 4) float32 on the arenas' device."""
+    _L = importlib.import_module("3dioumatch_amd._lib")
+    if K > MAX_K:
+        raise ValueError("scene_detections_merge: K = %d rows per tile, at most %d" % (K, MAX_K))
+    if cap < max_tiles * K:
+        raise ValueError("scene_detections_merge: cap = %d rows per scan, %d tiles of %d need %d"
+                         % (cap, max_tiles, K, max_tiles * K))
+    lin, words_in = arena_layout(T, K, NC)
+    lout, words_out = merged_layout(S, cap, NC)
+    for name, t, words in (("tile arena", tile_arena, words_in), ("merged arena", merged, words_out)):
+        if t.dtype != torch.float32 or t.numel() != words or not t.is_contiguous() or t.device != merged.device:
+            raise ValueError("scene_detections_merge: the %s does not match (S, T, K, C, cap) = (%d, %d, %d, %d, %d)"
+                             % (name, S, T, K, NC, cap))
+    for name, t, dtype, shape in (("first", first, torch.int32, (S,)), ("tiles", tiles, torch.int32, (S,)),
+                                  ("core", core, torch.float32, (T, 4))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != merged.device:
+            raise ValueError("scene_detections_merge: %s must be %s %s on %s" % (name, dtype, shape, merged.device))
+    a = _MergeArgs()
+    a.S, a.K, a.NC, a.cap, a.max_tiles = S, K, NC, cap, max_tiles
+    a.first, a.tiles, a.core = first.data_ptr(), tiles.data_ptr(), core.data_ptr()
+    for plane in PLANES:
+        setattr(a, plane + "_in", tile_arena.data_ptr() + 4 * lin[plane][0])
+    for plane in MERGED_PLANES:
+        setattr(a, plane, merged.data_ptr() + 4 * lout[plane][0])
+    with torch.cuda.device(merged.device):
+        _L.check(_L.lib.scene_detections_merge(ctypes.byref(a), _L.current_stream_ptr(merged.device)),
+                 "scene_detections_merge")
+    return merged
+
+
+def merged_map_cls_of(rows, num_class, per_class):
+    """map_cls_of for a scan's merged rows: tile, then proposal ascending; with per_class class-major."""
+    c = int(rows["count"])
+    order = np.lexsort((rows["proposal"][:c], rows["tile"][:c]))
+    if per_class:
+        return [(ii, rows["corners"][r], rows["score"][r, ii]) for ii in range(num_class) for r in order]
+    return [(int(rows["cls"][r]), rows["corners"][r], rows["score"][r]) for r in order]
+
+
+class TiledDetections(Detections):
+    """The merged detections of a detect_tiled run, one set per PARENT scan, over the merged layout;
+    `tiles` is the Detections of the tiles themselves (the first arena) and `store` the TileStore.
+    Reading makes the one device -> host copy of the merged arena."""
+    INT_PLANES = Detections.INT_PLANES + ("tile",)
+
+    def __init__(self, arena, store, cap, K, NC, num_class, tiles=None):
+        self.arena, self.names, self.K, self.NC, self.num_class = arena, list(store.parent_names), int(K), int(NC), \
+            int(num_class)
+        self.store, self.cap, self.tiles = store, int(cap), tiles
+        self.per_class_proposal = NC > 0
+        self.layout, _ = merged_layout(len(self.names), self.cap, self.NC)
+        self._planes = None
+
+    def as_map_cls(self):
+        return [merged_map_cls_of(self[i], self.num_class, self.per_class_proposal) for i in range(len(self))]
+
+    def save(self, directory):
+        """<scan>.npz per parent scan: count, the planes cut to `count` rows (`tile` among them: rows of
+        the tile store), and of the scan's tiles `tile_first` (the store row of its first tile),
+        `tile_names`, `window` and `core` (tiles, 4)."""
+        os.makedirs(directory, exist_ok=True)
+        st = self.store
+        for i, name in enumerate(self.names):
+            rows = self[i]
+            c = int(rows["count"])
+            a, b = int(st.first[i]), int(st.first[i] + st.tiles[i])
+            np.savez(os.path.join(directory, name + ".npz"), count=rows["count"], tile_first=np.int32(a),
+                     tile_names=np.array(st.names[a:b]), window=st.window[a:b], core=st.core[a:b],
+                     **{k: v[:c] for k, v in rows.items() if k != "count"})
+
+
+@torch.no_grad()
+def detect_tiled(engine, tile_store_or_loader, config_dict, batch_size=8, opt_step=0, opt_rate=5e-4, counter=0):
+    """detect() for scans larger than a room: the tiles of a scan_tiles.TileStore (or of a ScanLoader
+    over one) through detect()'s loop, then ONE merge launch -> TiledDetections, one set per parent
+    scan in the scan's own frame.  No host copy and no synchronising op before the result is read."""
+    from .scan_tiles import TileStore
+    loader = tile_store_or_loader
+    store = loader.store if isinstance(loader, ScanLoader) else loader
+    if not isinstance(store, TileStore):
+        raise ValueError("detect_tiled: a TileStore or a ScanLoader over one")
+    store, arena, K, NC = _pack_run("detect_tiled", engine, loader, config_dict, batch_size, opt_step, opt_rate,
+                                    counter)
+    S, T = len(store.parent_names), len(store)
+    max_tiles = int(store.tiles.max())
+    cap = max_tiles * K
+    with torch.cuda.device(engine.device):
+        merged = new_merged_arena(S, cap, NC, arena.device)
+        merge_gpu(merged, arena, store.dev["first"], store.dev["tiles"], store.dev["core"], S, T, K, NC, cap,
+                  max_tiles)
+    num_class = config_dict['dataset_config'].num_class
+    return TiledDetections(merged, store, cap, K, NC, num_class, Detections(arena, store.names, K, NC, num_class))

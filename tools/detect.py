@@ -3,11 +3,14 @@
     python tools/detect.py --checkpoint log/checkpoint.tar --out boxes scans/          # every .npy / .npz / .ply / .mat
     python tools/detect.py --checkpoint log/checkpoint.tar --out boxes a.npy b_pc.npz --dataset sunrgbd
     python tools/detect.py --synthetic 16 --out /tmp/boxes                             # no data, seeded weights
+    python tools/detect.py --checkpoint log/checkpoint.tar --out boxes floor.ply --tile 8 6 --overlap 1.0  # larger than a room
 
 Inputs are (n, 3) xyz or (n, 6) xyz + rgb clouds: `.npy` files, `.npz` files with a `pc` member, `.ply`
 files (their vertices, as they are), `.mat` depth clouds (SUN RGB-D's `instance`), or a directory of them.  --num_point / --use_color / --no_height /
 --num_target must be those the checkpoint was trained with (tools/train.py); the eval flags are train.py's eval_config_dict keys.
---out gets one <name>.npz per scan (votenet/detect.py: Detections.save)."""
+--out gets one <name>.npz per scan (votenet/detect.py: Detections.save).  With --tile every scan is cut on the
+device into overlapping windows of TX x TY metres (votenet/scan_tiles.py: TileStore), each window is detected on
+like a room and the boxes are merged per scan (detect_tiled, TiledDetections.save); without it nothing changes."""
 import argparse
 import importlib
 import os
@@ -37,7 +40,21 @@ def parser():
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--synthetic', type=int, default=0, metavar='N', help='run on N synthetic scans')
     ap.add_argument('--seed', type=int, default=0, help='seed of the point sampling')
+    ap.add_argument('--tile', type=float, nargs='+', default=None, metavar='M',
+                    help='TX [TY]: cut every scan into windows of TX x TY metres (TY = TX) and merge their boxes '
+                         '(name the inputs before it, or another flag or -- behind it)')
+    ap.add_argument('--overlap', type=float, default=1.0, metavar='M', help='nominal overlap of the windows, metres')
+    ap.add_argument('--min_points', type=int, default=1, metavar='N', help='windows with fewer points are not built')
     return ap
+
+
+def tiling(flags):
+    """None without --tile (the plain path), else ((tx, ty), overlap, min_points)."""
+    if flags.tile is None:
+        return None
+    if len(flags.tile) > 2:
+        raise SystemExit("--tile TX [TY]: one or two sizes, got %d" % len(flags.tile))
+    return (flags.tile[0], flags.tile[-1]), flags.overlap, flags.min_points
 
 
 def input_feature_dim(flags):
@@ -77,6 +94,7 @@ def cloud_files(inputs):
 
 def main(argv=None):
     flags = parser().parse_args(argv)
+    tiles = tiling(flags)
     if not flags.synthetic and not flags.inputs:
         raise SystemExit("cloud files or a directory (or --synthetic N)")
     if not flags.synthetic and flags.checkpoint is None:
@@ -109,8 +127,15 @@ def main(argv=None):
     if state is not None:
         detector.load_state_dict(state)
     detector = detector.to(dev).eval()
-    found = V.detect(I.InferenceEngine(detector), loader, eval_config_dict(cfg, flags),
-                     batch_size=flags.batch_size, opt_step=flags.opt_step, opt_rate=flags.opt_rate)
+    run = V.detect
+    if tiles is not None:
+        ST = importlib.import_module("3dioumatch_amd.votenet.scan_tiles")
+        store = ST.TileStore.from_store(store, tiles[0], overlap=tiles[1], min_points=tiles[2])
+        loader = SC.ScanLoader(store, num_point, use_color=flags.use_color, use_height=not flags.no_height,
+                               seed=flags.seed)
+        run = V.detect_tiled
+    found = run(I.InferenceEngine(detector), loader, eval_config_dict(cfg, flags),
+                batch_size=flags.batch_size, opt_step=flags.opt_step, opt_rate=flags.opt_rate)
     counts = found.planes()["count"]
     for name, c in zip(found.names, counts):
         print("%s: %d boxes" % (name, int(c)))
