@@ -16,4 +16,5 @@ from .train_meter import TrainMeter, tb_name  # noqa: F401
 from .trainer import Trainer, engine_evaluator, loader_epochs  # noqa: F401
 from .scan_data import ScanLoader, ScanStore  # noqa: F401
 from .detect import Detections, TiledDetections, detect, detect_tiled  # noqa: F401
+from .detect import host_merge_nms, merge_nms_gpu, seam_reach, seam_settings  # noqa: F401
 from .scan_tiles import TileStore, tile_grid  # noqa: F401

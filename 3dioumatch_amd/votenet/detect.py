@@ -26,6 +26,8 @@ Rows past `count` are zero.  `host_pack` restates the rule in numpy.
 
 detect_tiled() is the same loop over the tiles of a scan_tiles.TileStore and one merge launch into a
 second arena, one set of boxes per parent scan (see the section at the end; `host_merge` restates it).
+With seam_nms=True that merge is an NMS across the cuts, one box per object that two tiles see
+(scene_detections_merge_nms, four launches; the last section; `host_merge_nms` restates it).
 """
 import ctypes
 import importlib
@@ -254,8 +256,9 @@ def detect(engine, store_or_loader, config_dict, batch_size=8, opt_step=0, opt_r
 # scan):
 #     count (S,), tile (S, cap) i32: the row's tile (its row in the tile store), proposal, cls (S, cap),
 #     score (S, cap) or (S, cap, NC), box (S, cap, 7), corners (S, cap, 8, 3)
-# Rows past `count` are zero.  There is no cross-tile NMS: a box whose centre two neighbouring tiles
-# estimate on opposite sides of a cut may be kept twice or not at all.
+# Rows past `count` are zero.  This merge has no cross-tile NMS: a box whose centre two neighbouring
+# tiles estimate on opposite sides of a cut may be kept twice or not at all (seam_nms, further down, is
+# the merge that has one).
 MERGED_PLANES = ("count", "tile", "proposal", "cls", "score", "box", "corners")
 
 
@@ -354,13 +357,16 @@ def merged_map_cls_of(rows, num_class, per_class):
 class TiledDetections(Detections):
     """The merged detections of a detect_tiled run, one set per PARENT scan, over the merged layout;
     `tiles` is the Detections of the tiles themselves (the first arena) and `store` the TileStore.
-    Reading makes the one device -> host copy of the merged arena."""
+    `seam` is None for the plain merge, else the settings of the NMS across the cuts (seam, thresh,
+    old_type, same_class, dims) and `reach` its (T, 4) table.  Reading makes the one device -> host
+    copy of the merged arena."""
     INT_PLANES = Detections.INT_PLANES + ("tile",)
 
-    def __init__(self, arena, store, cap, K, NC, num_class, tiles=None):
+    def __init__(self, arena, store, cap, K, NC, num_class, tiles=None, seam=None, reach=None):
         self.arena, self.names, self.K, self.NC, self.num_class = arena, list(store.parent_names), int(K), int(NC), \
             int(num_class)
         self.store, self.cap, self.tiles = store, int(cap), tiles
+        self.seam, self.reach = seam, reach
         self.per_class_proposal = NC > 0
         self.layout, _ = merged_layout(len(self.names), self.cap, self.NC)
         self._planes = None
@@ -371,36 +377,244 @@ class TiledDetections(Detections):
     def save(self, directory):
         """<scan>.npz per parent scan: count, the planes cut to `count` rows (`tile` among them: rows of
         the tile store), and of the scan's tiles `tile_first` (the store row of its first tile),
-        `tile_names`, `window` and `core` (tiles, 4)."""
+        `tile_names`, `window` and `core` (tiles, 4); after an NMS across the cuts also `seam`,
+        `seam_thresh`, `seam_old_type`, `seam_same_class`, `seam_dims` and `reach` (tiles, 4)."""
         os.makedirs(directory, exist_ok=True)
         st = self.store
         for i, name in enumerate(self.names):
             rows = self[i]
             c = int(rows["count"])
             a, b = int(st.first[i]), int(st.first[i] + st.tiles[i])
+            extra = {}
+            if self.seam is not None:
+                extra = {"seam": np.float64(self.seam["seam"]), "seam_thresh": np.float64(self.seam["thresh"]),
+                         "seam_old_type": np.int32(self.seam["old_type"]),
+                         "seam_same_class": np.int32(self.seam["same_class"]),
+                         "seam_dims": np.int32(self.seam["dims"]), "reach": self.reach[a:b]}
             np.savez(os.path.join(directory, name + ".npz"), count=rows["count"], tile_first=np.int32(a),
                      tile_names=np.array(st.names[a:b]), window=st.window[a:b], core=st.core[a:b],
-                     **{k: v[:c] for k, v in rows.items() if k != "count"})
+                     **extra, **{k: v[:c] for k, v in rows.items() if k != "count"})
 
 
 @torch.no_grad()
-def detect_tiled(engine, tile_store_or_loader, config_dict, batch_size=8, opt_step=0, opt_rate=5e-4, counter=0):
+def detect_tiled(engine, tile_store_or_loader, config_dict, batch_size=8, opt_step=0, opt_rate=5e-4, counter=0,
+                 seam_nms=False, seam=None):
     """detect() for scans larger than a room: the tiles of a scan_tiles.TileStore (or of a ScanLoader
     over one) through detect()'s loop, then ONE merge launch -> TiledDetections, one set per parent
-    scan in the scan's own frame.  No host copy and no synchronising op before the result is read."""
+    scan in the scan's own frame.  No host copy and no synchronising op before the result is read.
+
+    seam_nms: merge with an NMS across the cuts instead (scene_detections_merge_nms, four launches;
+    the section below) over the rows whose centre lies within `seam` metres of their tile's core;
+    seam None: the store's overlap / 2.  The settings are config_dict's nms_iou, use_old_type_nms,
+    use_3d_nms and cls_nms (seam_settings)."""
     from .scan_tiles import TileStore
     loader = tile_store_or_loader
     store = loader.store if isinstance(loader, ScanLoader) else loader
     if not isinstance(store, TileStore):
         raise ValueError("detect_tiled: a TileStore or a ScanLoader over one")
+    if seam is not None and not seam_nms:
+        raise ValueError("detect_tiled: seam = %r without seam_nms" % (seam,))
+    settings = reach = None
+    if seam_nms:
+        settings = seam_settings(config_dict, store.overlap / 2 if seam is None else seam)
+        reach = seam_reach(store.core, settings["seam"])  # refused before the first launch
     store, arena, K, NC = _pack_run("detect_tiled", engine, loader, config_dict, batch_size, opt_step, opt_rate,
                                     counter)
     S, T = len(store.parent_names), len(store)
     max_tiles = int(store.tiles.max())
     cap = max_tiles * K
+    d = store.dev
     with torch.cuda.device(engine.device):
         merged = new_merged_arena(S, cap, NC, arena.device)
-        merge_gpu(merged, arena, store.dev["first"], store.dev["tiles"], store.dev["core"], S, T, K, NC, cap,
-                  max_tiles)
+        if seam_nms:
+            if settings["seam"] not in store.reach_dev:  # one upload per seam width
+                store.reach_dev[settings["seam"]] = torch.from_numpy(reach).to(arena.device)
+            merge_nms_gpu(merged, arena, d["first"], d["tiles"], d["core"], d["iy"], d["ix"],
+                          store.reach_dev[settings["seam"]], S, T, K, NC, cap, max_tiles, settings["thresh"],
+                          settings["old_type"], settings["same_class"], settings["dims"])
+        else:
+            merge_gpu(merged, arena, d["first"], d["tiles"], d["core"], S, T, K, NC, cap, max_tiles)
     num_class = config_dict['dataset_config'].num_class
-    return TiledDetections(merged, store, cap, K, NC, num_class, Detections(arena, store.names, K, NC, num_class))
+    return TiledDetections(merged, store, cap, K, NC, num_class, Detections(arena, store.names, K, NC, num_class),
+                           seam=settings, reach=reach)
+
+
+# ------------------------------------------------------------------ an NMS across the cuts
+# Each tile estimates the centre of an object near a cut on its own, so the plain merge may keep the
+# object twice (both tiles put the centre on their own side) or not at all (each puts it on the
+# other's).  scene_detections_merge_nms (include/scan_tile_hip.h) therefore looks past the core:
+#   reach      the core grown by `seam` metres on every finite side; float64 on the host, rounded once.
+#   candidate  a packed row whose centre lies in its tile's reach; OWNED if it lies in the core, else
+#              a GUEST.
+#   bounds     min / max of the row's eight packed corners per axis (float32, camera frame: what
+#              nms_3d_faster sees); area / volume, intersection and overlap in float64 in the
+#              expression order of nms_aabb_block_kernel; dims 2: the camera x / z footprint.
+#   key        score[row], or score[row, cls[row]] with per-class scores; the order is key
+#              descending, then tile, then packed row ascending.
+#   partners   two candidates of different, neighbouring tiles of one scan (|iy - iy'| <= 1 and
+#              |ix - ix'| <= 1) whose overlap is > thresh.  Rows of one tile never interact: the
+#              per-tile NMS has judged them.
+#   winner     in that order, a candidate none of whose higher-ordered partners is a winner.
+#   kept       an owned winner; a guest that is a winner AND has a partner.  An unmatched guest is
+#              dropped, so where no two tiles' boxes overlap the result is the plain merge.
+# The output is the merged layout above, the kept rows in tile order and packed order.
+def seam_settings(config_dict, seam):
+    """{seam, thresh, old_type, same_class, dims} of the NMS across the cuts from parse_predictions'
+    keys: nms_iou, use_old_type_nms, dims 3 with use_3d_nms else 2, and cls_nms in 3-D only, as
+    parse_predictions_device applies them.  use_iou_for_nms is NOT consulted: the key is the packed
+    score, whatever the per-tile NMS ranked by."""
+    dims = 3 if config_dict['use_3d_nms'] else 2
+    return {"seam": float(seam), "thresh": float(config_dict['nms_iou']),
+            "old_type": int(bool(config_dict['use_old_type_nms'])),
+            "same_class": int(bool(config_dict['cls_nms']) and dims == 3), "dims": dims}
+
+
+class _SeamArgs(ctypes.Structure):  # field order == include/scan_tile_hip.h ScanSeamArgs
+    _fields_ = (list(_MergeArgs._fields_) + [(n, _vp) for n in ("iy", "ix", "reach")] +
+                [("thresh", ctypes.c_double)] + [(n, _c_int) for n in ("old_type", "same_class", "dims")] +
+                [("scratch", _vp), ("scratch_bytes", ctypes.c_size_t)])
+
+
+def seam_reach(core, seam):
+    """(T, 4) float32 rlo_x, rhi_x, rlo_y, rhi_y: clo - seam, chi + seam in float64 from the float32
+    core, rounded once to float32; an infinite side stays infinite.  0 <= seam < inf."""
+    seam = float(seam)
+    if not 0 <= seam < np.inf:
+        raise ValueError("seam = %r metres: 0 <= seam" % (seam,))
+    core = np.asarray(core, np.float32).reshape(-1, 4).astype(np.float64)
+    reach = np.stack([core[:, 0] - seam, core[:, 1] + seam, core[:, 2] - seam, core[:, 3] + seam], 1)
+    return np.ascontiguousarray(reach.astype(np.float32))
+
+
+def host_merge_nms(planes, first, tiles, core, iy, ix, reach, thresh, old_type, same_class, dims, cap=None,
+                   info=None):
+    """The rule of the NMS across the cuts in numpy (the comment above), host_merge's arguments plus
+    iy, ix (T,), reach (T, 4) and the four settings -> the merged {plane: array}.  A sort and a loop
+    over the pairs in its order.  `info`, a dict, receives per scan `pairs` (partner pairs), `rounds`
+    (the longest chain of decisions that wait on one another), `kept_guests`, `dropped_owned`,
+    `most_candidates` (of one tile) and `most_above` (higher-ordered partners of one row)."""
+    if dims not in (2, 3) or (dims == 2 and same_class):
+        raise ValueError("host_merge_nms: dims 2 or 3, same_class with 3 only")
+    first, tiles = np.asarray(first, np.int64), np.asarray(tiles, np.int64)
+    core, reach = np.asarray(core, np.float32), np.asarray(reach, np.float32)
+    iy, ix = np.asarray(iy, np.int64), np.asarray(ix, np.int64)
+    thresh = float(thresh)
+    S, K = len(first), planes["proposal"].shape[1]
+    if cap is None:
+        cap = int(tiles.max()) * K
+    out = {"count": np.zeros(S, np.int32), "tile": np.zeros((S, cap), np.int32)}
+    for name in ("proposal", "cls", "score", "box", "corners"):
+        out[name] = np.zeros((S, cap) + planes[name].shape[2:], planes[name].dtype)
+    per_class = planes["score"].ndim == 3
+    stats = {k: [] for k in ("pairs", "rounds", "kept_guests", "dropped_owned", "most_candidates", "most_above")}
+    for s in range(S):
+        tile, row, owned = [], [], []
+        most = 0
+        for t in range(first[s], first[s] + tiles[s]):
+            c = int(planes["count"][t])
+            xy = np.asarray(planes["box"][t, :c, 0:2], np.float32)
+            x, y = xy[:, 0], xy[:, 1]
+            cand = (reach[t, 0] <= x) & (x < reach[t, 1]) & (reach[t, 2] <= y) & (y < reach[t, 3])
+            own = cand & (core[t, 0] <= x) & (x < core[t, 1]) & (core[t, 2] <= y) & (y < core[t, 3])
+            rs = np.nonzero(cand)[0]
+            most = max(most, len(rs))
+            tile += [t] * len(rs)
+            row += rs.tolist()
+            owned += own[rs].tolist()
+        tile, row, owned = np.array(tile, np.int64), np.array(row, np.int64), np.array(owned, bool)
+        cls = planes["cls"][tile, row].astype(np.int64)
+        key = np.asarray(planes["score"][tile, row, cls] if per_class else planes["score"][tile, row], np.float32)
+        order = np.lexsort((row, tile, -key))  # key descending, then tile, then packed row
+        tile, row, owned, cls, key = tile[order], row[order], owned[order], cls[order], key[order]
+        corners = np.asarray(planes["corners"][tile, row], np.float32).reshape(-1, 8, 3)
+        lo, hi = corners.min(1).astype(np.float64), corners.max(1).astype(np.float64)
+        ext = hi - lo
+        area = ext[:, 0] * ext[:, 2] if dims == 2 else ext[:, 0] * ext[:, 1] * ext[:, 2]
+        n = len(tile)
+        winner, partners, above = np.zeros(n, bool), np.zeros(n, np.int64), np.zeros(n, np.int64)
+        rounds = np.zeros(n, np.int64)
+        for i in range(n):  # row i against every row j above it
+            j = slice(0, i)
+            d = np.minimum(hi[j], hi[i]) - np.maximum(lo[j], lo[i])
+            d = np.where(d > 0, d, 0.0)
+            inter = d[:, 0] * d[:, 2] if dims == 2 else d[:, 0] * d[:, 1] * d[:, 2]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                o = inter / area[i] if old_type else inter / (area[j] + area[i] - inter)
+                if same_class:
+                    o = o * (cls[j] == cls[i]).astype(np.float64)
+                near = (tile[j] != tile[i]) & (np.abs(iy[tile[j]] - iy[tile[i]]) <= 1) & \
+                    (np.abs(ix[tile[j]] - ix[tile[i]]) <= 1)
+                p = np.nonzero(near & (o > thresh))[0]  # 0 / 0 is NaN: compares false
+            partners[i] += len(p)
+            partners[p] += 1
+            above[i] = len(p)
+            winner[i] = not winner[p].any()
+            if len(p):
+                rounds[i] = (rounds[p].max() if winner[i] else rounds[p[winner[p]]].min()) + 1
+        kept = winner & (owned | (partners > 0))
+        ks = np.nonzero(kept)[0]
+        ks = ks[np.lexsort((row[ks], tile[ks]))]  # tile store order, then packed order
+        c = len(ks)
+        out["count"][s] = c
+        out["tile"][s, :c] = tile[ks]
+        for name in ("proposal", "cls", "score", "box", "corners"):
+            out[name][s, :c] = planes[name][tile[ks], row[ks]]
+        for k, v in (("pairs", int(partners.sum()) // 2), ("rounds", int(rounds.max()) if n else 0),
+                     ("kept_guests", int((kept & ~owned).sum())), ("dropped_owned", int((owned & ~kept).sum())),
+                     ("most_candidates", most), ("most_above", int(above.max()) if n else 0)):
+            stats[k].append(v)
+    if info is not None:
+        info.update(stats)
+    return out
+
+
+def seam_scratch_bytes(S, T, K, max_tiles):
+    """scene_detections_merge_nms_scratch_bytes"""
+    _L = importlib.import_module("3dioumatch_amd._lib")
+    return int(_L.lib.scene_detections_merge_nms_scratch_bytes(S, T, K, max_tiles))
+
+
+def merge_nms_gpu(merged, tile_arena, first, tiles, core, iy, ix, reach, S, T, K, NC, cap, max_tiles, thresh,
+                  old_type, same_class, dims, scratch=None):
+    """Launch scene_detections_merge_nms: merge_gpu's arguments plus iy, ix (T,) int32, reach (T, 4)
+    float32 on the arenas' device and the four settings (seam_settings); `scratch`: a float64
+    tensor of at least seam_scratch_bytes(S, T, K, max_tiles) bytes, allocated here when None
+    (uninitialised: the launches write every word they read)."""
+    _L = importlib.import_module("3dioumatch_amd._lib")
+    who = "scene_detections_merge_nms"
+    if K > MAX_K:
+        raise ValueError("%s: K = %d rows per tile, at most %d" % (who, K, MAX_K))
+    if cap < max_tiles * K:
+        raise ValueError("%s: cap = %d rows per scan, %d tiles of %d need %d" % (who, cap, max_tiles, K, max_tiles * K))
+    if dims not in (2, 3) or (dims == 2 and same_class):
+        raise ValueError("%s: dims = %r (2 or 3) with same_class = %r (3-D only)" % (who, dims, same_class))
+    lin, words_in = arena_layout(T, K, NC)
+    lout, words_out = merged_layout(S, cap, NC)
+    for name, t, words in (("tile arena", tile_arena, words_in), ("merged arena", merged, words_out)):
+        if t.dtype != torch.float32 or t.numel() != words or not t.is_contiguous() or t.device != merged.device:
+            raise ValueError("%s: the %s does not match (S, T, K, C, cap) = (%d, %d, %d, %d, %d)"
+                             % (who, name, S, T, K, NC, cap))
+    for name, t, dtype, shape in (("first", first, torch.int32, (S,)), ("tiles", tiles, torch.int32, (S,)),
+                                  ("core", core, torch.float32, (T, 4)), ("iy", iy, torch.int32, (T,)),
+                                  ("ix", ix, torch.int32, (T,)), ("reach", reach, torch.float32, (T, 4))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != merged.device:
+            raise ValueError("%s: %s must be %s %s on %s" % (who, name, dtype, shape, merged.device))
+    need = seam_scratch_bytes(S, T, K, max_tiles)
+    if scratch is None:
+        scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=merged.device)
+    if scratch.dtype != torch.float64 or not scratch.is_contiguous() or scratch.device != merged.device or \
+            scratch.numel() * 8 < need:
+        raise ValueError("%s: the scratch must be float64, contiguous, %d bytes on %s" % (who, need, merged.device))
+    a = _SeamArgs()
+    a.S, a.K, a.NC, a.cap, a.max_tiles = S, K, NC, cap, max_tiles
+    a.first, a.tiles, a.core = first.data_ptr(), tiles.data_ptr(), core.data_ptr()
+    a.iy, a.ix, a.reach = iy.data_ptr(), ix.data_ptr(), reach.data_ptr()
+    a.thresh, a.old_type, a.same_class, a.dims = float(thresh), int(old_type), int(same_class), int(dims)
+    a.scratch, a.scratch_bytes = scratch.data_ptr(), scratch.numel() * 8
+    for plane in PLANES:
+        setattr(a, plane + "_in", tile_arena.data_ptr() + 4 * lin[plane][0])
+    for plane in MERGED_PLANES:
+        setattr(a, plane, merged.data_ptr() + 4 * lout[plane][0])
+    with torch.cuda.device(merged.device):
+        _L.check(_L.lib.scene_detections_merge_nms(ctypes.byref(a), _L.current_stream_ptr(merged.device)), who)
+    return merged

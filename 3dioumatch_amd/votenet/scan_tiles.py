@@ -220,8 +220,9 @@ class TileStore(ScanStore):
     """A ScanStore whose scans are the built tiles of `store`'s scans (`from_store`).  Beyond
     ScanStore's fields: `parent` (T,) the scan of each tile, `first`, `tiles` (S,) each scan's run of
     tiles, `iy`, `ix` (T,) the tile's place in its scan's grid, `window`, `core` (T, 4) float32 (host,
-    and in `dev`), `parent_names`, `source` (the parent store).  `clouds` (host rows) and `floor`
-    (host copy) are filled at first use."""
+    and in `dev`), `parent_names`, `source` (the parent store), `tile` (tx, ty) and `overlap` as
+    given, `reach_dev` (detect_tiled's device tables of its NMS across the cuts, by seam width).
+    `clouds` (host rows) and `floor` (host copy) are filled at first use."""
 
     def __init__(self, *args, **kwargs):
         raise TypeError("TileStore is built by TileStore.from_store(store, tile, overlap, min_points)")
@@ -232,6 +233,7 @@ class TileStore(ScanStore):
             raise ValueError("TileStore.from_store: a ScanStore (not itself a TileStore)")
         _check_overlap(*_tile_sizes(tile), overlap)  # refused before the first launch
         self = object.__new__(cls)
+        self.tile, self.overlap, self.reach_dev = _tile_sizes(tile), float(overlap), {}
         self.source, self.dataset, self.columns = store, store.dataset, store.columns
         self.device, self.dev, self.parent_names = store.device, None, list(store.names)
         self._clouds = self._floor = None
@@ -252,7 +254,7 @@ class TileStore(ScanStore):
         self._grid_fields(grid, built)
         self.count, self.offset, base = gather_bases(counts[built])
         self.dev = {k: to_device(getattr(self, k), self.device)
-                    for k in ("offset", "count", "parent", "window", "core", "first", "tiles")}
+                    for k in ("offset", "count", "parent", "window", "core", "first", "tiles", "iy", "ix")}
         self.dev["cloud"] = tile_gather_gpu(d["cloud"], d["offset"], d["count"], self.dev["parent"],
                                             self.dev["window"], to_device(base, self.device),
                                             int(self.count.sum(dtype=np.int64)), G)

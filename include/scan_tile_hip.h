@@ -12,6 +12,8 @@
 #ifndef SCAN_TILE_HIP_H
 #define SCAN_TILE_HIP_H
 
+#include <stddef.h>
+
 #include "scan_hip.h" /* SCAN_MAX_K */
 
 #ifdef __cplusplus
@@ -117,6 +119,78 @@ typedef struct ScanMergeArgs {
  * hipErrorInvalidValue, without a launch: NULL args or pointer, S < 1, K outside 1..SCAN_MAX_K,
  * NC < 0, max_tiles < 1, cap < max_tiles * K. */
 int scene_detections_merge(const ScanMergeArgs *args, void *stream);
+
+#define SCAN_SEAM_PARTNERS 4 /* higher-ordered partners a row records; a row with more rescans its neighbours */
+
+typedef struct ScanSeamArgs {
+  int S;                   /* parent scans */
+  int K;                   /* rows per tile of the tile arena, <= SCAN_MAX_K */
+  int NC;                  /* > 0: per-class scores; 0: one score per row */
+  int cap;                 /* rows per scan of the merged arena */
+  int max_tiles;           /* the most tiles any scan has, <= SCAN_TILE_MAX: cap >= max_tiles * K */
+  const int *first;        /* (S,) each scan's first tile */
+  const int *tiles;        /* (S,) each scan's number of tiles, <= max_tiles */
+  const float *core;       /* (T, 4) clo_x, chi_x, clo_y, chi_y */
+  /* the tile arena, as ScanMergeArgs */
+  const int *count_in;     /* (T,) */
+  const int *proposal_in;  /* (T, K) */
+  const int *cls_in;       /* (T, K) */
+  const float *score_in;   /* (T, K) or (T, K, NC) */
+  const float *box_in;     /* (T, K, 7) */
+  const float *corners_in; /* (T, K, 8, 3) */
+  /* the merged arena, as ScanMergeArgs; count: the scan's kept rows */
+  int *count;              /* (S,) */
+  int *tile;               /* (S, cap) */
+  int *proposal;           /* (S, cap) */
+  int *cls;                /* (S, cap) */
+  float *score;            /* (S, cap) or (S, cap, NC) */
+  float *box;              /* (S, cap, 7) */
+  float *corners;          /* (S, cap, 8, 3) */
+  /* the seam */
+  const int *iy;           /* (T,) the tile's row in its scan's grid */
+  const int *ix;           /* (T,) the tile's column */
+  const float *reach;      /* (T, 4) rlo_x, rhi_x, rlo_y, rhi_y: the core grown by the seam width on its finite sides */
+  double thresh;           /* two rows are partners where their overlap is > thresh */
+  int old_type;            /* overlap = intersection / area of the lower-ordered row, not / union */
+  int same_class;          /* rows of different classes never overlap; dims == 3 only */
+  int dims;                /* 3: volumes of the bounds; 2: areas of their camera x / z footprint */
+  void *scratch;           /* scene_detections_merge_nms_scratch_bytes(S, T, K, max_tiles) bytes, 8-byte aligned */
+  size_t scratch_bytes;    /* the size of `scratch` */
+} ScanSeamArgs;
+
+/* The size of ScanSeamArgs.scratch for S scans of T tiles in all, K rows per tile, at most max_tiles
+ * tiles per scan: per row of (scan, tile of the scan, packed row) the flags, the key, six float32
+ * bounds, the float64 area, the partner counts, SCAN_SEAM_PARTNERS partner rows and the state of the
+ * resolve.  A host function; 0 where an argument is < 1.  (T does not enter today: the rows are
+ * addressed by scan and tile of the scan, so that the launches stay inside the buffer whatever
+ * `first` holds.) */
+size_t scene_detections_merge_nms_scratch_bytes(int S, int T, int K, int max_tiles);
+
+/* scene_detections_merge with an NMS across the cuts: one box per object that two neighbouring tiles
+ * both see.  Four launches, none of which waits on another workgroup:
+ *   rows      per (scan, tile, 256 rows): row r < count_in is a CANDIDATE iff its box centre lies in the
+ *             tile's reach (the four compares above), OWNED iff it lies in the core, else a GUEST; its
+ *             bounds are the min / max of its eight corners per axis, its area / volume their float64
+ *             product ((x2 - x1) * (y2 - y1)) * (z2 - z1), or (x2 - x1) * (z2 - z1) for dims == 2, its key
+ *             score[row] (NC == 0) or score[row, cls[row]].
+ *   partners  per candidate: the candidates of the other tiles of its scan with |iy - iy'| <= 1 and
+ *             |ix - ix'| <= 1 whose overlap with it is > thresh -- float64, intersection l * w * h (l * h
+ *             for dims == 2) of the clamped extents, / (area_hi + area_lo - intersection), or / area_lo with
+ *             old_type, times (cls == cls') with same_class; 0 / 0 compares false.  It counts them and
+ *             records the first SCAN_SEAM_PARTNERS that are ordered above it: key descending, then tile,
+ *             then packed row ascending.  A candidate with none above it is a WINNER at once.
+ *   resolve   one workgroup per scan, in rounds: a candidate loses as soon as a partner above it has
+ *             won in an earlier round and wins once all of them have lost -- the greedy NMS in that
+ *             order.  Every round decides the highest undecided row, so the loop is a `for` over at
+ *             most the undecided rows; a row with more partners above it than it recorded rescans.
+ *   write     scene_detections_merge's compaction with KEPT in place of owned: an owned winner, or a
+ *             guest that won and has at least one partner.  Same layout, rows past `count` zero.
+ * Rows of one tile never interact.  The scratch may arrive uninitialised: every word is written
+ * before it is read.
+ * hipErrorInvalidValue, without a launch: NULL args or pointer, S < 1, K outside 1..SCAN_MAX_K,
+ * NC < 0, max_tiles outside 1..SCAN_TILE_MAX, cap < max_tiles * K, dims not 2 or 3, dims == 2 with
+ * same_class, a scratch that is misaligned or smaller than the size above. */
+int scene_detections_merge_nms(const ScanSeamArgs *args, void *stream);
 
 #ifdef __cplusplus
 }

@@ -4,13 +4,16 @@
     python tools/detect.py --checkpoint log/checkpoint.tar --out boxes a.npy b_pc.npz --dataset sunrgbd
     python tools/detect.py --synthetic 16 --out /tmp/boxes                             # no data, seeded weights
     python tools/detect.py --checkpoint log/checkpoint.tar --out boxes floor.ply --tile 8 6 --overlap 1.0  # larger than a room
+    python tools/detect.py --checkpoint log/checkpoint.tar --out boxes floor.ply --tile 8 --seam-nms       # ... one box per object on a cut
 
 Inputs are (n, 3) xyz or (n, 6) xyz + rgb clouds: `.npy` files, `.npz` files with a `pc` member, `.ply`
 files (their vertices, as they are), `.mat` depth clouds (SUN RGB-D's `instance`), or a directory of them.  --num_point / --use_color / --no_height /
 --num_target must be those the checkpoint was trained with (tools/train.py); the eval flags are train.py's eval_config_dict keys.
 --out gets one <name>.npz per scan (votenet/detect.py: Detections.save).  With --tile every scan is cut on the
 device into overlapping windows of TX x TY metres (votenet/scan_tiles.py: TileStore), each window is detected on
-like a room and the boxes are merged per scan (detect_tiled, TiledDetections.save); without it nothing changes."""
+like a room and the boxes are merged per scan (detect_tiled, TiledDetections.save); without it nothing changes.
+With --seam-nms the merge runs an NMS across the cuts (one box per object that two windows both see) over the boxes
+whose centre lies within --seam metres of their window's core, and the files also hold its settings and `reach`."""
 import argparse
 import importlib
 import os
@@ -45,6 +48,10 @@ def parser():
                          '(name the inputs before it, or another flag or -- behind it)')
     ap.add_argument('--overlap', type=float, default=1.0, metavar='M', help='nominal overlap of the windows, metres')
     ap.add_argument('--min_points', type=int, default=1, metavar='N', help='windows with fewer points are not built')
+    ap.add_argument('--seam-nms', dest='seam_nms', action='store_true',
+                    help='with --tile: merge with an NMS across the cuts, one box per object that two windows see')
+    ap.add_argument('--seam', type=float, default=None, metavar='M',
+                    help='with --seam-nms: how far past its core a window still votes, metres [overlap / 2]')
     return ap
 
 
@@ -55,6 +62,19 @@ def tiling(flags):
     if len(flags.tile) > 2:
         raise SystemExit("--tile TX [TY]: one or two sizes, got %d" % len(flags.tile))
     return (flags.tile[0], flags.tile[-1]), flags.overlap, flags.min_points
+
+
+def seam_flags(flags):
+    """detect_tiled's seam arguments: {} without --seam-nms."""
+    if not flags.seam_nms:
+        if flags.seam is not None:
+            raise SystemExit("--seam M goes with --seam-nms")
+        return {}
+    if flags.tile is None:
+        raise SystemExit("--seam-nms goes with --tile")
+    if flags.seam is not None and not flags.seam >= 0:
+        raise SystemExit("--seam M: 0 <= M, got %r" % flags.seam)
+    return {"seam_nms": True, "seam": flags.seam}
 
 
 def input_feature_dim(flags):
@@ -95,6 +115,7 @@ def cloud_files(inputs):
 def main(argv=None):
     flags = parser().parse_args(argv)
     tiles = tiling(flags)
+    seam = seam_flags(flags)
     if not flags.synthetic and not flags.inputs:
         raise SystemExit("cloud files or a directory (or --synthetic N)")
     if not flags.synthetic and flags.checkpoint is None:
@@ -135,7 +156,7 @@ def main(argv=None):
                                seed=flags.seed)
         run = V.detect_tiled
     found = run(I.InferenceEngine(detector), loader, eval_config_dict(cfg, flags),
-                batch_size=flags.batch_size, opt_step=flags.opt_step, opt_rate=flags.opt_rate)
+                batch_size=flags.batch_size, opt_step=flags.opt_step, opt_rate=flags.opt_rate, **seam)
     counts = found.planes()["count"]
     for name, c in zip(found.names, counts):
         print("%s: %d boxes" % (name, int(c)))

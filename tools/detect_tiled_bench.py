@@ -2,6 +2,7 @@
 host restatement, in ONE process.
 
     python tools/detect_tiled_bench.py [--repeats 3] [--out profiles/detect_tiled.json]
+    python tools/detect_tiled_bench.py --seam [--repeats 5] [--out profiles/detect_tiled_seam.json]
 
 Two workloads, ScanNet config, random weights, B = 8, N = 40 000:
   big    one synthetic scan of 1 M points over 28 m x 20 m, tiles of 8 m x 6 m with 1 m overlap: 4 x 4;
@@ -14,7 +15,14 @@ clouds to host-readable merged detections of
       detect, host_merge,
 alternated per repeat after a warm-up of each.  On `rooms` also detect() on the parent store against
 detect_tiled() on its one-tile TileStore (stores built before the clock starts), alternated, with the
-merge launch's device time next to them.  One JSON line; nothing here asserts a time."""
+merge launch's device time next to them.  One JSON line; nothing here asserts a time.
+
+--seam times the NMS across the cuts instead, on `big` alone (seam_arm): the four launches of
+scene_detections_merge_nms together against the plain merge launch between device events,
+detect_tiled() with and without seam_nms end to end, alternated, detect() on the tiles (the forward
+passes alone), host_merge_nms on the same arena, and the partner pairs and resolve rounds of the run.
+The launches one by one come from a kernel trace of this arm (seam_rows_kernel, seam_partners_kernel,
+seam_resolve_kernel, seam_write_kernel; tile_merge_kernel is the plain merge)."""
 import argparse
 import importlib
 import json
@@ -119,6 +127,45 @@ def launches(engine, clouds, cd):
                 int(tiles.tiles.max())))}
 
 
+def seam_arm(engine, clouds, cd, repeats):
+    """the --seam arm on `clouds` (module docstring)"""
+    parent = SC.ScanStore(clouds, DEV, "scannet")
+    tiles = ST.TileStore.from_store(parent, TILE, overlap=OVERLAP)
+    loader = SC.ScanLoader(tiles, N)
+    t = tiles.dev
+    found = V.detect_tiled(engine, loader, cd, batch_size=B, seam_nms=True)
+    S, T, K, NC, cap, most = len(parent), len(tiles), found.K, found.NC, found.cap, int(tiles.tiles.max())
+    st = found.seam
+    reach = tiles.reach_dev[st["seam"]]
+    merged = D.new_merged_arena(S, cap, NC, DEV)
+    scratch = torch.empty((D.seam_scratch_bytes(S, T, K, most) + 7) // 8, dtype=torch.float64, device=DEV)
+    row = {"scans": S, "tiles": T, "K": K, "cap": cap, "seam": st, "scratch_bytes": scratch.numel() * 8,
+           "scene_detections_merge_ms": device_ms(lambda: D.merge_gpu(
+               merged, found.tiles.arena, t["first"], t["tiles"], t["core"], S, T, K, NC, cap, most)),
+           "scene_detections_merge_nms_ms": device_ms(lambda: D.merge_nms_gpu(
+               merged, found.tiles.arena, t["first"], t["tiles"], t["core"], t["iy"], t["ix"], reach, S, T, K, NC, cap,
+               most, st["thresh"], st["old_type"], st["same_class"], st["dims"], scratch=scratch))}
+    times = wall((("seam_off", lambda: V.detect_tiled(engine, loader, cd, batch_size=B).planes()),
+                  ("seam_on", lambda: V.detect_tiled(engine, loader, cd, batch_size=B, seam_nms=True).planes()),
+                  ("tiles_only", lambda: V.detect(engine, loader, cd, batch_size=B).planes())), repeats)
+    for k, v in times.items():
+        row["detect_tiled_%s_s" % k] = round(statistics.median(v), 5)
+        row["detect_tiled_%s_s_repeats" % k] = [round(x, 5) for x in v]
+    planes, host, info = found.tiles.planes(), [], {}
+    for _ in range(3):
+        t0 = time.perf_counter()
+        want = D.host_merge_nms(planes, tiles.first, tiles.tiles, tiles.core, tiles.iy, tiles.ix, found.reach,
+                                st["thresh"], st["old_type"], st["same_class"], st["dims"], info=info)
+        host.append(time.perf_counter() - t0)
+    plain = D.host_merge(planes, tiles.first, tiles.tiles, tiles.core)
+    row.update({"host_merge_nms_s": round(statistics.median(host), 5), "packed_rows": int(planes["count"].sum()),
+                "kept_rows": int(found.planes()["count"].sum()), "plain_rows": int(plain["count"].sum()),
+                "device_is_host": bool(np.array_equal(found.planes()["count"], want["count"])),
+                "partner_pairs": info["pairs"], "resolve_rounds": info["rounds"],
+                "kept_guests": info["kept_guests"], "dropped_owned": info["dropped_owned"]})
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=3)
@@ -126,6 +173,7 @@ def main():
     ap.add_argument("--rooms", type=int, default=64)
     ap.add_argument("--room_points", type=int, default=150000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--seam", action="store_true", help="time the NMS across the cuts on `big` instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("detect_tiled_bench: needs the GPU (no timing without it)")
@@ -135,8 +183,13 @@ def main():
     out = {"what": "detect_tiled() against the host restatement; tiles of %g m x %g m, overlap %g m, B = %d, "
                    "N = %d, ScanNet config" % (TILE + (OVERLAP, B, N)),
            "device": torch.cuda.get_device_name(0), "repeats": args.repeats}
-    for name, clouds in (("big", big_cloud(args.big_points, 2)),
-                         ("rooms", SC.synthetic_clouds(args.rooms, args.room_points, seed=1, color=False))):
+    if args.seam:
+        out["what"] = "detect_tiled(seam_nms=True) against the plain merge; " + out["what"].split("; ", 1)[1]
+        out["big"] = seam_arm(engine, big_cloud(args.big_points, 2), cd, args.repeats)
+    workloads = () if args.seam else (
+        ("big", big_cloud(args.big_points, 2)),
+        ("rooms", SC.synthetic_clouds(args.rooms, args.room_points, seed=1, color=False)))
+    for name, clouds in workloads:
         times = wall((("detect_tiled", lambda: run_device(engine, clouds, cd)),
                       ("host", lambda: run_host(engine, clouds, cd))), args.repeats)
         row = launches(engine, clouds, cd)
