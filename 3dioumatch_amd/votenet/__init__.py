@@ -18,3 +18,4 @@ from .scan_data import ScanLoader, ScanStore  # noqa: F401
 from .detect import Detections, TiledDetections, detect, detect_tiled  # noqa: F401
 from .detect import host_merge_nms, merge_nms_gpu, seam_reach, seam_settings  # noqa: F401
 from .scan_tiles import TileStore, tile_grid  # noqa: F401
+from .scan_voxels import VoxelStore, host_voxels  # noqa: F401

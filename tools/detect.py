@@ -5,6 +5,7 @@
     python tools/detect.py --synthetic 16 --out /tmp/boxes                             # no data, seeded weights
     python tools/detect.py --checkpoint log/checkpoint.tar --out boxes floor.ply --tile 8 6 --overlap 1.0  # larger than a room
     python tools/detect.py --checkpoint log/checkpoint.tar --out boxes floor.ply --tile 8 --seam-nms       # ... one box per object on a cut
+    python tools/detect.py --checkpoint log/checkpoint.tar --out boxes floor.ply --voxel 0.05 --tile 8     # one point per 5 cm cell first
 
 Inputs are (n, 3) xyz or (n, 6) xyz + rgb clouds: `.npy` files, `.npz` files with a `pc` member, `.ply`
 files (their vertices, as they are), `.mat` depth clouds (SUN RGB-D's `instance`), or a directory of them.  --num_point / --use_color / --no_height /
@@ -13,7 +14,9 @@ files (their vertices, as they are), `.mat` depth clouds (SUN RGB-D's `instance`
 device into overlapping windows of TX x TY metres (votenet/scan_tiles.py: TileStore), each window is detected on
 like a room and the boxes are merged per scan (detect_tiled, TiledDetections.save); without it nothing changes.
 With --seam-nms the merge runs an NMS across the cuts (one box per object that two windows both see) over the boxes
-whose centre lies within --seam metres of their window's core, and the files also hold its settings and `reach`."""
+whose centre lies within --seam metres of their window's core, and the files also hold its settings and `reach`.
+With --voxel every scan is first downsampled on the device to one point per occupied cell of V (or VX x VY x VZ) metres
+(votenet/scan_voxels.py: VoxelStore), before --tile where both are given; without it nothing changes."""
 import argparse
 import importlib
 import os
@@ -52,7 +55,26 @@ def parser():
                     help='with --tile: merge with an NMS across the cuts, one box per object that two windows see')
     ap.add_argument('--seam', type=float, default=None, metavar='M',
                     help='with --seam-nms: how far past its core a window still votes, metres [overlap / 2]')
+    ap.add_argument('--voxel', type=float, nargs='+', default=None, metavar='M',
+                    help='V or VX VY VZ: keep one point per occupied cell of that size, before --tile '
+                         '(name the inputs before it, or another flag or -- behind it)')
+    ap.add_argument('--voxel-keep', dest='voxel_keep', default=None, choices=('first', 'nearest'),
+                    help="with --voxel: the cell's first point, or the one nearest its centre [first]")
     return ap
+
+
+def voxeling(flags):
+    """None without --voxel (the plain path), else ((vx, vy, vz), keep)."""
+    if flags.voxel is None:
+        if flags.voxel_keep is not None:
+            raise SystemExit("--voxel-keep goes with --voxel")
+        return None
+    if len(flags.voxel) not in (1, 3):
+        raise SystemExit("--voxel V or VX VY VZ: one or three sizes, got %d" % len(flags.voxel))
+    if not all(0 < v < float("inf") for v in flags.voxel):
+        raise SystemExit("--voxel: sizes in metres, each > 0, got %r" % (flags.voxel,))
+    v = flags.voxel
+    return (v[0], v[len(v) // 2], v[-1]), flags.voxel_keep or "first"
 
 
 def tiling(flags):
@@ -116,6 +138,7 @@ def main(argv=None):
     flags = parser().parse_args(argv)
     tiles = tiling(flags)
     seam = seam_flags(flags)
+    voxels = voxeling(flags)
     if not flags.synthetic and not flags.inputs:
         raise SystemExit("cloud files or a directory (or --synthetic N)")
     if not flags.synthetic and flags.checkpoint is None:
@@ -142,6 +165,9 @@ def main(argv=None):
         store = SC.ScanStore(clouds, dev, flags.dataset)
     else:
         store = SC.ScanStore.from_files(cloud_files(flags.inputs), dev, flags.dataset)
+    if voxels is not None:
+        SV = importlib.import_module("3dioumatch_amd.votenet.scan_voxels")
+        store = SV.VoxelStore.from_store(store, voxels[0], keep=voxels[1])
     loader = SC.ScanLoader(store, num_point, use_color=flags.use_color, use_height=not flags.no_height,
                            seed=flags.seed)
     detector = step.build_detector(cfg, num_proposal=flags.num_target, input_feature_dim=input_feature_dim(flags))
