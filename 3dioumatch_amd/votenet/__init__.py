@@ -19,3 +19,4 @@ from .detect import Detections, TiledDetections, detect, detect_tiled  # noqa: F
 from .detect import host_merge_nms, merge_nms_gpu, seam_reach, seam_settings  # noqa: F401
 from .scan_tiles import TileStore, tile_grid  # noqa: F401
 from .scan_voxels import VoxelStore, host_voxels  # noqa: F401
+from .point_labels import PointLabels, host_label_points, label_points  # noqa: F401

@@ -6,6 +6,7 @@
     python tools/detect.py --checkpoint log/checkpoint.tar --out boxes floor.ply --tile 8 6 --overlap 1.0  # larger than a room
     python tools/detect.py --checkpoint log/checkpoint.tar --out boxes floor.ply --tile 8 --seam-nms       # ... one box per object on a cut
     python tools/detect.py --checkpoint log/checkpoint.tar --out boxes floor.ply --voxel 0.05 --tile 8     # one point per 5 cm cell first
+    python tools/detect.py --checkpoint log/checkpoint.tar --out boxes floor.ply --tile 8 --labels         # ... and which box owns each point
 
 Inputs are (n, 3) xyz or (n, 6) xyz + rgb clouds: `.npy` files, `.npz` files with a `pc` member, `.ply`
 files (their vertices, as they are), `.mat` depth clouds (SUN RGB-D's `instance`), or a directory of them.  --num_point / --use_color / --no_height /
@@ -16,7 +17,10 @@ like a room and the boxes are merged per scan (detect_tiled, TiledDetections.sav
 With --seam-nms the merge runs an NMS across the cuts (one box per object that two windows both see) over the boxes
 whose centre lies within --seam metres of their window's core, and the files also hold its settings and `reach`.
 With --voxel every scan is first downsampled on the device to one point per occupied cell of V (or VX x VY x VZ) metres
-(votenet/scan_voxels.py: VoxelStore), before --tile where both are given; without it nothing changes."""
+(votenet/scan_voxels.py: VoxelStore), before --tile where both are given; without it nothing changes.
+With --labels --out also gets <name>_labels.npz per scan (votenet/point_labels.py: label_points, PointLabels.save): for every
+point of the scan AS LOADED, before --voxel and --tile, the row of <name>.npz that owns it or -1, that row's class, and
+the points per row; --labels-prefer and --labels-min-score are label_points' arguments; without it nothing changes."""
 import argparse
 import importlib
 import os
@@ -60,7 +64,36 @@ def parser():
                          '(name the inputs before it, or another flag or -- behind it)')
     ap.add_argument('--voxel-keep', dest='voxel_keep', default=None, choices=('first', 'nearest'),
                     help="with --voxel: the cell's first point, or the one nearest its centre [first]")
+    ap.add_argument('--labels', action='store_true',
+                    help='with --out: also write <name>_labels.npz, the box that owns each point of the scan as it '
+                         'was loaded (before --voxel / --tile)')
+    ap.add_argument('--labels-prefer', dest='labels_prefer', default=None, choices=('score', 'smallest'),
+                    help='with --labels: a point inside several boxes goes to the best-scored or the smallest [score]')
+    ap.add_argument('--labels-min-score', dest='labels_min_score', type=float, default=None, metavar='X',
+                    help='with --labels: boxes scored below X own nothing [0]')
     return ap
+
+
+def labeling(flags):
+    """None without --labels (the plain path), else (prefer, min_score)."""
+    if not flags.labels:
+        if flags.labels_prefer is not None or flags.labels_min_score is not None:
+            raise SystemExit("--labels-prefer and --labels-min-score go with --labels")
+        return None
+    if not flags.out:
+        raise SystemExit("--labels goes with --out")
+    least = 0.0 if flags.labels_min_score is None else flags.labels_min_score
+    if not abs(least) < float("inf"):
+        raise SystemExit("--labels-min-score X: a finite score, got %r" % (least,))
+    return flags.labels_prefer or "score", least
+
+
+def write_labels(found, raw_store, labels, out):
+    """label_points of the detections on the store as it was loaded -> <name>_labels.npz in `out`."""
+    PL = importlib.import_module("3dioumatch_amd.votenet.point_labels")
+    result = PL.label_points(found, raw_store, prefer=labels[0], min_score=labels[1])
+    result.save(out)
+    return result
 
 
 def voxeling(flags):
@@ -139,6 +172,7 @@ def main(argv=None):
     tiles = tiling(flags)
     seam = seam_flags(flags)
     voxels = voxeling(flags)
+    labels = labeling(flags)
     if not flags.synthetic and not flags.inputs:
         raise SystemExit("cloud files or a directory (or --synthetic N)")
     if not flags.synthetic and flags.checkpoint is None:
@@ -165,6 +199,7 @@ def main(argv=None):
         store = SC.ScanStore(clouds, dev, flags.dataset)
     else:
         store = SC.ScanStore.from_files(cloud_files(flags.inputs), dev, flags.dataset)
+    raw = store
     if voxels is not None:
         SV = importlib.import_module("3dioumatch_amd.votenet.scan_voxels")
         store = SV.VoxelStore.from_store(store, voxels[0], keep=voxels[1])
@@ -189,6 +224,9 @@ def main(argv=None):
     if flags.out:
         found.save(flags.out)
         print("wrote %d files to %s" % (len(found), flags.out))
+    if labels is not None:
+        write_labels(found, raw, labels, flags.out)
+        print("wrote %d label files to %s" % (len(found), flags.out))
     return found
 
 
