@@ -20,7 +20,10 @@ With --voxel every scan is first downsampled on the device to one point per occu
 (votenet/scan_voxels.py: VoxelStore), before --tile where both are given; without it nothing changes.
 With --labels --out also gets <name>_labels.npz per scan (votenet/point_labels.py: label_points, PointLabels.save): for every
 point of the scan AS LOADED, before --voxel and --tile, the row of <name>.npz that owns it or -1, that row's class, and
-the points per row; --labels-prefer and --labels-min-score are label_points' arguments; without it nothing changes."""
+the points per row; --labels-prefer and --labels-min-score are label_points' arguments; without it nothing changes.
+With --labels --truth DIR the labels are then scored against the ground-truth instances of a prepared ScanNet folder
+(DIR/<name>_ins_label.npy, DIR/<name>_sem_label.npy, row for row with the scan as loaded; votenet/mask_eval.py:
+MaskAPCalculator) and the mask AP metrics are printed per --mask-iou threshold; without it nothing changes."""
 import argparse
 import importlib
 import os
@@ -72,6 +75,44 @@ def parser():
     ap.add_argument('--labels-min-score', dest='labels_min_score', type=float, default=None, metavar='X',
                     help='with --labels: boxes scored below X own nothing [0]')
     return ap
+
+
+def mask_flags(ap):
+    """The mask scoring's flags, a group of their own that main() adds to parser()'s."""
+    ap.add_argument('--truth', default=None, metavar='DIR',
+                    help='with --labels: score the masks against DIR/<name>_ins_label.npy and _sem_label.npy')
+    ap.add_argument('--mask-iou', dest='mask_iou', type=float, nargs='+', default=None, metavar='T',
+                    help='with --truth: the mask IoU thresholds [0.25 0.5]')
+    ap.add_argument('--mask-min-points', dest='mask_min_points', type=int, default=None, metavar='N',
+                    help='with --truth: masks and ground-truth instances of fewer points do not count [1]')
+    return ap
+
+
+def mask_scoring(flags):
+    """None without --truth (the plain path), else (directory, thresholds, least points)."""
+    if flags.truth is None:
+        if flags.mask_iou is not None or flags.mask_min_points is not None:
+            raise SystemExit("--mask-iou and --mask-min-points go with --truth")
+        return None
+    if not flags.labels:
+        raise SystemExit("--truth goes with --labels")
+    least = 1 if flags.mask_min_points is None else flags.mask_min_points
+    if least < 1:
+        raise SystemExit("--mask-min-points N: 1 <= N, got %r" % (least,))
+    return flags.truth, tuple(flags.mask_iou or (0.25, 0.5)), least
+
+
+def score_masks(found, result, masks, device):
+    """MaskAPCalculator over the labels just made: prints and returns the metrics per threshold."""
+    ME = importlib.import_module("3dioumatch_amd.votenet.mask_eval")
+    truth = ME.PointTruth.from_scannet(masks[0], found.names, device)
+    meter = ME.MaskAPCalculator(masks[1])
+    meter.step(result, found, truth, min_points=masks[2], min_truth_points=masks[2])
+    metrics = meter.compute_metrics()
+    for thr, values in zip(masks[1], metrics):
+        print("mask IoU %g: %s" % (thr, {k: float(v) for k, v in values.items()}))
+    print("mean mask IoU of the matched detections: %g" % meter.mean_iou())
+    return metrics
 
 
 def labeling(flags):
@@ -168,11 +209,12 @@ def cloud_files(inputs):
 
 
 def main(argv=None):
-    flags = parser().parse_args(argv)
+    flags = mask_flags(parser()).parse_args(argv)
     tiles = tiling(flags)
     seam = seam_flags(flags)
     voxels = voxeling(flags)
     labels = labeling(flags)
+    masks = mask_scoring(flags)
     if not flags.synthetic and not flags.inputs:
         raise SystemExit("cloud files or a directory (or --synthetic N)")
     if not flags.synthetic and flags.checkpoint is None:
@@ -225,8 +267,10 @@ def main(argv=None):
         found.save(flags.out)
         print("wrote %d files to %s" % (len(found), flags.out))
     if labels is not None:
-        write_labels(found, raw, labels, flags.out)
+        result = write_labels(found, raw, labels, flags.out)
         print("wrote %d label files to %s" % (len(found), flags.out))
+        if masks is not None:
+            score_masks(found, result, masks, dev)
     return found
 
 
