@@ -4,24 +4,42 @@ There is NO CPU fallback: if the shared library is missing this module raises Im
 and every device entry point raises RuntimeError for non-GPU tensors.
 """
 import ctypes
+import importlib.util
 import os
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _load_records():
+    """records.py beside this file, ONE module per process under its full name.  The drop-in modules
+    load this file by path, and with dropin/ alone on sys.path the package cannot be imported: records.py
+    is then loaded by path too, so that every copy of this file, and the package later, binds one class."""
+    name = "3dioumatch_amd.records"
+    try:
+        return importlib.import_module(name)
+    except ModuleNotFoundError:
+        spec = importlib.util.spec_from_file_location(name, os.path.join(_HERE, "records.py"))
+        mod = sys.modules[name] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+
+
+records = _load_records()
+MlpOperand = records.MlpOperand  # (pointnet2._mlp_ext and the tests take it from here)
 LIB_PATH = os.path.join(_HERE, "lib3dioumatch_hip%s.so" % os.environ.get("PN2_LIB_SUFFIX", ""))  # (build.py)
 
 _c_int, _c_float, _vp, _sz = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
 
-class MlpOperand(ctypes.Structure):  # field order == include/mlp_hip.h
-    _fields_ = [("mode", _c_int), ("x", _vp), ("dz", _vp), ("scale", _vp), ("shift", _vp), ("mean", _vp),
-                ("invstd", _vp), ("coef", _vp), ("argmax", _vp), ("ns", _c_int), ("groups", _c_int),
-                ("lin_w", _vp)]
+def _rec(name):
+    """`const <name> *`: a typed pointer to the record of records.py, so that anything but that record
+    (or None) in its place -- another record, a raw address, an argument list in another order -- is a
+    ctypes.ArgumentError before the call instead of an address the library reads"""
+    return ctypes.POINTER(getattr(records, name))
 
 
-# an operand of the shared-MLP GEMMs: a typed pointer, so that anything but a record (or None) in its
-# place -- an argument list in another order, an old positional call -- is a ctypes.ArgumentError
-# before the call instead of an address the library reads
-_op = ctypes.POINTER(MlpOperand)
+_op = _rec("MlpOperand")  # an operand of the shared-MLP GEMMs
 
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 _SIGNATURES = {
@@ -148,20 +166,20 @@ _SIGNATURES = {
     "lhs_box_point_count": [_c_int] * 4 + [_vp] * 6,
     "votenet_decode_scores": [_c_int] * 5 + [_vp] * 13,
     "votenet_decode_scores_grad": [_c_int] * 5 + [_vp] * 13,
-    "lhs_pseudo_select": [_vp, _vp],
-    "lhs_pseudo_finish": [_vp, _vp],
-    "lhs_pseudo_stats": [_vp, _vp],
+    "lhs_pseudo_select": [_rec("LhsPseudoArgs"), _vp],
+    "lhs_pseudo_finish": [_rec("LhsPseudoArgs"), _vp],
+    "lhs_pseudo_stats": [_rec("LhsStatsArgs"), _vp],
     "lhs_pseudo_stats_workspace_bytes": [_c_int, _c_int],
     "lhs_nms_samecls": [_c_int, _c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _c_int, _vp, _vp],
     "iou3d_boxes_overlap_bev": [_c_int, _vp, _c_int, _vp, _vp, _vp],
     "iou3d_boxes_iou_bev": [_c_int, _vp, _c_int, _vp, _vp, _vp],
     "iou3d_boxes_iou3d": [_c_int, _vp, _c_int, _vp, _vp, _vp],
     "iou3d_scene_best_iou3d": [_c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp],
-    "votenet_loss_decode": [_vp, _vp],
-    "votenet_loss_forward_backward": [_vp, _vp],
-    "votenet_loss_scratch_floats": [_vp],
-    "votenet_eval_loss_decode": [_vp, _vp],
-    "votenet_eval_loss": [_vp, _vp, _vp, _vp],
+    "votenet_loss_decode": [_rec("VnLossArgs"), _vp],
+    "votenet_loss_forward_backward": [_rec("VnLossArgs"), _vp],
+    "votenet_loss_scratch_floats": [_rec("VnLossArgs")],
+    "votenet_eval_loss_decode": [_rec("VnLossArgs"), _vp],
+    "votenet_eval_loss": [_rec("VnLossArgs"), _vp, _vp, _vp],
     "votenet_bbox_jitter": [_c_int, _c_int, _c_int, _c_int] + [_vp] * 15,
     "votenet_gridconv_points": [_c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "votenet_iou_opt_box_step": [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _vp,
@@ -182,8 +200,8 @@ _SIGNATURES = {
     "votenet_train_meter_add": [_c_int, _vp, _vp, _vp, _vp],
     "iou3d_corners_iou3d": [_c_int, _vp, _c_int, _vp, _vp, _vp],
     "iou3d_corners_best_match": [_c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "iou3d_eval_match": [_vp, _vp],
-    "iou3d_eval_mark": [_vp, _vp],
+    "iou3d_eval_match": [_rec("EvalMatchArgs"), _vp],
+    "iou3d_eval_mark": [_rec("EvalMarkArgs"), _vp],
     "iou3d_nms_mask": [_vp, _vp, _c_int, _c_float, _vp],
     "iou3d_nms_normal_mask": [_vp, _vp, _c_int, _c_float, _vp],
     "iou3d_nms": [_vp, _c_int, _c_float, _c_int, _vp, _vp, _vp, _vp],
@@ -197,38 +215,38 @@ EXPORTS = tuple(_SIGNATURES)
 # loaders' entry points, bound with the rest but outside EXPORTS, which is the drop-in surface of the
 # reference's kernels
 _LOADER_SIGNATURES = {
-    "scene_batch_build": [_vp, _vp],
-    "scene_sunrgbd_batch_build": [_vp, _vp],
+    "scene_batch_build": [_rec("SceneBatchArgs"), _vp],
+    "scene_sunrgbd_batch_build": [_rec("SunBatchArgs"), _vp],
     "scene_sunrgbd_votes": [_vp, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp, _vp],
     # the label-free scan path (include/scan_hip.h)
-    "scene_scan_prepare": [_vp, _vp],
-    "scene_scan_batch_build": [_vp, _vp],
-    "scene_scan_semi_build": [_vp, _vp],
-    "scene_detections_pack": [_vp, _vp],
+    "scene_scan_prepare": [_rec("ScanPrepareArgs"), _vp],
+    "scene_scan_batch_build": [_rec("ScanBatchArgs"), _vp],
+    "scene_scan_semi_build": [_rec("ScanSemiArgs"), _vp],
+    "scene_detections_pack": [_rec("ScanPackArgs"), _vp],
     # scans larger than a room: device tiling and merged detections (include/scan_tile_hip.h)
-    "scene_scan_bounds": [_vp, _vp],
-    "scene_scan_tile_count": [_vp, _vp],
-    "scene_scan_tile_gather": [_vp, _vp],
-    "scene_detections_merge": [_vp, _vp],
-    "scene_detections_merge_nms": [_vp, _vp],
+    "scene_scan_bounds": [_rec("ScanBoundsArgs"), _vp],
+    "scene_scan_tile_count": [_rec("ScanTileCountArgs"), _vp],
+    "scene_scan_tile_gather": [_rec("ScanTileGatherArgs"), _vp],
+    "scene_detections_merge": [_rec("ScanMergeArgs"), _vp],
+    "scene_detections_merge_nms": [_rec("ScanSeamArgs"), _vp],
     "scene_detections_merge_nms_scratch_bytes": [_c_int, _c_int, _c_int, _c_int],
     # voxel-grid downsample of scan stores (include/scan_voxel_hip.h)
     "scene_scan_voxel_slots": [_c_int],
-    "scene_scan_voxel_mark": [_vp, _vp],
-    "scene_scan_voxel_count": [_vp, _vp],
-    "scene_scan_voxel_gather": [_vp, _vp],
+    "scene_scan_voxel_mark": [_rec("ScanVoxelArgs"), _vp],
+    "scene_scan_voxel_count": [_rec("ScanVoxelCountArgs"), _vp],
+    "scene_scan_voxel_gather": [_rec("ScanVoxelGatherArgs"), _vp],
     # per-point instance labels from packed detections (include/point_labels_hip.h)
     "scene_points_label_scratch_bytes": [_c_int, _c_int],
-    "scene_detections_frames": [_vp, _vp],
-    "scene_points_label": [_vp, _vp],
+    "scene_detections_frames": [_rec("DetectionsFramesArgs"), _vp],
+    "scene_points_label": [_rec("PointsLabelArgs"), _vp],
     # mask matching of point labels against ground-truth instances (include/mask_eval_hip.h)
     "scene_mask_scratch_bytes": [_c_int, _c_int, _c_int],
-    "scene_mask_overlap": [_vp, _vp],
-    "scene_mask_match": [_vp, _vp],
+    "scene_mask_overlap": [_rec("MaskOverlapArgs"), _vp],
+    "scene_mask_match": [_rec("MaskMatchArgs"), _vp],
     # raw ScanNet scans -> the preprocessed layout (include/scannet_raw_hip.h)
-    "scannet_raw_export": [_vp, _vp],
+    "scannet_raw_export": [_rec("ScanNetRawArgs"), _vp],
     # raw SUN RGB-D depth clouds -> kept rows, floors, store rows (include/sunrgbd_raw_hip.h)
-    "scene_sunrgbd_raw_export": [_vp, _vp],
+    "scene_sunrgbd_raw_export": [_rec("SunRgbdRawArgs"), _vp],
 }
 
 
@@ -264,3 +282,12 @@ def check(code, what):
 def current_stream_ptr(device):
     import torch
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def run(entry, record, device, *more, stream=None):
+    """Call the record entry point `entry(&record, *more, stream)` with `device` current, on the raw
+    `stream` (None: the device's current stream): the one place that launches with a record."""
+    import torch
+    with torch.cuda.device(device):
+        check(getattr(lib, entry)(ctypes.byref(record), *more,
+                                  current_stream_ptr(device) if stream is None else stream), entry)

@@ -29,25 +29,16 @@ second arena, one set of boxes per parent scan (see the section at the end; `hos
 With seam_nms=True that merge is an NMS across the cuts, one box per object that two tiles see
 (scene_detections_merge_nms, four launches; the last section; `host_merge_nms` restates it).
 """
-import ctypes
-import importlib
 import os
 
 import numpy as np
 import torch
 
+from .. import records
 from .scan_data import ScanLoader, ScanStore
 
 MAX_K = 1024  # SCAN_MAX_K
 PLANES = ("count", "proposal", "cls", "score", "box", "corners")
-
-_c_int, _vp = ctypes.c_int, ctypes.c_void_p
-
-
-class _PackArgs(ctypes.Structure):  # field order == include/scan_hip.h ScanPackArgs
-    _fields_ = ([(n, _c_int) for n in ("B", "K", "NC", "scene0")] +
-                [(n, _vp) for n in ("keep", "obj_prob", "cls", "score", "center", "size", "heading", "corners",
-                                    "count", "proposal", "cls_out", "score_out", "box", "corners_out")])
 
 
 def arena_layout(S, K, NC):
@@ -117,7 +108,7 @@ def pack_end_points(arena, S, scene0, end_points, config_dict):
 
 def pack_gpu(arena, S, scene0, keep, obj_prob, cls, score, center, size64, heading64, corners):
     """Launch scene_detections_pack for one batch into rows [scene0, scene0 + B) of `arena`."""
-    _L = importlib.import_module("3dioumatch_amd._lib")
+    from .. import _lib
     B, K = keep.shape
     NC = score.shape[2] if score.dim() == 3 else 0
     if K > MAX_K:
@@ -131,7 +122,7 @@ def pack_gpu(arena, S, scene0, keep, obj_prob, cls, score, center, size64, headi
            "cls": (cls, torch.int64, (B, K)), "score": (score, torch.float32, (B, K, NC) if NC else (B, K)),
            "center": (center, torch.float32, (B, K, 3)), "size": (size64, torch.float64, (B, K, 3)),
            "heading": (heading64, torch.float64, (B, K)), "corners": (corners, torch.float32, (B, K, 8, 3))}
-    a = _PackArgs()
+    a = records.ScanPackArgs()
     a.B, a.K, a.NC, a.scene0 = B, K, NC, scene0
     held = []
     for name, (t, dtype, shape) in ins.items():
@@ -143,9 +134,7 @@ def pack_gpu(arena, S, scene0, keep, obj_prob, cls, score, center, size64, headi
     base = arena.data_ptr()
     for plane, field in zip(PLANES, ("count", "proposal", "cls_out", "score_out", "box", "corners_out")):
         setattr(a, field, base + 4 * layout[plane][0])
-    with torch.cuda.device(arena.device):
-        _L.check(_L.lib.scene_detections_pack(ctypes.byref(a), _L.current_stream_ptr(arena.device)),
-                 "scene_detections_pack")
+    _lib.run("scene_detections_pack", a, arena.device)
     return arena
 
 
@@ -262,13 +251,6 @@ def detect(engine, store_or_loader, config_dict, batch_size=8, opt_step=0, opt_r
 MERGED_PLANES = ("count", "tile", "proposal", "cls", "score", "box", "corners")
 
 
-class _MergeArgs(ctypes.Structure):  # field order == include/scan_tile_hip.h ScanMergeArgs
-    _fields_ = ([(n, _c_int) for n in ("S", "K", "NC", "cap", "max_tiles")] +
-                [(n, _vp) for n in ("first", "tiles", "core", "count_in", "proposal_in", "cls_in", "score_in",
-                                    "box_in", "corners_in", "count", "tile", "proposal", "cls", "score", "box",
-                                    "corners")])
-
-
 def merged_layout(S, cap, NC):
     """arena_layout for the merged arena: {plane: (first word, shape)} and its size in words."""
     shapes = {"count": (S,), "tile": (S, cap), "proposal": (S, cap), "cls": (S, cap),
@@ -316,7 +298,7 @@ def new_merged_arena(S, cap, NC, device):
 def merge_gpu(merged, tile_arena, first, tiles, core, S, T, K, NC, cap, max_tiles):
     """Launch scene_detections_merge: the tile arena (T tiles, K rows each) -> `merged` (S scans, cap
     rows each); first, tiles (S,) int32 and core (T, 4) float32 on the arenas' device."""
-    _L = importlib.import_module("3dioumatch_amd._lib")
+    from .. import _lib
     if K > MAX_K:
         raise ValueError("scene_detections_merge: K = %d rows per tile, at most %d" % (K, MAX_K))
     if cap < max_tiles * K:
@@ -332,16 +314,14 @@ def merge_gpu(merged, tile_arena, first, tiles, core, S, T, K, NC, cap, max_tile
                                   ("core", core, torch.float32, (T, 4))):
         if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != merged.device:
             raise ValueError("scene_detections_merge: %s must be %s %s on %s" % (name, dtype, shape, merged.device))
-    a = _MergeArgs()
+    a = records.ScanMergeArgs()
     a.S, a.K, a.NC, a.cap, a.max_tiles = S, K, NC, cap, max_tiles
     a.first, a.tiles, a.core = first.data_ptr(), tiles.data_ptr(), core.data_ptr()
     for plane in PLANES:
         setattr(a, plane + "_in", tile_arena.data_ptr() + 4 * lin[plane][0])
     for plane in MERGED_PLANES:
         setattr(a, plane, merged.data_ptr() + 4 * lout[plane][0])
-    with torch.cuda.device(merged.device):
-        _L.check(_L.lib.scene_detections_merge(ctypes.byref(a), _L.current_stream_ptr(merged.device)),
-                 "scene_detections_merge")
+    _lib.run("scene_detections_merge", a, merged.device)
     return merged
 
 
@@ -469,12 +449,6 @@ def seam_settings(config_dict, seam):
             "same_class": int(bool(config_dict['cls_nms']) and dims == 3), "dims": dims}
 
 
-class _SeamArgs(ctypes.Structure):  # field order == include/scan_tile_hip.h ScanSeamArgs
-    _fields_ = (list(_MergeArgs._fields_) + [(n, _vp) for n in ("iy", "ix", "reach")] +
-                [("thresh", ctypes.c_double)] + [(n, _c_int) for n in ("old_type", "same_class", "dims")] +
-                [("scratch", _vp), ("scratch_bytes", ctypes.c_size_t)])
-
-
 def seam_reach(core, seam):
     """(T, 4) float32 rlo_x, rhi_x, rlo_y, rhi_y: clo - seam, chi + seam in float64 from the float32
     core, rounded once to float32; an infinite side stays infinite.  0 <= seam < inf."""
@@ -570,8 +544,8 @@ def host_merge_nms(planes, first, tiles, core, iy, ix, reach, thresh, old_type, 
 
 def seam_scratch_bytes(S, T, K, max_tiles):
     """scene_detections_merge_nms_scratch_bytes"""
-    _L = importlib.import_module("3dioumatch_amd._lib")
-    return int(_L.lib.scene_detections_merge_nms_scratch_bytes(S, T, K, max_tiles))
+    from .. import _lib
+    return int(_lib.lib.scene_detections_merge_nms_scratch_bytes(S, T, K, max_tiles))
 
 
 def merge_nms_gpu(merged, tile_arena, first, tiles, core, iy, ix, reach, S, T, K, NC, cap, max_tiles, thresh,
@@ -580,7 +554,7 @@ def merge_nms_gpu(merged, tile_arena, first, tiles, core, iy, ix, reach, S, T, K
     float32 on the arenas' device and the four settings (seam_settings); `scratch`: a float64
     tensor of at least seam_scratch_bytes(S, T, K, max_tiles) bytes, allocated here when None
     (uninitialised: the launches write every word they read)."""
-    _L = importlib.import_module("3dioumatch_amd._lib")
+    from .. import _lib
     who = "scene_detections_merge_nms"
     if K > MAX_K:
         raise ValueError("%s: K = %d rows per tile, at most %d" % (who, K, MAX_K))
@@ -605,7 +579,7 @@ def merge_nms_gpu(merged, tile_arena, first, tiles, core, iy, ix, reach, S, T, K
     if scratch.dtype != torch.float64 or not scratch.is_contiguous() or scratch.device != merged.device or \
             scratch.numel() * 8 < need:
         raise ValueError("%s: the scratch must be float64, contiguous, %d bytes on %s" % (who, need, merged.device))
-    a = _SeamArgs()
+    a = records.ScanSeamArgs()
     a.S, a.K, a.NC, a.cap, a.max_tiles = S, K, NC, cap, max_tiles
     a.first, a.tiles, a.core = first.data_ptr(), tiles.data_ptr(), core.data_ptr()
     a.iy, a.ix, a.reach = iy.data_ptr(), ix.data_ptr(), reach.data_ptr()
@@ -615,6 +589,5 @@ def merge_nms_gpu(merged, tile_arena, first, tiles, core, iy, ix, reach, S, T, K
         setattr(a, plane + "_in", tile_arena.data_ptr() + 4 * lin[plane][0])
     for plane in MERGED_PLANES:
         setattr(a, plane, merged.data_ptr() + 4 * lout[plane][0])
-    with torch.cuda.device(merged.device):
-        _L.check(_L.lib.scene_detections_merge_nms(ctypes.byref(a), _L.current_stream_ptr(merged.device)), who)
+    _lib.run(who, a, merged.device)
     return merged

@@ -18,11 +18,12 @@ eval_match_gpu / eval_mark_gpu bind the two kernels of the device-resident form 
 (eval_helper.DeviceAPCalculator): the same matching on a batch's dense (scene, proposal, class) slots
 with every pair's IoU computed once, and the marking of all classes and thresholds in one launch.
 """
-import ctypes
 import importlib
 
 import numpy as np
 import torch
+
+from ..records import EvalMarkArgs, EvalMatchArgs
 
 
 def corners_iou3d_gpu(a, b):
@@ -60,19 +61,7 @@ def corners_best_match_gpu(det, gt_begin, gt_count, gt):
     return ovmax, jmax
 
 
-_vp, _ll = ctypes.c_void_p, ctypes.c_longlong
 EVAL_MAX_CLASS = 64  # include/iou3d_hip.h IOU3D_EVAL_MAX_CLASS
-
-
-class EvalMatchArgs(ctypes.Structure):  # field order == include/iou3d_hip.h
-    _fields_ = ([(n, ctypes.c_int) for n in ("B", "K", "G", "C")] +
-                [(n, _vp) for n in ("det", "keep", "det_cls", "gt", "gt_valid", "gt_cls", "ovmax", "jmax")])
-
-
-class EvalMarkArgs(ctypes.Structure):  # field order == include/iou3d_hip.h
-    _fields_ = ([("n", _ll), ("num_class", ctypes.c_int), ("num_thresh", ctypes.c_int), ("num_gt", _ll)] +
-                [(n, _vp) for n in ("seg", "ovmax", "gt_id", "npos", "thresh", "first", "cum_tp", "rec",
-                                    "prec", "ap", "last_rec")])
 
 
 def _device_inputs(what, tensors):
@@ -91,7 +80,7 @@ def eval_match_gpu(det, keep, det_cls, gt, gt_valid, gt_cls, num_class):
     gt_cls (B,G) i64, all on the GPU; num_class = C >= 1: a slot per (proposal, class), 0: a slot per
     proposal with class det_cls -> (ovmax (B,K,max(C,1)) f64, jmax i32), include/iou3d_hip.h
     iou3d_eval_match: eval_det_cls' loop over the scene's ground truth of the slot's class."""
-    _L = importlib.import_module("3dioumatch_amd._lib")
+    from .. import _lib
     det, keep, det_cls, gt, gt_valid, gt_cls = _device_inputs("eval_match", [
         (det, torch.float32, "det"), (keep, torch.bool, "keep"), (det_cls, torch.int64, "det_cls"),
         (gt, torch.float32, "gt"), (gt_valid, torch.bool, "gt_valid"), (gt_cls, torch.int64, "gt_cls")])
@@ -108,8 +97,7 @@ def eval_match_gpu(det, keep, det_cls, gt, gt_valid, gt_cls, num_class):
     for name, t in (("det", det), ("keep", keep), ("det_cls", det_cls), ("gt", gt), ("gt_valid", gt_valid),
                     ("gt_cls", gt_cls), ("ovmax", ovmax), ("jmax", jmax)):
         setattr(a, name, t.data_ptr())
-    with torch.cuda.device(det.device):
-        _L.check(_L.lib.iou3d_eval_match(ctypes.byref(a), _L.current_stream_ptr(det.device)), "iou3d_eval_match")
+    _lib.run("iou3d_eval_match", a, det.device)
     return ovmax, jmax
 
 
@@ -118,7 +106,7 @@ def eval_mark_gpu(seg, ovmax, gt_id, npos, thresholds, num_gt, curves=False):
     ovmax (n) f64, gt_id (n) i32, npos (num_class) i64, thresholds (T) f64, all on the GPU; num_gt:
     ground-truth ids are below it -> (ap (T,num_class) f64, last_rec (T,num_class) f64, rec, prec
     (T,n) f64 or None without `curves`), include/iou3d_hip.h iou3d_eval_mark."""
-    _L = importlib.import_module("3dioumatch_amd._lib")
+    from .. import _lib
     seg, ovmax, gt_id, npos, thresholds = _device_inputs("eval_mark", [
         (seg, torch.int64, "seg"), (ovmax, torch.float64, "ovmax"), (gt_id, torch.int32, "gt_id"),
         (npos, torch.int64, "npos"), (thresholds, torch.float64, "thresholds")])
@@ -138,8 +126,7 @@ def eval_mark_gpu(seg, ovmax, gt_id, npos, thresholds, num_gt, curves=False):
                     ("first", first), ("cum_tp", cum_tp), ("rec", rec), ("prec", prec), ("ap", ap),
                     ("last_rec", last_rec)):
         setattr(a, name, t.data_ptr() if t is not None else None)
-    with torch.cuda.device(dev):
-        _L.check(_L.lib.iou3d_eval_mark(ctypes.byref(a), _L.current_stream_ptr(dev)), "iou3d_eval_mark")
+    _lib.run("iou3d_eval_mark", a, dev)
     return ap, last_rec, rec, prec
 
 

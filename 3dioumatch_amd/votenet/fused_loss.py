@@ -25,12 +25,7 @@ import os
 
 import torch
 
-_c_int, _ll, _vp = ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p
-
-
-class VnLossTensor(ctypes.Structure):
-    _fields_ = [("p", _vp), ("sb", _ll), ("sk", _ll), ("sc", _ll), ("sd", _ll)]
-
+from ..records import VnLossArgs, VnLossTensor
 
 _PRED = ("agg_xyz", "obj", "center", "h_scores", "h_resn", "s_scores", "s_resn", "sem", "iou",
          "iou_jit", "seed_xyz", "vote_xyz", "jit_center", "jit_size", "jit_heading")
@@ -53,20 +48,6 @@ _HEADS = (
 _FIELDS = tuple(row[0] for row in _HEADS)
 _GRADS = tuple(row[1] for row in _HEADS)
 _CONSISTENCY_GRADS = _GRADS[1:7]  # (g_obj is written too, as zeros: objectness is a statistic there)
-
-
-class VnLossArgs(ctypes.Structure):  # field order == include/loss_hip.h
-    _fields_ = ([(n, _c_int) for n in ("B", "K", "G", "S", "VF", "N", "NH", "NS", "NC", "NI",
-                                       "has_jitter", "consistency")] + [("grad_scale", ctypes.c_float)] +
-                [(n, _vp) for n in ("center_label", "box_label_mask", "heading_class_label",
-                                    "heading_residual_label", "size_class_label",
-                                    "size_residual_label", "sem_cls_label", "vote_label",
-                                    "vote_label_mask", "seed_inds")] +
-                [("seed_inds_stride", _ll), ("mean_size", _vp)] +
-                [(n, VnLossTensor) for n in _PRED] +
-                [(n, _vp) for n in ("boxes", "gt_boxes", "iou_lab", "iou_assign", "stats",
-                                    "objectness_label", "objectness_mask", "object_assignment")] +
-                [(n, _vp) for n in _GRADS] + [("gt_nearest", _vp), ("partials", _vp)])
 
 
 (ST_LOSS, ST_VOTE, ST_OBJ, ST_CENTER, ST_HCLS, ST_HREG, ST_SCLS, ST_SREG, ST_SEM, ST_BOX, ST_IOU,
@@ -104,9 +85,8 @@ def _launch(name, args, device):
         rc = getattr(_HOST_BUILD, name.replace("votenet_loss", "host_loss"))(ctypes.byref(args))
         assert rc == 0
         return
-    _L = importlib.import_module("3dioumatch_amd._lib")
-    with torch.cuda.device(device):
-        _L.check(getattr(_L.lib, name)(ctypes.byref(args), _L.current_stream_ptr(device)), name)
+    from .. import _lib
+    _lib.run(name, args, device)
 
 
 def _scratch_floats(args, device):
@@ -114,8 +94,8 @@ def _scratch_floats(args, device):
         if _HOST_BUILD is None:
             raise RuntimeError("the fused loss runs on the GPU only (no CPU path)")
         return int(_HOST_BUILD.host_loss_scratch_floats(ctypes.byref(args)))
-    _L = importlib.import_module("3dioumatch_amd._lib")
-    return int(_L.lib.votenet_loss_scratch_floats(ctypes.byref(args)))
+    from .. import _lib
+    return int(_lib.lib.votenet_loss_scratch_floats(ctypes.byref(args)))
 
 
 def _scene_iou(boxes, gt_boxes):
@@ -482,9 +462,8 @@ def _launch_eval(name, a, device, *more):
         rc = getattr(_EVAL_HOST_BUILD, name.replace("votenet_", "host_"))(ctypes.byref(a), *more)
         assert rc == 0
         return
-    _L = importlib.import_module("3dioumatch_amd._lib")
-    with torch.cuda.device(device):
-        _L.check(getattr(_L.lib, name)(ctypes.byref(a), *more, _L.current_stream_ptr(device)), name)
+    from .. import _lib
+    _lib.run(name, a, device, *more)
 
 
 def _eval_pass(src, config, heads, size_residuals, accum=None):

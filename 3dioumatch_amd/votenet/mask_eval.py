@@ -45,13 +45,12 @@ size, class and intersection tables, equal keys of a wave merged first where MER
 scene_mask_match (one wave per row).  Nothing in match_masks or MaskAPCalculator.step copies to the host
 or synchronises.
 """
-import ctypes
-import importlib
 import os
 
 import numpy as np
 import torch
 
+from .. import records
 from . import point_labels as PL
 from .detect import Detections
 from .eval_det import EVAL_MAX_CLASS, _mark
@@ -63,21 +62,6 @@ MASK_MERGE_ROUNDS = 4  # include/mask_eval_hip.h
 MAX_ENTRIES = 1 << 31  # words of the three tables
 MERGE = True           # the overlap form match_masks launches: measured in profiles/mask_eval.json
 NOT_A_DETECTION = EVAL_MAX_CLASS + 1
-
-_c_int, _vp = ctypes.c_int, ctypes.c_void_p
-
-
-class _OverlapArgs(ctypes.Structure):  # field order == include/mask_eval_hip.h MaskOverlapArgs
-    _fields_ = ([(n, _c_int) for n in ("S", "cap", "G", "max_blocks", "merge", "clear")] +
-                [(n, _vp) for n in ("offset", "count", "instance", "truth_instance", "truth_class", "scratch")] +
-                [("scratch_bytes", ctypes.c_size_t)])
-
-
-class _MatchArgs(ctypes.Structure):  # field order == include/mask_eval_hip.h MaskMatchArgs
-    _fields_ = ([(n, _c_int) for n in ("S", "cap", "G", "NC", "NS", "min_points", "min_truth_points")] +
-                [(n, _vp) for n in ("rows", "cls", "score", "points", "scratch")] +
-                [("scratch_bytes", ctypes.c_size_t)] +
-                [(n, _vp) for n in ("ovmax", "jmax", "row_score", "key", "klass", "npos")])
 
 
 def table_entries(S, cap, G):
@@ -229,8 +213,8 @@ def host_match_masks(instance, points, planes, truth, num_class, min_points=1, m
 # ---------------------------------------------------------------------------------- the launches
 def mask_scratch_bytes(S, cap, G):
     """scene_mask_scratch_bytes"""
-    _L = importlib.import_module("3dioumatch_amd._lib")
-    return int(_L.lib.scene_mask_scratch_bytes(S, cap, G))
+    from .. import _lib
+    return int(_lib.lib.scene_mask_scratch_bytes(S, cap, G))
 
 
 def scratch_views(scratch, S, cap, G):
@@ -240,7 +224,7 @@ def scratch_views(scratch, S, cap, G):
 
 
 def overlap_record(offset, count, max_blocks, instance, truth_instance, truth_class, scratch, S, cap, G, merge, clear):
-    a = _OverlapArgs()
+    a = records.MaskOverlapArgs()
     a.S, a.cap, a.G, a.max_blocks, a.merge, a.clear = S, cap, G, max_blocks, int(bool(merge)), int(bool(clear))
     a.offset, a.count, a.instance = offset.data_ptr(), count.data_ptr(), instance.data_ptr()
     a.truth_instance, a.truth_class, a.scratch = truth_instance.data_ptr(), truth_class.data_ptr(), scratch.data_ptr()
@@ -252,16 +236,17 @@ def overlap_gpu(offset, count, max_blocks, instance, truth_instance, truth_class
                 scratch=None):
     """Launch scene_mask_overlap over flat (P,) int32 device arrays -> the scratch, an int32 tensor of
     table_entries(S, cap, G) words (it may be given, holding anything while `clear` is on)."""
+    from .. import _lib
     if scratch is None:
         scratch = torch.empty(table_entries(S, cap, G), dtype=torch.int32, device=instance.device)
-    PL._run("scene_mask_overlap", overlap_record(offset, count, max_blocks, instance, truth_instance, truth_class,
-                                                 scratch, S, cap, G, merge, clear), instance.device)
+    _lib.run("scene_mask_overlap", overlap_record(offset, count, max_blocks, instance, truth_instance, truth_class,
+                                                  scratch, S, cap, G, merge, clear), instance.device)
     return scratch
 
 
 def match_record(rows, cls, score, points, scratch, G, NC, min_points, min_truth_points, out):
     S, cap = points.shape
-    a = _MatchArgs()
+    a = records.MaskMatchArgs()
     a.S, a.cap, a.G, a.NC, a.NS = S, cap, G, NC, score.shape[2] if score.dim() == 3 else 0
     a.min_points, a.min_truth_points = min_points, min_truth_points
     a.rows, a.cls, a.score, a.points = rows.data_ptr(), cls.data_ptr(), score.data_ptr(), points.data_ptr()
@@ -277,6 +262,7 @@ MATCH_OUTPUTS = (("ovmax", torch.float64), ("jmax", torch.int32), ("score", torc
 def match_gpu(rows, cls, score, points, scratch, G, NC, min_points=1, min_truth_points=1, out=None):
     """Launch scene_mask_match with an overlap scratch -> {ovmax, jmax, score, key (S, cap), klass (S, G),
     npos (65,) int64}.  Any of them may be given in `out` holding anything, except npos, which is ADDED to."""
+    from .. import _lib
     S, cap = points.shape
     out = dict(out or {})
     for name, dtype in MATCH_OUTPUTS:
@@ -286,8 +272,8 @@ def match_gpu(rows, cls, score, points, scratch, G, NC, min_points=1, min_truth_
         out["klass"] = torch.empty((S, G), dtype=torch.int32, device=points.device)
     if "npos" not in out:
         out["npos"] = torch.zeros(EVAL_MAX_CLASS + 1, dtype=torch.int64, device=points.device)
-    PL._run("scene_mask_match", match_record(rows, cls, score, points, scratch, G, NC, min_points, min_truth_points,
-                                             out), points.device)
+    _lib.run("scene_mask_match", match_record(rows, cls, score, points, scratch, G, NC, min_points, min_truth_points,
+                                              out), points.device)
     return out
 
 

@@ -36,13 +36,12 @@ csrc/point_labels.hip).  Nothing in label_points copies to the host or synchroni
 the result makes ONE copy.  `host_label_points` restates the rule in numpy and is the path of a
 `device=None` store or of an arena on another device.
 """
-import ctypes
-import importlib
 import os
 
 import numpy as np
 import torch
 
+from .. import records
 from .detect import MAX_K, Detections
 from .scan_data import ScanStore
 
@@ -51,20 +50,6 @@ LABEL_BOX_CHUNK = 256  # include/point_labels_hip.h
 PREFER = ("score", "smallest")
 CULL = True            # label_points' default: measured in profiles/label_points.json
 HOST_POINTS = 1 << 16  # points per pass of the numpy restatement
-
-_c_int, _vp = ctypes.c_int, ctypes.c_void_p
-
-
-class _FramesArgs(ctypes.Structure):  # field order == include/point_labels_hip.h DetectionsFramesArgs
-    _fields_ = ([(n, _c_int) for n in ("S", "K", "cap", "NC", "prefer")] + [("min_score", ctypes.c_double)] +
-                [(n, _vp) for n in ("count", "cls", "score", "box", "frames", "points", "scratch")] +
-                [("scratch_bytes", ctypes.c_size_t)])
-
-
-class _LabelArgs(ctypes.Structure):  # field order == include/point_labels_hip.h PointsLabelArgs
-    _fields_ = ([(n, _c_int) for n in ("S", "C", "K", "cap", "cull", "max_blocks")] +
-                [(n, _vp) for n in ("cloud", "offset", "count", "rows", "frames", "scratch")] +
-                [("scratch_bytes", ctypes.c_size_t)] + [(n, _vp) for n in ("instance", "semantic", "points")])
 
 
 def _prefer(prefer):
@@ -162,19 +147,13 @@ def host_label_points(planes, clouds, prefer="score", min_score=0.0, frames=None
 # ---------------------------------------------------------------------------------- the launches
 def label_scratch_bytes(S, cap):
     """scene_points_label_scratch_bytes"""
-    _L = importlib.import_module("3dioumatch_amd._lib")
-    return int(_L.lib.scene_points_label_scratch_bytes(S, cap))
-
-
-def _run(entry, record, device):
-    _L = importlib.import_module("3dioumatch_amd._lib")
-    with torch.cuda.device(device):
-        _L.check(getattr(_L.lib, entry)(ctypes.byref(record), _L.current_stream_ptr(device)), entry)
+    from .. import _lib
+    return int(_lib.lib.scene_points_label_scratch_bytes(S, cap))
 
 
 def frames_record(count, cls, score, box, K, prefer, min_score, frames, points, scratch):
     S, cap = cls.shape
-    a = _FramesArgs()
+    a = records.DetectionsFramesArgs()
     a.S, a.K, a.cap, a.NC, a.prefer = S, K, cap, score.shape[2] if score.dim() == 3 else 0, _prefer(prefer)
     a.min_score = _min_score(min_score)
     a.count, a.cls, a.score, a.box = count.data_ptr(), cls.data_ptr(), score.data_ptr(), box.data_ptr()
@@ -188,6 +167,7 @@ def frames_gpu(count, cls, score, box, K, prefer="score", min_score=0.0, frames=
     (S, cap) or (S, cap, NC) float32, box (S, cap, 7) float32 (views of an arena will do) ->
     (frames (S, cap, 8) float32, points (S, cap) int32 zeroed, scratch: int64 words).  The three outputs
     may be given; they may hold anything."""
+    from .. import _lib
     S, cap = cls.shape
     dev = cls.device
     if frames is None:
@@ -196,8 +176,8 @@ def frames_gpu(count, cls, score, box, K, prefer="score", min_score=0.0, frames=
         points = torch.empty((S, cap), dtype=torch.int32, device=dev)
     if scratch is None:
         scratch = torch.empty(label_scratch_bytes(S, cap) // 8, dtype=torch.int64, device=dev)
-    _run("scene_detections_frames", frames_record(count, cls, score, box, K, prefer, min_score, frames, points, scratch),
-         dev)
+    _lib.run("scene_detections_frames",
+             frames_record(count, cls, score, box, K, prefer, min_score, frames, points, scratch), dev)
     return frames, points, scratch
 
 
@@ -211,7 +191,7 @@ def scratch_views(scratch, S, cap):
 
 def label_record(cloud, offset, count, max_blocks, rows, frames, scratch, K, cull, instance, semantic, points):
     S, cap = points.shape
-    a = _LabelArgs()
+    a = records.PointsLabelArgs()
     a.S, a.C, a.K, a.cap, a.cull, a.max_blocks = S, cloud.shape[1], K, cap, int(bool(cull)), max_blocks
     a.cloud, a.offset, a.count, a.rows = cloud.data_ptr(), offset.data_ptr(), count.data_ptr(), rows.data_ptr()
     a.frames, a.scratch = frames.data_ptr(), scratch.data_ptr()
@@ -224,13 +204,14 @@ def label_gpu(cloud, offset, count, max_blocks, rows, frames, scratch, K, points
               semantic=None):
     """Launch scene_points_label over the scans of a flat (P, C) device cloud with what frames_gpu
     returned (`points` is added to) -> (instance (P,), semantic (P,)) int32; both may be given."""
+    from .. import _lib
     P = cloud.shape[0]
     if instance is None:
         instance = torch.empty(P, dtype=torch.int32, device=cloud.device)
     if semantic is None:
         semantic = torch.empty(P, dtype=torch.int32, device=cloud.device)
-    _run("scene_points_label", label_record(cloud, offset, count, max_blocks, rows, frames, scratch, K, cull, instance,
-                                            semantic, points), cloud.device)
+    _lib.run("scene_points_label", label_record(cloud, offset, count, max_blocks, rows, frames, scratch, K, cull,
+                                                instance, semantic, points), cloud.device)
     return instance, semantic
 
 

@@ -5,11 +5,11 @@ their 3-D boxes one by one in numpy and runs utils/nms.py:lhs_3d_faster_samecls
 (models/loss_helper_unlabeled.py:447-487); here the same computation is one kernel launch with no
 host round trip, so the semi-supervised step stays capturable in a HIP graph.
 """
-import importlib
-
 import torch
 
-_L = importlib.import_module("3dioumatch_amd._lib")
+from .. import _lib as _L
+from .. import records
+
 _lib = _L.lib
 
 
@@ -134,24 +134,6 @@ def box_point_count_gpu(points, center, size, heading, out=None):
     return count
 
 
-import ctypes  # noqa: E402
-
-_c_int, _c_float, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
-
-
-class LhsPseudoArgs(ctypes.Structure):  # field order == include/lhs_hip.h
-    _fields_ = ([(n, _c_int) for n in ("S", "K", "NC", "NI", "NH", "NS")] +
-                [(n, _c_float) for n in ("obj_threshold", "cls_threshold", "iou_threshold")] +
-                [("use_nms", _c_int)] +
-                [(n, _vp) for n in ("objectness", "sem_cls", "iou", "heading_scores", "heading_residuals",
-                                    "size_scores", "size_residuals", "center", "vote_xyz", "mean_size",
-                                    "flip_x", "flip_y", "rot_mat", "scale", "box_center", "box_size",
-                                    "box_heading", "box_score", "passed", "negative", "false_xyz", "picked",
-                                    "label_mask", "center_label", "false_center_label", "sem_cls_label",
-                                    "heading_label", "size_label", "heading_residual_label",
-                                    "size_residual_label", "iou_label", "pseudo_gt_ratio")])
-
-
 def pseudo_labels_supported(pred_center, scale, f32=(), i64=(), sem_cls=None, iou_scores=None):
     """The two-launch form covers GPU tensors, 64 <= K <= 1024 proposals, a per-axis scale (S,1,3),
     float32 network outputs (`f32`), int64 flip flags (`i64`) on the same device and one IoU score
@@ -190,7 +172,7 @@ def pseudo_labels_gpu(objectness, sem_cls, iou_scores, heading_scores, heading_r
         t = t.detach().contiguous()
         keep.append(t)
         return t.data_ptr()
-    a = LhsPseudoArgs()
+    a = records.LhsPseudoArgs()
     a.S, a.K = s, k
     a.NC, a.NI, a.NH, a.NS = sem_cls.shape[2], iou_scores.shape[2], heading_scores.shape[2], size_scores.shape[2]
     a.obj_threshold, a.cls_threshold, a.iou_threshold = float(obj_threshold), float(cls_threshold), float(iou_threshold)
@@ -219,29 +201,17 @@ def pseudo_labels_gpu(objectness, sem_cls, iou_scores, heading_scores, heading_r
     a.false_xyz = false_xyz.data_ptr()
     for name, t in out.items():
         setattr(a, name, t.data_ptr())
-    stream = _L.current_stream_ptr(dev)
-    with torch.cuda.device(dev):
-        _L.check(_lib.lhs_pseudo_select(ctypes.byref(a), stream), "lhs_pseudo_select")
-        picked = None
-        if nms is not None:
-            picked = torch.zeros((s, n), dtype=torch.int32, device=dev)
+    _L.run("lhs_pseudo_select", a, dev)
+    if nms is not None:
+        picked = torch.zeros((s, n), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
             _L.check(_lib.lhs_nms_samecls(s, n, box_center.data_ptr(), box_size.data_ptr(), box_heading.data_ptr(),
                                           box_score.data_ptr(), out["sem_cls_label"].data_ptr(), float(nms[0]),
-                                          1 if nms[1] else 0, picked.data_ptr(), stream), "lhs_nms_samecls")
-            a.picked = picked.data_ptr()
-        _L.check(_lib.lhs_pseudo_finish(ctypes.byref(a), stream), "lhs_pseudo_finish")
+                                          1 if nms[1] else 0, picked.data_ptr(), _L.current_stream_ptr(dev)),
+                     "lhs_nms_samecls")
+        a.picked = picked.data_ptr()
+    _L.run("lhs_pseudo_finish", a, dev)
     return out
-
-
-class LhsStatsArgs(ctypes.Structure):  # field order == include/lhs_hip.h
-    _fields_ = ([(n, _c_int) for n in ("S", "K", "NC", "NI", "NH", "NS", "labeled", "rows")] +
-                [(n, _c_float) for n in ("obj_threshold", "cls_threshold", "iou_threshold")] +
-                [(n, _vp) for n in ("objectness", "sem_cls", "iou", "heading_scores", "heading_residuals",
-                                    "size_scores", "size_residuals", "center", "vote_xyz", "mean_size",
-                                    "label_mask", "gt_center", "gt_heading_class", "gt_heading_residual",
-                                    "gt_size_class", "gt_size_residual", "gt_sem_cls", "gt_box_mask",
-                                    "student_objectness", "student_vote_xyz", "flip_x", "flip_y", "rot_mat",
-                                    "scale", "iou_labels", "stats", "workspace")])
 
 
 # order of the kernel's `stats` output (include/lhs_hip.h LHS_STAT_*)
@@ -276,7 +246,7 @@ def pseudo_label_stats_gpu(objectness, sem_cls, iou_scores, heading_scores, head
         keep.append(t)
         return t.data_ptr()
     rows = labeled + s
-    a = LhsStatsArgs()
+    a = records.LhsStatsArgs()
     a.S, a.K, a.labeled, a.rows = s, k, labeled, rows
     a.NC, a.NI, a.NH, a.NS = sem_cls.shape[2], iou_scores.shape[2], heading_scores.shape[2], size_scores.shape[2]
     a.obj_threshold, a.cls_threshold, a.iou_threshold = float(obj_threshold), float(cls_threshold), float(iou_threshold)
@@ -301,8 +271,7 @@ def pseudo_label_stats_gpu(objectness, sem_cls, iou_scores, heading_scores, head
     stats = torch.empty((len(STAT_KEYS),), dtype=f32, device=dev)
     workspace = torch.empty((int(_lib.lhs_pseudo_stats_workspace_bytes(s, k)),), dtype=torch.uint8, device=dev)
     a.iou_labels, a.stats, a.workspace = iou_labels.data_ptr(), stats.data_ptr(), workspace.data_ptr()
-    with torch.cuda.device(dev):
-        _L.check(_lib.lhs_pseudo_stats(ctypes.byref(a), _L.current_stream_ptr(dev)), "lhs_pseudo_stats")
+    _L.run("lhs_pseudo_stats", a, dev)
     out = {"unlabeled_iou_labels": iou_labels}
     out.update({name: stats[i] for i, name in enumerate(STAT_KEYS)})
     if assignment:  # (the first S*K int32 of the workspace, include/lhs_hip.h)

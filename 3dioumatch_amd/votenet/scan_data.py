@@ -30,13 +30,12 @@ first too) the batches are bit-equal to the labeled loaders' eval batches.
 Zero sign: -0.0 and +0.0 compare equal in numpy's partition, so where the selected order statistic is
 a zero its sign is unspecified; floors are compared with ==, everything else bit for bit.
 """
-import ctypes
-import importlib
 import os
 
 import numpy as np
 import torch
 
+from .. import records
 from .scannet_raw import read_ply_vertices
 from .sunrgbd_raw import read_mat_points
 from .scene_loader import (DRAW_EMA, DRAW_STUDENT, MAX_BATCH, SceneError, draw_key, epoch_plan,  # noqa: F401
@@ -46,8 +45,6 @@ from .scene_loader import (DRAW_EMA, DRAW_STUDENT, MAX_BATCH, SceneError, draw_k
 DATASETS = ("scannet", "sunrgbd")
 MEAN_COLOR_RGB = {"scannet": np.array([109.8, 97.2, 83.8]),  # scannet_detection_dataset.py:24
                   "sunrgbd": np.array([0.5, 0.5, 0.5])}      # sunrgbd_detection_dataset.py:41
-
-_c_int, _c_uint, _vp = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p
 
 
 def host_floor(z):
@@ -70,26 +67,6 @@ def host_floor(z):
     if g >= f(0.5):
         return f(b - f(d * f(f(1) - g)))
     return f(a + f(d * g))
-
-
-class _PrepareArgs(ctypes.Structure):  # field order == include/scan_hip.h ScanPrepareArgs
-    _fields_ = [("S", _c_int), ("C", _c_int)] + [(n, _vp) for n in ("cloud", "offset", "count", "floor", "nonfinite")]
-
-
-class _BatchArgs(ctypes.Structure):  # field order == include/scan_hip.h ScanBatchArgs
-    _fields_ = ([(n, _c_int) for n in ("B", "N", "C", "use_color", "use_height", "dataset")] +
-                [("seed", _c_uint), ("counter", _c_uint)] +
-                [(n, _c_int * MAX_BATCH) for n in ("scene", "scan_idx")] +
-                [(n, _vp) for n in ("cloud", "offset", "count", "floor", "idx_in", "point_clouds", "scan_idx_out")])
-
-
-class _SemiArgs(ctypes.Structure):  # field order == include/scan_hip.h ScanSemiArgs
-    _fields_ = ([(n, _c_int) for n in ("B", "N", "C", "use_color", "use_height", "dataset", "row0")] +
-                [("seed", _c_uint), ("counter", _c_uint)] +
-                [(n, _c_int * MAX_BATCH) for n in ("scene", "scan_idx")] +
-                [(n, _vp) for n in ("cloud", "offset", "count", "floor", "idx_in", "ema_idx_in", "u_in",
-                                    "point_clouds", "ema_point_clouds", "flip_x_axis", "flip_y_axis",
-                                    "rot_angle", "rot_mat", "scale", "supervised_mask", "scan_idx_out")])
 
 
 DRAW_UNIFORM = 2  # draw index of the first augmentation uniform of a row (scene_hip.h, sunrgbd_hip.h)
@@ -130,17 +107,15 @@ def _load_cloud(path):
 
 def scan_prepare_gpu(cloud, offset, count):
     """(floor (S,) f32, nonfinite (S,) i32) of the scans of a flat (P, C) device cloud: one launch."""
-    _L = importlib.import_module("3dioumatch_amd._lib")
+    from .. import _lib
     S = count.shape[0]
     floor = torch.empty(S, dtype=torch.float32, device=cloud.device)
     nonfinite = torch.empty(S, dtype=torch.int32, device=cloud.device)
-    a = _PrepareArgs()
+    a = records.ScanPrepareArgs()
     a.S, a.C = S, cloud.shape[1]
     a.cloud, a.offset, a.count = cloud.data_ptr(), offset.data_ptr(), count.data_ptr()
     a.floor, a.nonfinite = floor.data_ptr(), nonfinite.data_ptr()
-    with torch.cuda.device(cloud.device):
-        _L.check(_L.lib.scene_scan_prepare(ctypes.byref(a), _L.current_stream_ptr(cloud.device)),
-                 "scene_scan_prepare")
+    _lib.run("scene_scan_prepare", a, cloud.device)
     return floor, nonfinite
 
 
@@ -266,7 +241,7 @@ class ScanLoader(object):
         if tuple(pc.shape) != (B, N, self.channels) or pc.dtype != torch.float32 or not pc.is_contiguous() or \
                 tuple(si.shape) != (B,) or si.dtype != torch.int64 or pc.device != st.device:
             raise ValueError("output set does not match the batch layout")
-        a = _BatchArgs()
+        a = records.ScanBatchArgs()
         a.B, a.N, a.C = B, N, st.columns
         a.use_color, a.use_height = int(self.use_color), int(self.use_height)
         a.dataset = DATASETS.index(st.dataset)
@@ -378,7 +353,7 @@ class ScanLoader(object):
             if k not in out or tuple(out[k].shape) != s or out[k].dtype != d or not out[k].is_contiguous() or \
                     out[k].device != st.device:
                 raise ValueError("output set does not match the rows' layout at %r" % k)
-        a = _SemiArgs()
+        a = records.ScanSemiArgs()
         a.B, a.N, a.C, a.row0 = B, N, st.columns, row0
         a.use_color, a.use_height = int(self.use_color), int(self.use_height)
         a.dataset = DATASETS.index(st.dataset)

@@ -30,36 +30,16 @@ path of a `device=None` parent.
 Dropped tiles keep their cores: a detection whose centre falls into the core of a tile that was not
 built (fewer than min_points points there) is owned by no tile.
 """
-import ctypes
-import importlib
-
 import numpy as np
 import torch
 
+from .. import records
 from .scan_data import ScanStore, host_floor, scan_prepare_gpu
 from .scene_loader import scene_offsets, to_device
 
 SEGMENT = 65536   # SCAN_TILE_SEGMENT
 BLOCK = 1024      # SCAN_TILE_BLOCK
 MAX_TILES = 4096  # SCAN_TILE_MAX
-
-_c_int, _c_ll, _vp = ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p
-
-
-class _BoundsArgs(ctypes.Structure):  # field order == include/scan_tile_hip.h ScanBoundsArgs
-    _fields_ = ([(n, _c_int) for n in ("S", "C", "max_segments")] +
-                [(n, _vp) for n in ("cloud", "offset", "count", "partial", "bounds")])
-
-
-class _CountArgs(ctypes.Structure):  # field order == include/scan_tile_hip.h ScanTileCountArgs
-    _fields_ = ([(n, _c_int) for n in ("T", "C", "max_segments")] +
-                [(n, _vp) for n in ("cloud", "offset", "count", "parent", "window", "counts")])
-
-
-class _GatherArgs(ctypes.Structure):  # field order == include/scan_tile_hip.h ScanTileGatherArgs
-    _fields_ = ([(n, _c_int) for n in ("T", "C", "max_segments")] + [("rows", _c_ll)] +
-                [(n, _vp) for n in ("cloud", "offset", "count", "parent", "window", "base", "crops")])
-
 
 # ---------------------------------------------------------------------------------- the grid
 def _tile_sizes(tile):
@@ -164,45 +144,40 @@ def _segments(count):
 
 def scan_bounds_gpu(cloud, offset, count, max_segments):
     """(S, 4) float32 xmin, xmax, ymin, ymax of the scans of a flat (P, C) device cloud: two launches."""
-    _L = importlib.import_module("3dioumatch_amd._lib")
+    from .. import _lib
     S = count.shape[0]
     partial = torch.empty((S, max_segments, 4), dtype=torch.float32, device=cloud.device)
     bounds = torch.empty((S, 4), dtype=torch.float32, device=cloud.device)
-    a = _BoundsArgs()
+    a = records.ScanBoundsArgs()
     a.S, a.C, a.max_segments = S, cloud.shape[1], max_segments
     a.cloud, a.offset, a.count = cloud.data_ptr(), offset.data_ptr(), count.data_ptr()
     a.partial, a.bounds = partial.data_ptr(), bounds.data_ptr()
-    with torch.cuda.device(cloud.device):
-        _L.check(_L.lib.scene_scan_bounds(ctypes.byref(a), _L.current_stream_ptr(cloud.device)), "scene_scan_bounds")
+    _lib.run("scene_scan_bounds", a, cloud.device)
     return bounds
 
 
 def tile_count_gpu(cloud, offset, count, parent, window, max_segments):
     """(T, max_segments) int32: per tile and segment of its parent the rows inside the window."""
-    _L = importlib.import_module("3dioumatch_amd._lib")
+    from .. import _lib
     T = parent.shape[0]
     counts = torch.empty((T, max_segments), dtype=torch.int32, device=cloud.device)
-    a = _CountArgs()
+    a = records.ScanTileCountArgs()
     a.T, a.C, a.max_segments = T, cloud.shape[1], max_segments
     a.cloud, a.offset, a.count = cloud.data_ptr(), offset.data_ptr(), count.data_ptr()
     a.parent, a.window, a.counts = parent.data_ptr(), window.data_ptr(), counts.data_ptr()
-    with torch.cuda.device(cloud.device):
-        _L.check(_L.lib.scene_scan_tile_count(ctypes.byref(a), _L.current_stream_ptr(cloud.device)),
-                 "scene_scan_tile_count")
+    _lib.run("scene_scan_tile_count", a, cloud.device)
     return counts
 
 
 def tile_gather_gpu(cloud, offset, count, parent, window, base, rows, max_segments):
     """(rows, C) float32: the crops, segment g of tile t written from row base[t, g] on."""
-    _L = importlib.import_module("3dioumatch_amd._lib")
+    from .. import _lib
     crops = torch.empty((rows, cloud.shape[1]), dtype=torch.float32, device=cloud.device)
-    a = _GatherArgs()
+    a = records.ScanTileGatherArgs()
     a.T, a.C, a.max_segments, a.rows = parent.shape[0], cloud.shape[1], max_segments, rows
     a.cloud, a.offset, a.count = cloud.data_ptr(), offset.data_ptr(), count.data_ptr()
     a.parent, a.window, a.base, a.crops = parent.data_ptr(), window.data_ptr(), base.data_ptr(), crops.data_ptr()
-    with torch.cuda.device(cloud.device):
-        _L.check(_L.lib.scene_scan_tile_gather(ctypes.byref(a), _L.current_stream_ptr(cloud.device)),
-                 "scene_scan_tile_gather")
+    _lib.run("scene_scan_tile_gather", a, cloud.device)
     return crops
 
 

@@ -20,12 +20,12 @@ feed and eval_batches are scene_loader's, shared with sunrgbd_data and scan_data
 Keys, dtypes and shapes are those of data.make_batch (pretrain, eval) and data.make_semi_batch
 (semi-supervised); semi batches also carry `supervised_mask_host`.
 """
-import ctypes
 import os
 
 import numpy as np
 import torch
 
+from .. import records
 from . import scannet_raw as raw
 from .scene_loader import (DRAW_EMA, DRAW_STUDENT, MAX_BATCH, MAX_NUM_OBJ, SceneError, SceneLoader,  # noqa: F401
                            SceneStore, _read_list, draw_key, epoch_plan, eval_batches, feed, launch,
@@ -35,8 +35,6 @@ MAX_INSTANCES = 1024  # dense instance ids per scene (SB_MAX_INST)
 MEAN_COLOR_RGB = np.array([109.8, 97.2, 83.8])  # scannet_ssl_dataset.py:21
 NYU40IDS = np.array([3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 14, 16, 24, 28, 33, 34, 36, 39])  # model_util_scannet.py:30
 DRAW_UNIFORM = 2  # draw index of the first of a row's four uniforms (scene_hip.h)
-
-_c_int, _c_uint, _vp = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p
 
 
 def uniforms(seed, counter, row):
@@ -277,20 +275,6 @@ def host_scene(scene, idx, u=None, votes=True, boxes="raw", mean_size=None, has_
 
 
 # ------------------------------------------------------------------ batches
-class _Args(ctypes.Structure):  # field order == include/scene_hip.h SceneBatchArgs
-    _fields_ = ([(n, _c_int) for n in ("B", "N", "C", "has_height", "augment", "ema", "vote_rows",
-                                       "box_rows", "box_aug_rows", "NS")] +
-                [("seed", _c_uint), ("counter", _c_uint)] +
-                [(n, _c_int * MAX_BATCH) for n in ("scene", "scan_idx", "supervised")] +
-                [(n, _vp) for n in ("cloud", "inst", "sem", "offset", "count", "ninst", "boxes", "nbox",
-                                    "mean_size", "idx_in", "ema_idx_in", "u_in", "idx_out", "table",
-                                    "point_clouds", "ema_point_clouds", "vote_label", "vote_label_mask",
-                                    "center_label", "heading_class_label", "heading_residual_label",
-                                    "size_class_label", "size_residual_label", "sem_cls_label",
-                                    "box_label_mask", "supervised_mask", "scan_idx_out", "flip_x_axis",
-                                    "flip_y_axis", "rot_angle", "rot_mat", "scale")])
-
-
 class ScanNetLoader(SceneLoader):
     """SceneLoader with the semantics of the reference's ScanNet datasets:
 
@@ -300,7 +284,7 @@ class ScanNetLoader(SceneLoader):
 
     `config`: scannet_config(mean_size_arr=...).  Explicit draws: {'idx': (B, N) ints, 'ema_idx':
     (B, N), 'u': (B, 4) float64 uniforms}."""
-    _Args, _ENTRY, _DATASET = _Args, "scene_batch_build", "scannet"
+    _Args, _ENTRY, _DATASET = records.SceneBatchArgs, "scene_batch_build", "scannet"
     _STORE_KEYS = ("cloud", "inst", "sem", "offset", "count", "ninst", "boxes", "nbox")
     _UNIFORMS = {"u": 4}
     _uniforms = staticmethod(uniforms)

@@ -35,13 +35,13 @@ scene_loader.sample_indices(seed, 0, scan_index, DRAW_STUDENT, n, max_points) --
 device computes the same function (csrc/scene_common.h) -- or the explicit `choices[name]`.
 """
 import csv
-import ctypes
 import json
 import os
 
 import numpy as np
 import torch
 
+from .. import records
 from .scene_loader import (DRAW_STUDENT, MAX_NUM_OBJ, SceneError, explicit_indices, launch, sample_indices,
                            to_device)
 
@@ -63,8 +63,6 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
 SUFFIXES = {"mesh": "_vh_clean_2.ply", "agg": ".aggregation.json", "seg": "_vh_clean_2.0.010000.segs.json",
             "meta": ".txt"}
-
-_c_int, _c_uint, _c_ll, _vp = ctypes.c_int, ctypes.c_uint, ctypes.c_longlong, ctypes.c_void_p
 
 
 # ------------------------------------------------------------------ the mesh file
@@ -370,14 +368,6 @@ def host_export_raw_scan(rec, max_points=MAX_NUM_POINT, seed=0, scan_index=0, ch
 
 
 # ------------------------------------------------------------------ the device export
-class _Args(ctypes.Structure):  # field order == include/scannet_raw_hip.h ScanNetRawArgs
-    _fields_ = ([("S", _c_int), ("P", _c_ll), ("Q", _c_ll), ("T", _c_ll), ("max_objects", _c_int),
-                 ("max_points", _c_int), ("seed", _c_uint)] +
-                [(n, _vp) for n in ("raw", "seg", "matrix", "vert_offset", "seg_offset", "seg_label", "seg_object",
-                                    "obj_offset", "object_label", "out_offset", "keep", "scan_index", "choice",
-                                    "extent", "vert", "ins_label", "sem_label", "bbox", "nbox")])
-
-
 def _offsets(counts):
     return np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64)
 
@@ -428,7 +418,7 @@ def _stage_chunk(chunk, device, max_points, seed, choices):
     out_at, out_total = _layout(outputs)
     out = torch.empty(out_total // 8, dtype=torch.float64, device=device)  # every output, one block
     extent = torch.empty((T + 1) * 6, dtype=torch.int32, device=device)
-    a = _Args()
+    a = records.ScanNetRawArgs()
     a.S, a.P, a.Q, a.T = S, P, Q, T
     a.max_objects, a.max_points, a.seed = int(objects.max()), int(max_points), int(seed) & 0xFFFFFFFF
     for k, _ in inputs:

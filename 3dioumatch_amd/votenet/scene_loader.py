@@ -15,7 +15,6 @@ scan_data (scans without labels).  Nothing here knows a dataset.
 The device builders (csrc/scene_batch.hip, sunrgbd_batch.hip, scan_batch.hip) differ in their
 arithmetic and stay apart; they share csrc/scene_common.h.
 """
-import ctypes
 import importlib
 
 import numpy as np
@@ -169,14 +168,13 @@ def launch(entry, args, keep, stream, device):
     """Run the builder `entry` of the library on `stream` (None: the device's current stream) with
     the filled args record.  `keep`: the device memory the caller allocated for this call on the
     CURRENT stream and that `stream` writes or reads -- fresh outputs, scratch, uploaded draws."""
-    _L = importlib.import_module("3dioumatch_amd._lib")
+    from .. import _lib
     current = torch.cuda.current_stream(device)
     if stream is None:
         stream = current
     if keep and stream != current:
         stream.wait_stream(current)  # the blocks just allocated may have been freed by queued work
-    with torch.cuda.device(device):
-        _L.check(getattr(_L.lib, entry)(ctypes.byref(args), stream.cuda_stream), entry)
+    _lib.run(entry, args, device, stream=stream.cuda_stream)
     for t in keep:  # not handed to another allocation before `stream` is done with them
         t.record_stream(stream)
 
@@ -222,7 +220,7 @@ class SceneLoader(object):
     gives the size residuals, in float64 as the reference.  Device draws are keyed by (seed, counter,
     batch row, draw index); `draws=` replaces them with explicit ones.
 
-    A dataset's loader sets `_Args` (the ctypes form of its args record), `_ENTRY` (the library's
+    A dataset's loader sets `_Args` (its args record, a class of records.py), `_ENTRY` (the library's
     builder), `_STORE_KEYS` (the store's device arrays, named as the record's fields), `_UNIFORMS`
     (explicit per-row uniforms: key -> how many; draw `key` goes to the field `key_in`) and
     `_uniforms` (seed, counter, row -> the row's augmentation uniforms), and overrides `_host_row`

@@ -26,13 +26,13 @@ shared with scannet_data and scan_data and re-exported here.
 Keys, dtypes and shapes are those of data.make_batch (pretrain, eval) and data.make_semi_batch
 (semi-supervised) for sunrgbd_config(); semi batches also carry `supervised_mask_host`.
 """
-import ctypes
 import importlib
 import os
 
 import numpy as np
 import torch
 
+from .. import records
 from . import sunrgbd_raw as raw
 from .scene_loader import (DRAW_EMA, DRAW_STUDENT, MAX_BATCH, MAX_NUM_OBJ, SceneError, SceneLoader,  # noqa: F401
                            SceneStore, _element, _read_list, draw_key, epoch_plan, eval_batches, feed,
@@ -43,8 +43,6 @@ MEAN_COLOR_RGB = np.array([0.5, 0.5, 0.5])  # sunrgbd_detection_dataset.py:41 (c
 VOTE_COLS = 10     # mask, three votes
 # draw indices of the hash beyond the two point samples (sunrgbd_hip.h)
 DRAW_FLIP, DRAW_ANGLE, DRAW_SCALE, DRAW_COLOR, DRAW_JITTER, DRAW_DROP = 2, 3, 4, 5, 11, 12
-
-_c_int, _c_uint, _vp = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p
 
 
 # ------------------------------------------------------------------ reading scans and splits
@@ -386,21 +384,6 @@ def point_uniforms(seed, counter, row, n):
 
 
 # ------------------------------------------------------------------ batches
-class _Args(ctypes.Structure):  # field order == include/sunrgbd_hip.h SunBatchArgs
-    _fields_ = ([(n, _c_int) for n in ("B", "N", "C", "has_height", "augment", "color_aug", "ema",
-                                       "vote_rows", "box_rows", "box_aug_rows", "div256_from", "NS",
-                                       "num_heading_bin", "u_point_stride")] +
-                [("seed", _c_uint), ("counter", _c_uint)] +
-                [(n, _c_int * MAX_BATCH) for n in ("scene", "scan_idx", "supervised")] +
-                [(n, _vp) for n in ("cloud", "votes", "offset", "count", "boxes", "nbox", "mean_size",
-                                    "idx_in", "ema_idx_in", "u_in", "u_color_in", "u_point_in",
-                                    "point_clouds", "ema_point_clouds", "vote_label", "vote_label_mask",
-                                    "center_label", "heading_class_label", "heading_residual_label",
-                                    "size_class_label", "size_residual_label", "sem_cls_label",
-                                    "box_label_mask", "supervised_mask", "scan_idx_out", "flip_x_axis",
-                                    "flip_y_axis", "rot_angle", "rot_mat", "scale")])
-
-
 class SunRgbdLoader(SceneLoader):
     """SceneLoader with the semantics of the reference's SUN RGB-D datasets:
 
@@ -413,7 +396,7 @@ class SunRgbdLoader(SceneLoader):
     the source point index.  Explicit draws: {'idx': (B, N) ints, 'ema_idx': (B, N), 'u': (B, 3)
     float64 uniforms (flip, angle, scale), 'u_color': (B, 6), 'u_point': (B, 2, n_max) jitter and
     drop by source point}."""
-    _Args, _ENTRY, _DATASET = _Args, "scene_sunrgbd_batch_build", "sunrgbd"
+    _Args, _ENTRY, _DATASET = records.SunBatchArgs, "scene_sunrgbd_batch_build", "sunrgbd"
     _STORE_KEYS = ("cloud", "offset", "count", "boxes", "nbox")
     _UNIFORMS = {"u": 3, "u_color": 6}
     _uniforms = staticmethod(uniforms)

@@ -37,7 +37,6 @@ Stricter than the reference, each a SceneError naming the scene: a label line th
 or a non-numeric one, a non-finite label value, more than MAX_NUM_OBJ kept boxes, NaN or Inf in a
 cloud.  A scene with no kept box is kept (--gen_v1_data passes skip_empty_scene=False).
 """
-import ctypes
 import os
 import struct
 import zlib
@@ -45,6 +44,7 @@ import zlib
 import numpy as np
 import torch
 
+from .. import records
 from .scene_loader import DRAW_STUDENT, MAX_NUM_OBJ, SceneError, explicit_indices, launch, sample_indices, to_device
 
 NUM_POINT = 50000  # sunrgbd_data.py --gen_v1_data / --gen_v2_data
@@ -57,8 +57,6 @@ TYPE2CLASS = {'bed': 0, 'table': 1, 'sofa': 2, 'chair': 3, 'toilet': 4, 'desk': 
 CHUNK_POINTS = 1 << 22
 KEEP_DRAWN, KEEP_GIVEN = 0, 1  # SUNRAW_KEEP_*
 ROW_COLS = 7                   # SUNRAW_ROW_COLS: x y z, r g b - 0.5, z - floor
-
-_c_int, _c_uint, _c_ll, _vp = ctypes.c_int, ctypes.c_uint, ctypes.c_longlong, ctypes.c_void_p
 
 # ------------------------------------------------------------------ Level-5 MAT files
 _MI = {1: "i1", 2: "u1", 3: "<i2", 4: "<u2", 5: "<i4", 6: "<u4", 7: "<f4", 9: "<f8", 12: "<i8", 13: "<u8"}
@@ -334,12 +332,6 @@ def host_export_trainval_scene(rec, num_point=NUM_POINT, seed=0, scan_index=0, c
 
 
 # ------------------------------------------------------------------ the device export
-class _Args(ctypes.Structure):  # field order == include/sunrgbd_raw_hip.h SunRgbdRawArgs
-    _fields_ = ([("S", _c_int), ("num_point", _c_int), ("elem", _c_int), ("seed", _c_uint), ("P", _c_ll)] +
-                [(n, _vp) for n in ("raw", "raw_offset", "keep", "scan_index", "choice",
-                                    "kept", "floor", "nonfinite", "rows")])
-
-
 def _layout(sections):
     """[(name, bytes)] -> ({name: offset}, total), every section on a 16-byte boundary."""
     at, total = {}, 0
@@ -377,7 +369,7 @@ def _stage_chunk(chunk, device, num_point, seed, choices):
                ("nonfinite", S * 8)]
     out_at, out_total = _layout(outputs)
     out = torch.empty(out_total // 8, dtype=torch.float64, device=device)  # every output, one block
-    a = _Args()
+    a = records.SunRgbdRawArgs()
     a.S, a.num_point, a.elem, a.seed, a.P = S, N, int(dtype == np.float64), int(seed) & 0xFFFFFFFF, P
     for k, _ in inputs:
         setattr(a, k, upload.data_ptr() + at[k])

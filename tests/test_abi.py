@@ -2,6 +2,7 @@
 headers in include/ declare (no compute without a GPU), every declaration cites the reference
 interface it replaces, and the Python drop-in modules expose the reference's pybind surfaces."""
 import ctypes
+import glob
 import importlib
 import os
 import re
@@ -10,8 +11,12 @@ import pytest
 
 from conftest import ROOT, load_pkg
 
+# the drop-in surface of the reference's kernels: every declaration cites what it replaces
 HEADERS = ["pn2_hip.h", "iou3d_hip.h", "mlp_hip.h", "lhs_hip.h", "loss_hip.h"]
-DECL = re.compile(r"^(?:int|size_t|const char \*)\s*\*?\s*((?:pn2|iou3d|mlp|lhs|votenet)_\w+)\s*\(", re.M)
+# every header: the loaders' and the scan path's too, which have no counterpart in the reference
+ALL_HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(ROOT, "include", "*.h")))
+DECL = re.compile(r"^(?:int|size_t|long long|const char \*)\s*\*?\s*"
+                  r"((?:pn2|iou3d|mlp|lhs|votenet|scene|scannet)_\w+)\s*\(", re.M)
 
 
 def declared(header):
@@ -29,7 +34,11 @@ def test_headers_declare_expected_entry_points():
         assert must in names, must
 
 
-@pytest.mark.parametrize("header", HEADERS)
+def test_the_headers_are_all_there():
+    assert len(ALL_HEADERS) >= 14 and set(HEADERS) <= set(ALL_HEADERS)
+
+
+@pytest.mark.parametrize("header", ALL_HEADERS)
 def test_library_exports_every_declared_symbol(header):
     pkg = load_pkg()
     so = os.path.join(os.path.dirname(pkg.__file__), "lib3dioumatch_hip.so")
@@ -55,6 +64,15 @@ def test_ctypes_binding_covers_the_headers():
     L = importlib.import_module("3dioumatch_amd._lib")
     names = sum((declared(h)[1] for h in HEADERS), [])
     assert set(names) == set(L.EXPORTS)
+    every = sum((declared(h)[1] for h in ALL_HEADERS), [])
+    assert len(every) == len(set(every)) >= 163
+    assert not set(L.EXPORTS) & set(L._LOADER_SIGNATURES)
+    assert set(every) == set(L.EXPORTS) | set(L._LOADER_SIGNATURES)
+    # and nothing is declared in a form the pattern above does not read
+    loose = re.compile(r"^[A-Za-z_][\w \*]*?\b(\w+)\s*\([^;{]*\)\s*;", re.M)
+    for h in ALL_HEADERS:
+        text = re.sub(r"/\*.*?\*/", "", declared(h)[0], flags=re.S)
+        assert set(loose.findall(text)) == set(declared(h)[1]), h
 
 
 def test_dropin_surfaces_match_reference_pybind_names():
@@ -74,6 +92,37 @@ def test_dropin_surfaces_match_reference_pybind_names():
     # OpenPCDet/pcdet/ops/iou3d_nms/iou3d_nms_utils.py:12-116
     for n in ["boxes_bev_iou_cpu", "boxes_iou_bev", "boxes_iou3d_gpu", "nms_gpu", "nms_normal_gpu"]:
         assert callable(getattr(ut, n))
+
+
+def test_dropin_directory_alone_on_the_path_is_enough(tmp_path):
+    """`sys.path.insert(0, ".../3dioumatch_amd/dropin")` and nothing else of
+    this repository.  A fresh interpreter, started outside the repository, imports the drop-in modules
+    without the package being importable; both of them and _mlp_ext share one binding and one set of
+    record classes."""
+    import subprocess
+    import sys
+    dropin = os.path.join(ROOT, "3dioumatch_amd", "dropin")
+    code = "\n".join([
+        "import os, sys",
+        "root = %r" % ROOT,
+        "sys.path[:] = [p for p in sys.path if os.path.abspath(p or os.getcwd()) != root]",
+        "sys.path.insert(0, %r)" % dropin,
+        "import importlib.util",
+        "assert importlib.util.find_spec('3dioumatch_amd') is None",
+        "import pointnet2._ext as ext",
+        "import pointnet2._mlp_ext as K",
+        "import pcdet.ops.iou3d_nms.iou3d_nms_cuda as cu",
+        "assert '3dioumatch_amd' not in sys.modules",
+        "assert cu._L is ext._L and K.MlpOperand is ext._L.records.MlpOperand",
+        "assert sys.modules['3dioumatch_amd.records'] is ext._L.records",
+        "assert 'pn2_ball_query' in ext._L.EXPORTS and callable(cu.boxes_iou_bev_cpu)",
+        "print('dropin alone: ok')"])
+    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
+    paths = [p for p in os.environ.get("PYTHONPATH", "").split(os.pathsep) if p and os.path.abspath(p) != ROOT]
+    if paths:
+        env["PYTHONPATH"] = os.pathsep.join(paths)
+    run = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), env=env, capture_output=True, text=True)
+    assert run.returncode == 0 and "dropin alone: ok" in run.stdout, run.stderr[-2000:]
 
 
 def test_no_cpu_fallback_in_device_entry_points():

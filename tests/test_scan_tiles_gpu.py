@@ -191,9 +191,10 @@ def test_merge_is_host_merge(NC):
 
     # scan 1 alone into its rows of a sentinel arena: scan 0's rows are untouched
     L = importlib.import_module("3dioumatch_amd._lib")
+    R = importlib.import_module("3dioumatch_amd.records")
     merged = torch.full((words,), 7.0, dtype=torch.float32, device=DEV)
     keep = [_dev(first[1:]), _dev(tiles[1:]), _dev(core)]
-    a = D._MergeArgs()
+    a = R.ScanMergeArgs()
     a.S, a.K, a.NC, a.cap, a.max_tiles = 1, K, NC, cap, 4
     a.first, a.tiles, a.core = (t.data_ptr() for t in keep)
     lin, _ = D.arena_layout(T, K, NC)
@@ -207,7 +208,7 @@ def test_merge_is_host_merge(NC):
     # refusals, without a launch
     with pytest.raises(ValueError, match="cap"):
         D.merge_gpu(merged, tile_arena, _dev(first), _dev(tiles), _dev(core), S, T, K, NC, 4 * K - 1, 4)
-    a = D._MergeArgs()
+    a = R.ScanMergeArgs()
     for f, _ in a._fields_[5:]:
         setattr(a, f, tile_arena.data_ptr())
     invalid = 1  # hipErrorInvalidValue

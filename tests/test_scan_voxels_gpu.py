@@ -277,6 +277,7 @@ def _launches_with_outside(SV, ST, store, voxel, keep):
 def test_entry_points_refuse_without_a_launch():
     _, SC, ST, SV = _mods()
     L = importlib.import_module("3dioumatch_amd._lib")
+    R = importlib.import_module("3dioumatch_amd.records")
     store = SC.ScanStore(cases.clouds("edge", 3), DEV, "scannet")
     d, G = store.dev, 1
     mark = SV.voxel_mark_gpu(d["cloud"], d["offset"], d["count"], store.count, 0.25, "first", G)
@@ -293,7 +294,7 @@ def test_entry_points_refuse_without_a_launch():
     def refused(change):
         a = record()
         change(a)
-        c, g = SV._CountArgs(), SV._GatherArgs()
+        c, g = R.ScanVoxelCountArgs(), R.ScanVoxelGatherArgs()
         c.mark, c.counts = a, counts.data_ptr()
         g.mark, g.rows = a, P
         g.base, g.out, g.source = base.data_ptr(), out.data_ptr(), source.data_ptr()
@@ -319,7 +320,7 @@ def test_entry_points_refuse_without_a_launch():
     for change in changes:
         assert refused(change) == [INVALID] * 3
     a = record()
-    c, g = SV._CountArgs(), SV._GatherArgs()
+    c, g = R.ScanVoxelCountArgs(), R.ScanVoxelGatherArgs()
     c.mark, g.mark, g.rows = a, a, P
     assert L.lib.scene_scan_voxel_count(ctypes.byref(c), None) == INVALID  # counts NULL
     for name in ("base", "out", "source"):

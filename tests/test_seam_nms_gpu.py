@@ -131,6 +131,7 @@ def test_more_candidates_than_a_workgroup_has_threads():
 def test_refusals_without_a_launch():
     _, _, _, D = _mods()
     L = importlib.import_module("3dioumatch_amd._lib")
+    R = importlib.import_module("3dioumatch_amd.records")
     planes, settings, _, _ = hand_case("corner", 3)
     case = Case(planes, tables(), 3)
     K, cap = case.K, case.cap
@@ -140,7 +141,7 @@ def test_refusals_without_a_launch():
     invalid = 1  # hipErrorInvalidValue
 
     def args(**over):
-        a = D._SeamArgs()
+        a = R.ScanSeamArgs()
         for f, kind in a._fields_:
             if kind is ctypes.c_void_p:
                 setattr(a, f, case.arena.data_ptr())
@@ -156,12 +157,12 @@ def test_refusals_without_a_launch():
                  {"dims": 2}, {"cap": 4 * K - 1}, {"max_tiles": 0}, {"scratch_bytes": need - 1}, {"scratch_bytes": 0},
                  {"scratch": scratch.data_ptr() + 4}):
         assert call(ctypes.byref(args(**over)), None) == invalid, over
-    for f, kind in D._SeamArgs._fields_:
+    for f, kind in R.ScanSeamArgs._fields_:
         if kind is ctypes.c_void_p:
             assert call(ctypes.byref(args(**{f: None})), None) == invalid, f
     assert call(None, None) == invalid
-    assert [f for f, _ in D._SeamArgs._fields_[:21]] == [f for f, _ in D._MergeArgs._fields_]
-    assert ctypes.sizeof(D._SeamArgs) == ctypes.sizeof(D._MergeArgs) + 3 * 8 + 8 + 3 * 4 + 4 + 8 + 8
+    assert [f for f, _ in R.ScanSeamArgs._fields_[:21]] == [f for f, _ in R.ScanMergeArgs._fields_]
+    assert ctypes.sizeof(R.ScanSeamArgs) == ctypes.sizeof(R.ScanMergeArgs) + 3 * 8 + 8 + 3 * 4 + 4 + 8 + 8
 
     # the binding
     d = case.dev

@@ -14,6 +14,7 @@ from conftest import ROOT, load_pkg
 
 load_pkg()
 L = importlib.import_module("3dioumatch_amd._lib")
+R = importlib.import_module("3dioumatch_amd.records")
 SL = importlib.import_module("3dioumatch_amd.votenet.scene_loader")
 SC = importlib.import_module("3dioumatch_amd.votenet.scan_data")
 SD = importlib.import_module("3dioumatch_amd.votenet.scannet_data")
@@ -201,9 +202,9 @@ def test_the_loader_refuses_what_a_store_cannot_give(data):
 
 
 def _valid_args():
-    a = SC._SemiArgs()
+    a = R.ScanSemiArgs()
     a.B, a.N, a.C, a.use_color, a.use_height, a.dataset, a.row0 = 2, 16, 6, 1, 1, 0, 1
-    for name, kind in SC._SemiArgs._fields_:
+    for name, kind in R.ScanSemiArgs._fields_:
         if kind is ctypes.c_void_p and name not in ("idx_in", "ema_idx_in", "u_in"):
             setattr(a, name, 0x1000)  # never dereferenced: every call below is refused before a launch
     return a
@@ -226,7 +227,7 @@ def test_the_entry_refuses_bad_arguments_without_a_launch(field, value):
 def test_the_entry_refuses_a_null_record_and_is_no_drop_in_export():
     assert L.lib.scene_scan_semi_build(None, None) == INVALID
     assert "scene_scan_semi_build" in L._LOADER_SIGNATURES and "scene_scan_semi_build" not in L.EXPORTS
-    assert ctypes.sizeof(SC._SemiArgs) == 4 * 9 + 2 * 4 * 64 + 4 + 8 * 16  # scan_hip.h ScanSemiArgs, padded
+    assert ctypes.sizeof(R.ScanSemiArgs) == 4 * 9 + 2 * 4 * 64 + 4 + 8 * 16  # scan_hip.h ScanSemiArgs, padded
 
 
 # ------------------------------------------------------------------ planning
