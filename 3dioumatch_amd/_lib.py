@@ -207,7 +207,7 @@ _SIGNATURES = {
     "iou3d_nms": [_vp, _c_int, _c_float, _c_int, _vp, _vp, _vp, _vp],
     "iou3d_boxes_iou_bev_cpu": [_c_int, _vp, _c_int, _vp, _vp],
 }
-_RESTYPE = {"pn2_ball_query_workspace_bytes": _sz, "lhs_pseudo_stats_workspace_bytes": _sz, "pn2_grid_bytes": _sz, "pn2_fps_workspace_bytes": _sz, "mlp_bn_workspace_floats": _sz, "mlp_gemm_wgrad_workspace_floats": _sz, "mlp_wgrad_first4_workspace_bytes": _sz, "mlp_gemm_backward_fused_workspace_floats": _sz, "mlp_bn_finalize_pairs_scratch_bytes": _sz, "mlp_chain_lin4_image_bytes": _sz, "mlp_eval_stored_image_bytes": _sz, "mlp_weight_image_elems": _sz, "mlp_pool_gram_workspace_floats": _sz, "scene_detections_merge_nms_scratch_bytes": _sz, "scene_scan_voxel_slots": ctypes.c_longlong, "scene_points_label_scratch_bytes": _sz, "scene_mask_scratch_bytes": _sz, "pn2_error_string": ctypes.c_char_p}
+_RESTYPE = {"pn2_ball_query_workspace_bytes": _sz, "lhs_pseudo_stats_workspace_bytes": _sz, "pn2_grid_bytes": _sz, "pn2_fps_workspace_bytes": _sz, "mlp_bn_workspace_floats": _sz, "mlp_gemm_wgrad_workspace_floats": _sz, "mlp_wgrad_first4_workspace_bytes": _sz, "mlp_gemm_backward_fused_workspace_floats": _sz, "mlp_bn_finalize_pairs_scratch_bytes": _sz, "mlp_chain_lin4_image_bytes": _sz, "mlp_eval_stored_image_bytes": _sz, "mlp_weight_image_elems": _sz, "mlp_pool_gram_workspace_floats": _sz, "scene_detections_merge_nms_scratch_bytes": _sz, "scene_scan_voxel_slots": ctypes.c_longlong, "scene_points_label_scratch_bytes": _sz, "scene_points_index_scratch_bytes": _sz, "scene_mask_scratch_bytes": _sz, "pn2_error_string": ctypes.c_char_p}
 
 EXPORTS = tuple(_SIGNATURES)
 
@@ -239,6 +239,9 @@ _LOADER_SIGNATURES = {
     "scene_points_label_scratch_bytes": [_c_int, _c_int],
     "scene_detections_frames": [_rec("DetectionsFramesArgs"), _vp],
     "scene_points_label": [_rec("PointsLabelArgs"), _vp],
+    # per-detection point lists: a stable multi-split of the label plane (include/point_index_hip.h)
+    "scene_points_index_scratch_bytes": [_c_int, _c_int, _c_int, ctypes.c_longlong],
+    "scene_points_index": [_rec("PointsIndexArgs"), _vp],
     # mask matching of point labels against ground-truth instances (include/mask_eval_hip.h)
     "scene_mask_scratch_bytes": [_c_int, _c_int, _c_int],
     "scene_mask_overlap": [_rec("MaskOverlapArgs"), _vp],

@@ -189,6 +189,12 @@ class PointsLabelArgs(ctypes.Structure):
                 [("scratch_bytes", _sz)] + [(n, _vp) for n in ("instance", "semantic", "points")])
 
 
+# ---------------------------------------------------------------------------------- include/point_index_hip.h
+class PointsIndexArgs(ctypes.Structure):
+    _fields_ = ([(n, _int) for n in ("S", "cap", "max_segments")] + [("P", _ll)] +
+                [(n, _vp) for n in ("key", "offset", "count", "start", "order", "scratch")] + [("scratch_bytes", _sz)])
+
+
 # ---------------------------------------------------------------------------------- include/mask_eval_hip.h
 class MaskOverlapArgs(ctypes.Structure):
     _fields_ = ([(n, _int) for n in ("S", "cap", "G", "max_blocks", "merge", "clear")] +

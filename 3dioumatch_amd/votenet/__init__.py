@@ -20,4 +20,5 @@ from .detect import host_merge_nms, merge_nms_gpu, seam_reach, seam_settings  # 
 from .scan_tiles import TileStore, tile_grid  # noqa: F401
 from .scan_voxels import VoxelStore, host_voxels  # noqa: F401
 from .point_labels import PointLabels, host_label_points, label_points  # noqa: F401
+from .point_index import PointIndex, host_point_index, point_index_gpu  # noqa: F401
 from .mask_eval import MaskAPCalculator, MaskMatch, PointTruth, host_match_masks, match_masks  # noqa: F401

@@ -6,6 +6,7 @@
     tiled = detect_tiled(engine, TileStore.from_store(raw, 8.0), config_dict, seam_nms=True)
     labels = label_points(tiled, tiled.store.source)        # tiles are not recentred: the boxes hold for the parent
     labels.instance, labels.semantic, labels.points         # device tensors; labels[i], by_name, points_of, save read
+    labels.index()                                          # the points of each row as lists (votenet/point_index.py)
 
 The reference answers "which points lie in this box" with extract_pc_in_box3d (sunrgbd/sunrgbd_utils.py:215-224),
 a scipy Delaunay hull per box on the host (models/ap_helper.py:123-135).  Here the test is the closed form
@@ -229,6 +230,7 @@ class PointLabels(object):
         self.names, self.count, self.offset, self.cap = list(names), count, offset, int(cap)
         self.prefer, self.min_score, self.frames = prefer, float(min_score), frames
         self._words, self._host = words, None  # rows | points | instance | semantic, one int32 buffer
+        self._index = None                     # index()'s PointIndex, built once
         S, P = len(self.names), int(np.sum(count, dtype=np.int64))
         self._cuts = np.cumsum([0, S, S * self.cap, P, P])
         a = self._cuts
@@ -258,20 +260,35 @@ class PointLabels(object):
     def by_name(self, name):
         return self[self.names.index(name)]
 
+    def index(self):
+        """The PointIndex of these labels (votenet/point_index.py): per-row point lists, built once and
+        kept; on the device where the labels are device tensors, without a host read, else in numpy."""
+        if self._index is None:
+            from .point_index import build_index
+            self._index = build_index(self.names, self.count, self.offset, self.cap, self.instance)
+        return self._index
+
     def points_of(self, i, row):
         """The indices, in scan i, of the points that packed row `row` owns."""
+        if self._index is not None and 0 <= int(row) < self.cap:  # the same array, as a slice of the lists
+            return self._index.points_of(i, row).astype(np.int64)
         return np.nonzero(self[i]["instance"] == int(row))[0]
 
-    def save(self, directory):
+    def save(self, directory, index=False):
         """<name>_labels.npz per scan: instance, semantic, points (cut to the scan's count of
-        detections), prefer, min_score."""
+        detections), prefer, min_score; with `index` also the scan's order and start (cut to the scan's
+        count of detections plus one) of index()."""
         os.makedirs(directory, exist_ok=True)
         rows = self.host()["rows"]
+        lists = self.index() if index else None
         for i, name in enumerate(self.names):
             one = self[i]
+            more = {}
+            if lists is not None:
+                more = {"order": lists[i]["order"], "start": lists[i]["start"][:int(rows[i]) + 1]}
             np.savez(os.path.join(directory, name + "_labels.npz"), instance=one["instance"], semantic=one["semantic"],
                      points=one["points"][:int(rows[i])], prefer=np.array(self.prefer),
-                     min_score=np.float64(self.min_score))
+                     min_score=np.float64(self.min_score), **more)
 
 
 def _read_layout(found, S):

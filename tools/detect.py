@@ -21,6 +21,8 @@ With --voxel every scan is first downsampled on the device to one point per occu
 With --labels --out also gets <name>_labels.npz per scan (votenet/point_labels.py: label_points, PointLabels.save): for every
 point of the scan AS LOADED, before --voxel and --tile, the row of <name>.npz that owns it or -1, that row's class, and
 the points per row; --labels-prefer and --labels-min-score are label_points' arguments; without it nothing changes.
+With --labels --labels-index the files also hold each row's point list (votenet/point_index.py: PointLabels.index):
+`order`, the scan's points grouped by owning row, and `start`, where each row's list begins in it.
 With --labels --truth DIR the labels are then scored against the ground-truth instances of a prepared ScanNet folder
 (DIR/<name>_ins_label.npy, DIR/<name>_sem_label.npy, row for row with the scan as loaded; votenet/mask_eval.py:
 MaskAPCalculator) and the mask AP metrics are printed per --mask-iou threshold; without it nothing changes."""
@@ -115,6 +117,20 @@ def score_masks(found, result, masks, device):
     return metrics
 
 
+def index_flags(ap):
+    """The point lists' flag, a group of its own that main() adds to parser()'s."""
+    ap.add_argument('--labels-index', dest='labels_index', action='store_true',
+                    help='with --labels: <name>_labels.npz also holds order and start, the point list of every row')
+    return ap
+
+
+def indexing(flags):
+    """False without --labels-index (the plain path)."""
+    if getattr(flags, "labels_index", False) and not flags.labels:
+        raise SystemExit("--labels-index goes with --labels")
+    return bool(getattr(flags, "labels_index", False))
+
+
 def labeling(flags):
     """None without --labels (the plain path), else (prefer, min_score)."""
     if not flags.labels:
@@ -129,11 +145,12 @@ def labeling(flags):
     return flags.labels_prefer or "score", least
 
 
-def write_labels(found, raw_store, labels, out):
-    """label_points of the detections on the store as it was loaded -> <name>_labels.npz in `out`."""
+def write_labels(found, raw_store, labels, out, index=False):
+    """label_points of the detections on the store as it was loaded -> <name>_labels.npz in `out`;
+    with `index` the files also hold the point lists."""
     PL = importlib.import_module("3dioumatch_amd.votenet.point_labels")
     result = PL.label_points(found, raw_store, prefer=labels[0], min_score=labels[1])
-    result.save(out)
+    result.save(out, index=bool(index))
     return result
 
 
@@ -209,12 +226,13 @@ def cloud_files(inputs):
 
 
 def main(argv=None):
-    flags = mask_flags(parser()).parse_args(argv)
+    flags = index_flags(mask_flags(parser())).parse_args(argv)
     tiles = tiling(flags)
     seam = seam_flags(flags)
     voxels = voxeling(flags)
     labels = labeling(flags)
     masks = mask_scoring(flags)
+    lists = indexing(flags)
     if not flags.synthetic and not flags.inputs:
         raise SystemExit("cloud files or a directory (or --synthetic N)")
     if not flags.synthetic and flags.checkpoint is None:
@@ -267,7 +285,7 @@ def main(argv=None):
         found.save(flags.out)
         print("wrote %d files to %s" % (len(found), flags.out))
     if labels is not None:
-        result = write_labels(found, raw, labels, flags.out)
+        result = write_labels(found, raw, labels, flags.out, index=lists)
         print("wrote %d label files to %s" % (len(found), flags.out))
         if masks is not None:
             score_masks(found, result, masks, dev)
